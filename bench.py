@@ -322,6 +322,42 @@ def secondary_legs(dev, sd, headline_precision, steps, note):
     return legs
 
 
+DUMP_BUDGET_BYTES = 60 << 20         # the arrays; the .npy headers stay well inside 64 MB with them
+
+
+def dump_outputs(dump_dir, out, losses, model):
+    """What the last timed step computed, as a caller of Trainer.step receives it -- the model outputs and the loss terms -- plus the
+    parameters its Adam update left, one DIR/<name>.npy each (float64 for float64 and integer tensors, float32 otherwise).  Non-tensor
+    outputs (the wireframe objects) are skipped.  If the whole set exceeds 64 MB, the budget is shared out smallest array first and an
+    array above its share is replaced by a fixed sample of its flattened elements (seeded indices, sorted): the same for every run
+    with the same arguments."""
+    import numpy as np
+    arrays = {}
+    if hasattr(out, "padded"):
+        # networks.JunctionOutputs: the compacted junction entries are built here, not through out[k], which would cache them in the
+        # graph's own output object
+        out = dict(dict.items(out), **{k: v[out.good] for k, v in out.padded.items() if not dict.__contains__(out, k)})
+    for prefix, d in (("out.", out), ("loss.", losses)):
+        for k, v in d.items():
+            if isinstance(v, torch.Tensor):
+                arrays[prefix + k] = v.detach()
+    for k, v in model.named_parameters():
+        arrays["param." + k] = v.detach()
+    for name, t in arrays.items():
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        arrays[name] = t.double() if wide else t.float()
+    left = DUMP_BUDGET_BYTES
+    os.makedirs(dump_dir, exist_ok=True)
+    for i, name in enumerate(sorted(arrays, key=lambda n: (arrays[n].numel() * arrays[n].element_size(), n))):
+        a = arrays[name].cpu().numpy()
+        cap = left // (len(arrays) - i)
+        if a.nbytes > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sock:
@@ -401,7 +437,11 @@ def main():
                          "in total split over the ranks, DTU model switches, strong scaling")
     ap.add_argument("--precision", choices=["fp32", "bf16", "bf16x3", "fp16", "fp16x3"], default=DEFAULT_PRECISION,
                     help="GEMM build: fp32 = exact-f32 MFMA (parity build); bf16 = bf16 MFMA, fp32 accumulate (BASELINE config 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (outputs, loss terms, updated parameters) as DIR/<name>.npy, 64 MB at most")
     args = ap.parse_args()
+    if args.steps < 1 and not args.dry_run:
+        ap.error("--steps must be at least 1: the result line is the time of one timed step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(respawn_under_torchrun(args.gpus))
@@ -499,10 +539,14 @@ def main():
         lib.neat_prof_enable(1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, losses = tr.step(inp, gt)
+        out, losses = tr.step(inp, gt)
     barrier()
     elapsed = time.perf_counter() - t0
     note(f"timed region done: {elapsed:.3f}s for {args.steps} steps")
+    if args.dump_outputs and rank == 0:
+        # untimed, before anything else runs on this trainer: a replayed step's outputs are the graph's static buffers
+        dump_outputs(args.dump_outputs, out, losses, tr.model)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     dist_info = None
     if dist.is_initialized():
         # what a bad scaling curve would be diagnosed from, in the same line: every rank's own time per step (the headline uses the

@@ -1,8 +1,9 @@
-"""Container-side pin of the conf layer: every conf the reference ships parses through neat_amd/conf.py,
-builds the HIP model class, and `synth.ABC_NEAT_A_MODEL_CONF / _LOSS_CONF` -- which every golden fixture and bench.py call "the
-abc-neat-a model" -- equal the `model` / `loss` blocks of the reference's own confs/abc-neat-a.conf key for key.  A silent drift of
-either would invalidate every "this is abc-neat-a" claim.  /root/reference does not exist on the GPU box: skipped there."""
-import glob
+"""Pin of the conf layer: every conf the reference ships parses through neat_amd/conf.py, builds the HIP
+model class, and `synth.ABC_NEAT_A_MODEL_CONF / _LOSS_CONF` -- which every golden fixture and bench.py call "the abc-neat-a model" --
+equal the `model` / `loss` blocks of the reference's own confs/abc-neat-a.conf key for key.  A silent drift of either would
+invalidate every "this is abc-neat-a" claim.  The confs are stored as parsed values in tests/golden/reference_confs.json
+(tests/golden/make_conf_fixture.py); each is rendered back to conf text here and parsed again."""
+import json
 import os
 
 import pytest
@@ -10,8 +11,9 @@ import pytest
 from neat_amd import conf as C
 from neat_amd import synth
 
-CONF_DIR = "/root/reference/code/confs"
-pytestmark = pytest.mark.skipif(not os.path.isdir(CONF_DIR), reason="/root/reference is only present in the build container")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_confs.json")
+with open(FIXTURE) as _f:
+    SHIPPED = json.load(_f)
 
 
 def _plain(node):
@@ -24,19 +26,37 @@ def _plain(node):
     return float(node)
 
 
-def _shipped():
-    return sorted(glob.glob(os.path.join(CONF_DIR, "*.conf")) + glob.glob(os.path.join(CONF_DIR, "*", "*.conf")))
+def _render(node, indent=""):
+    """A parsed tree as conf text: nested `name { ... }` blocks, `key = value`, lists, quoted strings."""
+    if isinstance(node, dict):
+        inner = indent + "    "
+        return "{\n" + "".join(f"{inner}{k} = {_render(v, inner)}\n" for k, v in node.items()) + indent + "}"
+    if isinstance(node, list):
+        return "[" + ", ".join(_render(v, indent) for v in node) + "]"
+    if isinstance(node, bool):
+        return "true" if node else "false"
+    if node is None:
+        return "null"
+    if isinstance(node, str):
+        return json.dumps(node)
+    return repr(node)
+
+
+def _parse(path):
+    text = f"# {path}\n" + "\n".join(f"{k} {_render(v)}" for k, v in SHIPPED[path].items())
+    return C.parse_string(text)
 
 
 def test_all_shipped_confs_are_found():
-    assert len(_shipped()) == 8 and os.path.join(CONF_DIR, "abc-neat-a.conf") in _shipped()
+    assert len(SHIPPED) == 8 and "abc-neat-a.conf" in SHIPPED
 
 
-@pytest.mark.parametrize("path", _shipped() or ["-"], ids=lambda p: os.path.basename(p))
+@pytest.mark.parametrize("path", sorted(SHIPPED), ids=lambda p: os.path.basename(p))
 def test_shipped_conf_parses_and_builds_the_model(path):
     from neat_amd import networks
     from neat_amd.loss import VolSDFLoss
-    tree = C.parse_file(path)
+    tree = _parse(path)
+    assert _plain(tree) == _plain(SHIPPED[path]), path
     for block in ("train", "dataset", "model", "loss"):
         assert isinstance(tree.get_config(block), C.ConfTree), (path, block)
     # the accessors the reference's trainer and model constructor use (volsdf_train.py:141-182, rend_a :258-315)
@@ -54,6 +74,6 @@ def test_shipped_conf_parses_and_builds_the_model(path):
 
 
 def test_synth_conf_is_the_reference_abc_neat_a_conf():
-    tree = C.parse_file(os.path.join(CONF_DIR, "abc-neat-a.conf"))
+    tree = _parse("abc-neat-a.conf")
     assert _plain(tree.get_config("model")) == _plain(synth.ABC_NEAT_A_MODEL_CONF)
     assert _plain(tree.get_config("loss")) == _plain(synth.ABC_NEAT_A_LOSS_CONF)
