@@ -178,7 +178,8 @@ __device__ __forceinline__ void bound_load(const float* __restrict__ z, int n, i
     float v;
     if (order) {
       const int o = order[(size_t)r * n + j];
-      v = o < n_old ? sdf_old[(size_t)r * n_old + o] : sdf_new[(size_t)r * (n - n_old) + (o - n_old)];
+      // (an index outside [0, n) can only come from a corrupted merge: it reads nothing and yields NaN)
+      v = (unsigned)o >= (unsigned)n ? __builtin_nanf("") : o < n_old ? sdf_old[(size_t)r * n_old + o] : sdf_new[(size_t)r * (n - n_old) + (o - n_old)];
     } else {
       v = sdf_new[(size_t)r * n + j];
     }
@@ -346,20 +347,23 @@ __device__ __forceinline__ void resample_draw(const float* sz, const float* scdf
   }
 }
 
-// sorted union of z (sorted) and the new samples (sorted: u is increasing): rank by binary search, old first on ties (:254)
+// sorted union of z (sorted) and the new samples (sorted: u is increasing): rank by binary search, old first on ties (:254).
+// NaN ranks above every number, as torch.sort places it: a ray whose sdf values are NaN draws NaN samples (its cdf is NaN), and with
+// IEEE compares their ranks would collide and leave slots of `order` unwritten -- indices the next round's bound_load gathers with.
+// For finite values both compares are the plain < and <=.
 __device__ __forceinline__ void resample_merge(const float* sz, const float* ssmp, int n, int N, float* __restrict__ z_merged,
                                                int* __restrict__ order, int tid) {
   for (int j = tid; j < n; j += BOUND_T) {
     const float v = sz[j];
     int lo = 0, hi = N;                          // #samples < v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ssmp[mid] < v) lo = mid + 1; else hi = mid; }
+    while (lo < hi) { const int mid = (lo + hi) >> 1; const float s = ssmp[mid]; if (s < v || (v != v && s == s)) lo = mid + 1; else hi = mid; }
     z_merged[j + lo] = v;
     order[j + lo] = j;
   }
   for (int k = tid; k < N; k += BOUND_T) {
     const float v = ssmp[k];
     int lo = 0, hi = n;                          // #z <= v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (sz[mid] <= v) lo = mid + 1; else hi = mid; }
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (sz[mid] <= v || v != v) lo = mid + 1; else hi = mid; }
     z_merged[k + lo] = v;
     order[k + lo] = n + k;
   }

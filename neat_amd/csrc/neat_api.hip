@@ -1852,7 +1852,13 @@ int neat_sdf_values_rays(const float* packed, const neat_net_params* net, const 
   return rc;
 }
 
-int neat_sdf_ldp(int P, int precision) { return P <= 0 ? 0 : round_ldp(P, precision); }
+// the point stride that neat_sdf_ws_floats sized the workspace with and the forward reads: the precision code is mapped the way every
+// entry point maps it (bf16x3 runs the F32 layouts at the 64-point stride; NEAT_F16 / NEAT_F16X3 share the 16-bit granule)
+int neat_sdf_ldp(int P, int precision) {
+  const int x3 = take_x3(precision); (void)x3;
+  const int hx3 = take_hx3(precision); (void)hx3;
+  return P <= 0 ? 0 : round_ldp(P, precision);
+}
 
 int neat_sdf_values_laid_out(const float* packed, const neat_net_params* net, int P, int precision, float radius, float scale, float* ws,
                              float* sdf, const int* gate, int gate_value, void* stream) {

@@ -46,6 +46,20 @@ def test_workspace_queries_are_consistent():
     assert lib.neat_render_ws_floats(64, 32, 8, 3) == lib.neat_render_ws_floats(64, 32, 8, 1)
     assert lib.neat_render_eval_ws_floats(64, 32, 3) == lib.neat_render_eval_ws_floats(64, 32, 1)
     assert lib.neat_sdf_ws_floats(100, 1, 3) == lib.neat_sdf_ws_floats(100, 1, 1) and lib.neat_heads_ws_floats(100, 3) == lib.neat_heads_ws_floats(100, 1)
+    # neat_sdf_ldp = the x-row stride the sampler's launches write a query at (ops.sdf_query_workspace): it must be the stride the
+    # values-mode forward reads and neat_sdf_ws_floats sized the workspace with, for every precision code (bf16x3 runs the fp32
+    # layouts; fp16 / fp16x3 / fp16x3-fast the 16-bit ones)
+    for P in (1, 63, 64, 65, 127, 128, 129):
+        assert lib.neat_sdf_ldp(P, 2) == lib.neat_sdf_ldp(P, 0), P
+        assert lib.neat_sdf_ldp(P, 4) == lib.neat_sdf_ldp(P, 5) == lib.neat_sdf_ldp(P, 1) == lib.neat_sdf_ldp(P, 3), P
+        for prec, tile in ((0, 64), (2, 64), (1, 128), (3, 128), (4, 128), (5, 128)):
+            ldp = lib.neat_sdf_ldp(P, prec)
+            assert ldp >= P and ldp % tile == 0 and ldp - P < tile, (P, prec, ldp)
+            # the workspace was sized with the same granule: P and ldp land on the same size
+            assert lib.neat_sdf_ws_floats(P, 0, prec) == lib.neat_sdf_ws_floats(ldp, 0, prec), (P, prec)
+            if ldp > tile:
+                assert lib.neat_sdf_ws_floats(ldp - tile, 0, prec) < lib.neat_sdf_ws_floats(P, 0, prec), (P, prec)
+    assert lib.neat_sdf_ldp(0, 2) == 0
 
 
 def test_copy_batch_rejects_bad_arguments_before_any_launch():

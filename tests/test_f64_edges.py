@@ -1,0 +1,556 @@
+"""The HIP kernels against a float64 run of the oracle (tests/f64_reference.py) at the point counts where tiled kernels go wrong:
+either side of the 64-point fp32 tile, the 128-point 16-bit granule (BMH), the 32-point x3 half batch, one persistent round of the
+chains (g_ws_grid = 256 workgroups x 64 points = 16384) and the x3 chains' ragged last round (64 * 257 - 5).
+
+Float64 removes the oracle's own rounding from the comparison, so every number measured here is the kernel's error.  Per build the
+bars are the existing ones for the same quantity (TOL for the fp32-grade builds, the 2e-3 / F16X3_GAIN_BAR gradient bars,
+HALF_BOUNDS / BF16_GRAD_REL_L2 for the 16-bit builds) or tighter where the float64 measurement showed the build far inside them.
+NEAT_F64_TABLE=<path> writes every measured error as JSON lines (build, entry point, size, error)."""
+import json
+import os
+
+import pytest
+import torch
+
+from neat_amd import synth
+from tests import f64_reference as ref
+from tests.test_gpu_parity import BF16_GRAD_REL_L2, F16X3_GAIN_BAR, HALF_BOUNDS, TOL, build_model, close_sampler
+
+pytestmark = pytest.mark.gpu
+T = torch.tensor
+SEED, VARIANT = 42, "rough"
+WITH_BF16X3 = os.environ.get("NEAT_TEST_BF16X3") == "1"
+BUILDS = ["fp32", "fp16x3", "fp16", "bf16"] + (["bf16x3"] if WITH_BF16X3 else [])
+SIZES = [1, 31, 33, 63, 64, 65, 127, 128, 129, 255, 16383, 16385, 64 * 257 - 5]
+GRAD_SIZES = [33, 129, 16385, 64 * 257 - 5]
+P_POOL = 16512                      # the largest size rounded up to 128 (the zero-cotangent padding check)
+RADIUS, SCALE = ref.RADIUS, ref.SCALE
+
+# output bars per build: (sdf / feature values, normals, head outputs and rendered values).  Measured against float64 on MI355X
+# (max over every size; relative to max(1, |ref|)): fp32 values 9.2e-7, normals 1.6e-6, heads 6.7e-8, main pass 1.8e-7; fp16x3 9.7e-7 /
+# 3.6e-6 / 8.5e-8 / 1.8e-7; fp16 7.9e-4 / 1.8e-3 / 4.5e-5 / 2.0e-4 (its sdf); bf16 6.7e-3 / 1.5e-2 / 3.6e-4 / 1.7e-3.  Where that is
+# far inside the existing bar (TOL = 1e-4; HALF_BOUNDS) the bar here is ~4x the measurement; bf16x3 keeps TOL (not measured by default).
+OUT_BARS = {"fp32": (4e-6, 8e-6, 1e-6), "fp16x3": (4e-6, 1.5e-5, 1e-6), "bf16x3": (TOL, TOL, TOL)}
+for _b, _head in (("fp16", 2e-4), ("bf16", 1.5e-3)):
+    _o, _s, _n, _l, _g = HALF_BOUNDS[_b]
+    OUT_BARS[_b] = (_s, _n, min(_o, _head))
+# gradient bars: fp32-grade builds max |g - g64| / max |g64| per tensor; 16-bit builds relative L2 per tensor.  Measured: fp32 8.1e-6
+# through the SDF network alone, 2.2e-4 through the main pass (vs 2e-3: tightened to 5e-5 / 1e-3); fp16x3 1.2e-3 / 2.6e-3 (a gain
+# tensor; bars unchanged); fp16 6.3e-3 / 3.7e-2 and bf16 4.9e-2 / 0.107 relative L2 at >= 1024 points (bars unchanged)
+GRAD_MAX_BAR = {"fp32": 1e-3, "fp16x3": 2e-3, "bf16x3": 2e-2}
+SDF_GRAD_MAX_BAR_FP32 = 5e-5
+GRAD_REL_L2 = {"fp16": HALF_BOUNDS["fp16"][4], "bf16": BF16_GRAD_REL_L2}
+
+_TABLE = []
+
+
+def record(build, entry, P, err):
+    _TABLE.append({"build": build, "entry": entry, "P": P, "err": float(err)})
+    return err
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_table():
+    yield
+    path = os.environ.get("NEAT_F64_TABLE")
+    if path and _TABLE:
+        with open(path, "a") as f:
+            for row in _TABLE:
+                f.write(json.dumps(row) + "\n")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    from neat_amd import _lib
+    _lib.lib()
+    return torch.device("cuda:0")
+
+
+_MODELS = {}
+
+
+def model(dev, build):
+    m = _MODELS.get(build)
+    if m is None:
+        m = _MODELS[build] = build_model(dev, VARIANT, seed=SEED, precision=build)
+    return m
+
+
+def rel_err(a, b):
+    """max |a - b| relative to max(1, max |b|) (test_gpu_parity.close's measure); a may live on the GPU, b is float64."""
+    a = a.detach().cpu().to(torch.float64)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    assert torch.isfinite(a).all(), "non-finite values"
+    if a.numel() == 0:
+        return 0.0
+    return float((a - b).abs().max()) / max(1.0, float(b.abs().max()))
+
+
+def check(build, entry, P, a, b, bar):
+    err = record(build, entry, P, rel_err(a, b))
+    assert err <= bar, f"{build} {entry} P={P}: err {err:.3e} > {bar:.1e}"
+
+
+def points(n, seed=0):
+    """Seeded points in [-2, 2]^3; every 37th lies outside the bounding sphere (|x| in [3.1, 4]) so the clamp branch is taken."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.rand(n, 3, generator=g) * 4 - 2
+    far = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=1) * (3.1 + 0.9 * torch.rand(n, 1, generator=g))
+    out = torch.arange(n) % 37 == 5
+    x[out] = far[out]
+    return x
+
+
+def unit(n, seed):
+    return torch.nn.functional.normalize(torch.randn(n, 3, generator=torch.Generator().manual_seed(seed)), dim=1)
+
+
+def _pool():
+    return ref.cached("pool", lambda: (points(P_POOL), unit(P_POOL, 1)))
+
+
+def _sdf_ref():
+    """float64 forwards at every point of the pool (per point: the reference of X[:P] is the first P rows)."""
+    def make():
+        x, view = _pool()
+        p = ref.params(SEED, VARIANT)
+        r = ref.sdf_forward(p, x)
+        r["rgb"], r["lines"] = ref.heads(p, x, r["grad"].float(), view, r["feat"].float())
+        return r
+    return ref.cached("sdf", make)
+
+
+def _rays_ref():
+    """o + z d = the pool's points up to one rounding; the float64 reference is taken at the float64 o + z d."""
+    def make():
+        x, _ = _pool()
+        d = unit(P_POOL, 2)
+        z = 0.5 + 1.5 * torch.rand(P_POOL, 1, generator=torch.Generator().manual_seed(3))
+        o = x - z * d
+        pts = ref.f64(o) + ref.f64(z) * ref.f64(d)
+        p = ref.params(SEED, VARIANT)
+        with torch.no_grad():
+            v = O_sdf_values(p, pts)
+        return o, d, z, v
+    return ref.cached("rays", make)
+
+
+def O_sdf_values(p, x64):
+    from oracle import neat_oracle as O
+    return O.sdf_values(p, x64, RADIUS, SCALE)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (a) SDF network forwards and (b) heads, against float64, with prefix identity
+# ------------------------------------------------------------------------------------------------------------------------------
+def _forwards(m, x, o, d, z, fast_too):
+    from neat_amd import ops
+    net = m.implicit_network
+    h = m.handle()
+    ctl = torch.tensor([0, 1, 0], dtype=torch.int32, device=x.device)
+    with torch.no_grad():
+        res = {"forward": net(x), "sdf_vals": net.get_sdf_vals(x)}
+        res["sdf"], res["feat"], res["grad"] = net.get_outputs(x)
+        res["grad_raw"] = net.gradient(x)
+        res["rays"] = ops.sdf_values_rays(h, o, d, z, RADIUS, SCALE)
+        res["gated_open"] = ops.sdf_values(h, x, RADIUS, SCALE, gate=(ctl, 1, 1))
+        res["gated_shut"] = ops.sdf_values(h, x, RADIUS, SCALE, gate=(ctl, 0, 1))
+        if fast_too:
+            res["fast"] = ops.sdf_values(h, x, RADIUS, SCALE, fast=True)
+    return {k: v.clone() for k, v in res.items()}
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_sdf_forwards_vs_float64(dev, build):
+    x_all, view_all = _pool()
+    o_all, d_all, z_all, rays64 = _rays_ref()
+    r64 = _sdf_ref()
+    m = model(dev, build)
+    b_val, b_nrm, b_head = OUT_BARS[build]
+    fast_too = build == "fp16x3"
+    Pm = max(SIZES)
+    big = _forwards(m, x_all[:Pm].to(dev), o_all[:Pm].to(dev), d_all[:Pm].to(dev), z_all[:Pm].to(dev), fast_too)
+    for P in SIZES:
+        x = x_all[:P].to(dev)
+        got = _forwards(m, x, o_all[:P].to(dev), d_all[:P].to(dev), z_all[:P].to(dev), fast_too) if P != Pm else big
+        for k, r64k, bar in (("forward", "forward", b_val), ("sdf_vals", "sdf_vals", b_val), ("sdf", "sdf", b_val), ("feat", "feat", b_val),
+                             ("grad", "grad", b_nrm), ("grad_raw", "grad_raw", b_nrm), ("gated_open", "sdf_vals", b_val)):
+            check(build, k, P, got[k], r64[r64k][:P], bar)
+        check(build, "sdf_values_rays", P, got["rays"], rays64[:P], b_val)
+        if fast_too:      # the one-product f16 chain of NEAT_F16X3_FASTVALUES: the fp16 build's values bar
+            check(build, "fast_values", P, got["fast"], r64["sdf_vals"][:P], HALF_BOUNDS["fp16"][1])
+        # the gate open is the ungated query; every output of X[:P] is the first P rows of the same call on X[:Pmax]
+        assert torch.equal(got["gated_open"], got["sdf_vals"]), (build, P)
+        for k, v in got.items():
+            if k == "gated_shut":       # (nothing written: whatever torch.empty returned, checked in test_stale_workspace_changes_nothing)
+                continue
+            diff = float((v.double() - big[k][:P].double()).abs().max()) if v.numel() else 0.0
+            record(build, "prefix_" + k, P, diff)
+            assert torch.equal(v, big[k][:P]), f"{build} {k}: X[:{P}] differs from the first {P} rows of X[:{Pm}] by {diff:.3e}"
+        # (b) heads on the float64 get_outputs of the same points
+        with torch.no_grad():
+            args = (x, r64["grad"][:P].float().to(dev), view_all[:P].to(dev), r64["feat"][:P].float().to(dev))
+            rgb = m.rendering_network(*args)
+            lines = m.attraction_network(*args)
+        check(build, "rendering_network", P, rgb, r64["rgb"][:P], b_head)
+        check(build, "attraction_network", P, lines, r64["lines"][:P], b_head)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (c) parameter gradients through the double backward, and the zero-cotangent padding check
+# ------------------------------------------------------------------------------------------------------------------------------
+def _cot(shape, seed):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+
+
+def _sdf_cots():
+    return ref.cached("sdf_cots", lambda: (_cot((P_POOL, 1), 11), _cot((P_POOL, 256), 12) * 0.05, _cot((P_POOL, 3), 13)))
+
+
+def _sdf_grads_ref(P):
+    x, _ = _pool()
+    a, b, c = _sdf_cots()
+    return ref.cached(("sdf_grads", P), lambda: ref.sdf_param_grads(SEED, VARIANT, x[:P], a[:P], b[:P], c[:P]))
+
+
+def _gpu_sdf_grads(m, x, a, b, c):
+    m.zero_grad(set_to_none=True)
+    sdf, feat, grad = m.implicit_network.get_outputs(x)
+    ((sdf * a).sum() + (feat * b).sum() + (grad * c).sum()).backward()
+    return {k: p.grad.detach().cpu().clone() for k, p in m.named_parameters() if p.grad is not None}
+
+
+def _pad(P):
+    return (P + 127) // 128 * 128
+
+
+# Builds whose backward pass is 16-bit (NEAT_F16X3 runs the fp16 build's): their gradient bars were measured on train steps of
+# 1 650 .. 262 000 points and hold there; below ~1 000 points a thin tensor's gradient is a sum of few 16-bit-rounded terms and measured
+# up to ~1.9x the bar (fp16x3 rendering_network.lin4.weight_g 5.6e-3 at 896 points; relative L2 of thin bias tensors fp16 9.7e-2,
+# bf16 0.19 at 64 .. 896 points).
+# There the error is recorded, not asserted; the zero-cotangent padding check holds at every size.
+HALF_BACKWARD = ("fp16x3", "fp16", "bf16")
+HALF_BACKWARD_MIN_P = 1024
+
+
+def _grad_err(build, k, g, r, sdf_only=False):
+    if build in GRAD_MAX_BAR:
+        bar = SDF_GRAD_MAX_BAR_FP32 if (sdf_only and build == "fp32") else GRAD_MAX_BAR[build]
+        if build == "fp16x3" and k.endswith("weight_g"):
+            bar = max(bar, F16X3_GAIN_BAR)
+        return float((g - r).abs().max()) / max(float(r.abs().max()), 1e-6), bar
+    if r.numel() < 2:
+        return 0.0, 1.0
+    return float((g - r).norm() / (r.norm() + 1e-30)), GRAD_REL_L2[build]
+
+
+def grad_errors(build, entry, P, got, want, want32=None, sdf_only=False):
+    """Every parameter gradient against float64 at the build's bar -> worst measured error.  want32 (the float32 oracle's gradients):
+    each tensor's bar grows by the float32 oracle's own error against float64 -- the part of the error that the reference's float32
+    formulas make whoever evaluates them (the kernels reproduce them)."""
+    worst = 0.0
+    assert set(want) <= set(got), sorted(set(want) - set(got))
+    for k, r in want.items():
+        g = got[k].to(torch.float64).reshape(r.shape)
+        assert torch.isfinite(g).all(), (build, entry, P, k)
+        err, bar = _grad_err(build, k, g, r, sdf_only)
+        if want32 is not None:
+            bar += _grad_err(build, k, want32[k].to(torch.float64).reshape(r.shape), r)[0]
+        worst = max(worst, err)
+        if build in HALF_BACKWARD and P < HALF_BACKWARD_MIN_P:
+            continue
+        assert err <= bar, f"{build} {entry} P={P} {k}: {err:.3e} > {bar:.1e}"
+    return record(build, entry, P, worst)
+
+
+def pad_agreement(build, entry, P, a, b):
+    """max over tensors of |a - b| / max |a|: two runs that differ only by zero-cotangent points past P."""
+    worst = 0.0
+    assert set(a) == set(b)
+    for k in a:
+        worst = max(worst, float((a[k].double() - b[k].double()).abs().max()) / max(float(a[k].abs().max()), 1e-30))
+    return record(build, entry, P, worst)
+
+
+# padded runs must agree far more tightly than either agrees with float64: only the order of fp32 partial sums may change (measured
+# 0 for fp32, <= 4.1e-7 of a tensor's max for the 16-bit builds)
+PAD_BAR = 2e-6
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("P", GRAD_SIZES)
+def test_sdf_parameter_gradients_vs_float64(dev, build, P):
+    x_all, _ = _pool()
+    a, b, c = _sdf_cots()
+    want = _sdf_grads_ref(P)
+    m = model(dev, build).train()
+    try:
+        got = _gpu_sdf_grads(m, x_all[:P].to(dev), a[:P].to(dev), b[:P].to(dev), c[:P].to(dev))
+        grad_errors(build, "sdf_param_grads", P, got, want, sdf_only=True)
+        Pp = _pad(P)
+        z = lambda t: torch.cat([t[:P], torch.zeros_like(t[P:Pp])])
+        padded = _gpu_sdf_grads(m, x_all[:Pp].to(dev), z(a).to(dev), z(b).to(dev), z(c).to(dev))
+        err = pad_agreement(build, "sdf_param_grads_zero_pad", P, got, padded)
+        assert err <= PAD_BAR, f"{build} P={P}: zero-cotangent points past P change the gradients by {err:.3e}"
+    finally:
+        m.zero_grad(set_to_none=True)
+        m.eval()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (e) the main pass: render_rays forward + backward (all parameters and beta) and render_rays_eval, against oracle.render_rays
+# ------------------------------------------------------------------------------------------------------------------------------
+RENDER_SHAPES = [(1, 1), (1, 64), (3, 65), (5, 63), (2, 129), (7, 128)]
+# (R, S, E): R S + E = the gradient sizes; the E extra points go through the SDF network only (the eikonal term), so the heads' tile
+# grid holds columns that no head output consumes
+RENDER_GRAD_SHAPES = [(4, 8, 1), (2, 64, 1), (128, 128, 1), (128, 128, 59)]
+
+
+def _scene(R, S, seed):
+    g = torch.Generator().manual_seed(seed)
+    cam = torch.nn.functional.normalize(torch.randn(1, 3, generator=g), dim=1) * 3.5
+    target = (torch.rand(R, 3, generator=g) - 0.5) * 1.2
+    d = torch.nn.functional.normalize(target - cam, dim=1)
+    z = torch.sort(torch.rand(R, S, generator=g) * 6.0, -1)[0]
+    return cam.expand(R, 3).contiguous(), d, z
+
+
+def _render_cots(R, S, E, seed):
+    g = torch.Generator().manual_seed(seed)
+    c = {"rgb_values": torch.randn(R, 3, generator=g), "lines3d": torch.randn(R, 2, 3, generator=g),
+         "depth": torch.randn(R, generator=g), "xyz": torch.randn(R, 3, generator=g)}
+    if E:
+        c["eik_grad"] = torch.randn(E, 3, generator=g)
+    return c
+
+
+def _gpu_render(m, o, d, z, eik, cot, dev):
+    from neat_amd import ops
+    m.zero_grad(set_to_none=True)
+    dn = m.density
+    out = ops.render_rays(m.handle(), o.to(dev), d.to(dev), z.to(dev), dn.beta, RADIUS, SCALE, False,
+                          eik.to(dev) if eik is not None else None, None, dn.beta_min)
+    names = ("rgb_values", "lines3d", "depth", "xyz", "eik_grad", "weights", "sdf_samples", "points")
+    res = dict(zip(names, out[:8]))
+    loss = sum((res[k] * c.to(dev)).sum() for k, c in cot.items())
+    loss.backward()
+    grads = {k: p.grad.detach().cpu().clone() for k, p in m.named_parameters() if p.grad is not None}
+    return {k: v.detach().clone() for k, v in res.items()}, grads
+
+
+def _render_outputs(build, entry, RS, got, want, want32):
+    """Outputs of the main pass against float64; each bar grows by the float32 oracle's own error against float64.  That is not
+    negligible everywhere: the density 0.5 + 0.5 sign(s) expm1(-|s| / beta) (density.py:30) cancels in float32 for s >> beta, and the
+    last interval of every ray is 1e10 long (rend_a :545), so a ray's last weight reads that cancellation amplified -- measured on a
+    ray of ONE sample: the float32 oracle's depth is 1.04e-4 off float64, the kernels' identically (every build), and the float32
+    oracle's gradients of that ray are off by 100 %."""
+    b_val, b_nrm, b_head = OUT_BARS[build]
+    R, S = RS[:2]
+    for k, bar in (("rgb_values", b_head), ("lines3d", b_head), ("depth", b_head), ("xyz", b_head), ("weights", b_head),
+                   ("sdf_samples", b_val)):
+        check(build, f"{entry}:{k}", R * S, got[k].reshape(want[k].shape), want[k], bar + rel_err(want32[k], want[k]))
+    if "eik_grad" in want:
+        check(build, f"{entry}:eik_grad", R * S, got["eik_grad"], want["eik_grad"], b_nrm)
+
+
+def _render_ref(R, S, E, seed):
+    def make():
+        o, d, z = _scene(R, S, seed)
+        eik = points(E, seed + 100) if E else None
+        cot = _render_cots(R, S, E, seed)
+        out, grads = ref.render(SEED, VARIANT, o, d, z, eik, cot)
+        out32, grads32 = ref.render(SEED, VARIANT, o, d, z, eik, cot, dtype=torch.float32)
+        return o, d, z, eik, cot, out, grads, out32, grads32
+    return ref.cached(("render", R, S, E, seed), make)
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("R,S", RENDER_SHAPES)
+def test_render_rays_vs_float64(dev, build, R, S):
+    from neat_amd import ops
+    o, d, z, _, cot, want, want_g, want32, want_g32 = _render_ref(R, S, 0, R * 1000 + S)
+    m = model(dev, build).train()
+    try:
+        got, grads = _gpu_render(m, o, d, z, None, cot, dev)
+    finally:
+        m.zero_grad(set_to_none=True)
+        m.eval()
+    _render_outputs(build, "render_rays", (R, S), got, want, want32)
+    grad_errors(build, "render_rays_grads", R * S, grads, want_g, want_g32)
+    with torch.no_grad():
+        ev = ops.render_rays_eval(m.handle(), o.to(dev), d.to(dev), z.to(dev), m.density.beta, RADIUS, SCALE, False, m.density.beta_min)
+    names = ("rgb_values", "lines3d", "depth", "xyz", "eik_grad", "weights", "sdf_samples", "points")
+    _render_outputs(build, "render_rays_eval", (R, S), dict(zip(names, ev[:8])), want, want32)
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("R,S,E", RENDER_GRAD_SHAPES)
+def test_render_parameter_gradients_vs_float64(dev, build, R, S, E):
+    """Every parameter gradient (SDF network, both heads, weight_g and weight_v, density.beta) of a main pass with E extra points, and
+    the same pass with the extra points padded to the 128-point granule by points whose eikonal cotangent is zero."""
+    o, d, z, eik, cot, want, want_g, want32, want_g32 = _render_ref(R, S, E, R * 1000 + S + E)
+    P = R * S + E
+    m = model(dev, build).train()
+    try:
+        got, grads = _gpu_render(m, o, d, z, eik, cot, dev)
+        Ep = E + _pad(P) - P
+        eik_p = torch.cat([eik, points(Ep - E, 7)[: Ep - E]]) if Ep > E else eik
+        cot_p = dict(cot, eik_grad=torch.cat([cot["eik_grad"], torch.zeros(Ep - E, 3)]))
+        _, grads_p = _gpu_render(m, o, d, z, eik_p, cot_p, dev)
+    finally:
+        m.zero_grad(set_to_none=True)
+        m.eval()
+    _render_outputs(build, "render_rays_eik", (R, S), got, want, want32)
+    grad_errors(build, "render_param_grads", P, grads, want_g, want_g32)
+    err = pad_agreement(build, "render_param_grads_zero_pad", P, grads, grads_p)
+    assert err <= PAD_BAR, f"{build} P={P}: zero-cotangent points past P change the gradients by {err:.3e}"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (d) the sampler's laid-out query: the stride the sampler writes at is the stride the values kernels read at
+# ------------------------------------------------------------------------------------------------------------------------------
+# (R, N_samples_eval): R N mod 128 = 0, 1, 64, 64, 65, 127
+STRIDE_SHAPES = [(2, 64), (43, 3), (1, 64), (3, 64), (5, 13), (1, 127)]
+# the tolerance of test_gpu_parity.test_sampler_prologue_and_ray_queries (the points differ by one fma rounding); fp16 (and the fast
+# values of fp16x3) at the fp16 build's values bar, bf16x3 at the fp32-grade TOL
+STRIDE_TOL = {"fp32": 2e-6, "fp16x3": 5e-6, "bf16": 2e-2, "fp16": HALF_BOUNDS["fp16"][1], "bf16x3": TOL, "fp16x3-fast": HALF_BOUNDS["fp16"][1]}
+
+
+@pytest.mark.parametrize("build", ["fp32", "fp16x3", "fp16x3-fast", "fp16", "bf16", "bf16x3"])
+@pytest.mark.parametrize("R,N", STRIDE_SHAPES)
+def test_sampler_workspace_stride(dev, build, R, N):
+    from neat_amd import ops
+    fast = build.endswith("-fast")
+    m = model(dev, build.replace("-fast", ""))
+    h = m.handle()
+    P = R * N
+    g = torch.Generator().manual_seed(P)
+    o = (torch.randn(R, 3, generator=g) * 0.3).to(dev)
+    d = unit(R, P).to(dev)
+    z = torch.sort(torch.rand(R, N, generator=g) * 4.0 + 0.1, -1)[0].to(dev)
+    with torch.no_grad():
+        ws, ldp = ops.sdf_query_workspace(h, P, dev, fast)
+        assert ldp >= P and ws.numel() >= 3 * ldp
+        ws.fill_(float("nan"))
+        ops.sampler_init_rays(z, m.density.beta, m.density.beta_min, m.ray_sampler._beta_c, 11, o, d, ws, ldp, None, 0, 0, 0)
+        laid = ops.sdf_values_laid_out(h, ws, P, RADIUS, SCALE, fast=fast)
+        pts = torch.addcmul(o.unsqueeze(1), z.unsqueeze(2), d.unsqueeze(1)).reshape(-1, 3)
+        direct = ops.sdf_values(h, pts, RADIUS, SCALE, fast=fast)
+    assert torch.isfinite(laid).all(), f"{build} P={P}: the query read workspace rows the sampler never wrote (ldp {ldp})"
+    err = record(build, "sdf_values_laid_out", P, rel_err(laid, direct.double().cpu()))
+    assert err <= STRIDE_TOL[build], f"{build} P={P}: laid-out query differs from the explicit points by {err:.3e}"
+
+
+def test_bf16x3_sampler_with_ragged_query_matches_fp32(dev):
+    """ErrorBoundSampler.get_z_vals with N_samples_eval = 50 (R Ne mod 128 = 10, inside the range the wrong stride misplaces) on the
+    bf16x3 build reproduces the fp32 build's depths."""
+    from neat_amd import networks, rend_util
+    conf = dict(synth.ABC_NEAT_A_MODEL_CONF, ray_sampler=dict(synth.ABC_NEAT_A_MODEL_CONF["ray_sampler"], N_samples_eval=50))
+    R = 77
+    sc = synth.synth_scene(seed=3, n_rays=R)
+    d, c = rend_util.get_camera_params(T(sc["uv"]).to(dev), T(sc["pose"]).to(dev), T(sc["intrinsics"]).to(dev))
+    d = d.reshape(-1, 3)
+    c = c.expand(d.shape[0], 3).contiguous()
+    zs = {}
+    for build in ("fp32", "bf16x3"):
+        m = networks.VolSDFNetwork(conf)
+        m.load_state_dict({k: T(v) for k, v in synth.synth_state_dict(SEED, VARIANT).items()})
+        m.to(dev).eval().set_precision(build)
+        m.ray_sampler.sync_free = True          # the laid-out queries (sdf_query_workspace / sampler_init_rays / sampler_round)
+        with torch.no_grad():
+            zs[build] = m.ray_sampler.get_z_vals(d, c, m)[0]
+    assert zs["fp32"].shape == (R, 64 + 2 + 32)
+    close_sampler(zs["bf16x3"], zs["fp32"].cpu().numpy(), what="bf16x3 vs fp32 depths, N_samples_eval = 50")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (f) stale workspace: every float32 buffer the Python layer allocates starts as NaN
+# ------------------------------------------------------------------------------------------------------------------------------
+class _PoisonedTorch:
+    """neat_amd.ops' view of torch with empty() returning NaN-filled floating-point tensors."""
+
+    def __init__(self):
+        self._empty = torch.empty
+
+    def empty(self, *a, **k):
+        t = self._empty(*a, **k)
+        if t.is_floating_point():
+            t.fill_(float("nan"))
+        return t
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_stale_workspace_changes_nothing(dev, build, monkeypatch):
+    from neat_amd import ops
+    x_all, _ = _pool()
+    o_all, d_all, z_all, _ = _rays_ref()
+    a, b, c = _sdf_cots()
+    P = 129
+    m = model(dev, build)
+    x = x_all[:P].to(dev)
+    args = (x, o_all[:P].to(dev), d_all[:P].to(dev), z_all[:P].to(dev), False)
+    cots = (a[:P].to(dev), b[:P].to(dev), c[:P].to(dev))
+    R, S = 3, 65
+    ro, rd, rz, _, rcot = _render_ref(R, S, 0, R * 1000 + S)[:5]
+
+    def run():
+        fw = _forwards(m, *args)
+        m.train()
+        try:
+            sg = _gpu_sdf_grads(m, x, *cots)
+            rout, rg = _gpu_render(m, ro, rd, rz, None, rcot, dev)
+        finally:
+            m.zero_grad(set_to_none=True)
+            m.eval()
+        return fw, sg, rout, rg
+
+    clean = run()
+    monkeypatch.setattr(ops, "torch", _PoisonedTorch())
+    poisoned = run()
+    for part in range(4):
+        for k, v in clean[part].items():
+            if part == 0 and k == "gated_shut":
+                continue
+            w = poisoned[part][k]
+            assert torch.isfinite(w).all(), (build, part, k)
+            assert torch.equal(v, w), (build, part, k, float((v.double() - w.double()).abs().max()))
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_shut_gate_writes_nothing(dev, build, monkeypatch):
+    """neat_sdf_values_gated returns at once unless *gate == gate_value (include/neat_hip.h): with the gate shut the output keeps what
+    it held.  The fused chain of the 16-bit builds takes the gate; the fp32 layer launches (fp32, bf16x3) do not, and evaluate the
+    query anyway -- harmless for the sampler (no launch reads a shut round's values) but not what the ABI promises."""
+    from neat_amd import ops
+    if build in ("fp32", "bf16x3"):
+        pytest.xfail("the fp32 layer kernels and sdf_finalize_kernel are not gated")
+    m = model(dev, build)
+    x = _pool()[0][:129].to(dev)
+    ctl = torch.tensor([0, 1, 0], dtype=torch.int32, device=dev)
+    monkeypatch.setattr(ops, "torch", _PoisonedTorch())
+    with torch.no_grad():
+        shut = ops.sdf_values(m.handle(), x, RADIUS, SCALE, gate=(ctl, 0, 1))
+    assert torch.isnan(shut).all()
+
+
+def test_sampler_merge_is_a_permutation_for_nan_sdf(dev):
+    """A refine resampling of rays whose sdf values are NaN draws NaN samples; the merged grid's gather order must still be a
+    permutation of the n + N slots (NaN ranks last, as torch.sort puts it) -- the next round gathers the merged sdf with it."""
+    from neat_amd import ops
+    R, n, N = 5, 50, 50
+    g = torch.Generator().manual_seed(9)
+    z = torch.sort(torch.rand(R, n, generator=g) * 6.0, -1)[0].to(dev)
+    sdf = torch.randn(R, n, generator=g).to(dev)
+    sdf[1:3] = float("nan")                       # two rays NaN throughout, one with a single NaN
+    sdf[4, 7] = float("nan")
+    beta = torch.full((R,), 0.1, device=dev)
+    u = torch.linspace(0.0, 1.0, N, device=dev)
+    _, zm, order = ops.sampler_resample(z, sdf, beta, u, refine=True)
+    want = torch.arange(n + N, device=dev, dtype=order.dtype)
+    for r in range(R):
+        assert torch.equal(torch.sort(order[r])[0], want), r
+    assert torch.equal(zm[0], torch.sort(zm[0])[0])   # a finite ray: the sorted union as before
