@@ -37,7 +37,7 @@ typedef struct neat_net_grads {
   float* db[NEAT_NUM_LAYERS];
 } neat_net_grads;
 
-int neat_abi_version(void);      /* 13 */
+int neat_abi_version(void);      /* 14 */
 
 /* `precision` selects the build of the GEMM-class kernels:
  *   NEAT_F32  (0): exact-f32 MFMA, fp32 activations  -- parity build (outputs within 1e-4 of the reference)
@@ -100,6 +100,15 @@ int neat_sdf_forward(const float* packed, const neat_net_params* net, const floa
 int neat_sdf_backward(const float* packed, const neat_net_params* net, float* ws, int P, int precision,
                       const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
                       const neat_net_grads* grads, void* stream);
+/* ABI v14: neat_sdf_backward, differentiated in the query points x as well (rend_a :111-137 are plain autograd in x: get_outputs,
+ * gradient, forward and get_sdf_vals; the normal, built with create_graph=True at :121-127, included).  Same arguments plus
+ * scale (the forward's sphere scale: the clamped sdf s (radius - |x|) and its gradient -s x/|x| depend on it) and d_x [P,3] row-major,
+ * which receives dL/dx of L = <d_out257, forward()> + <d_sdf, sdf> + <d_feat, feat> + <d_grad, d sdf/dx>, first order (d_x itself is
+ * not differentiable).  grads may be NULL, and so may any layer's dv/dg/db (all three together): no weight gradient is formed for those
+ * layers -- a frozen network whose input points are optimised.  The parameter gradients it does write equal neat_sdf_backward's. */
+int neat_sdf_backward_x(const float* packed, const neat_net_params* net, float* ws, int P, int precision, float scale,
+                        const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
+                        const neat_net_grads* grads, float* d_x, void* stream);
 
 /* ---- a6+a7: the two heads on given inputs (RenderingNetwork.forward :235-255,
  * AttractionFieldNetwork.forward :175-197), row-major inputs; rgb [P,3], lines [P,2,3]. */

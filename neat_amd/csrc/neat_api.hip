@@ -1043,7 +1043,10 @@ hipError_t wgrad(const Ctx& c, const SdfWs& w, int layer_id, const WPair* pairs_
 // nc: the cotangent of the normals still has to be formed (its arguments); null = w.gh is set
 struct NormalCot { const float* sc_r; const float* sc_a; const float* extra_rm; int P_main; const float* d_tail_rm; const float* slot; const float* slot_a;
                    const float* dbeta_ray = nullptr; int R = 0; const float* beta_ptr = nullptr; float* dbeta = nullptr; };
-hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grads* gr, const NormalCot* nc = nullptr) {
+// keep_a4 (x-gradient, neat_sdf_backward_x): a^_4 must survive the chain for the skip rows of lin4 (sdf_input_grad), so the chain variables
+// do not alternate between two buffers (a^_2 would overwrite it); a^_4 then stays in m[4], a^_0 in m[0] -- the same bits (tuning key 24).
+// Layers whose gr->dv is null get no weight gradient (a frozen network); the in-kernel gradient launches need all of 1..7.
+hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grads* gr, const NormalCot* nc = nullptr, bool keep_a4 = false) {
   const PackLayout& L = c.L();
   hipError_t e;
   if (c.prec && nc) {
@@ -1085,7 +1088,7 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   auto u16p = [](const Arr& a) { return reinterpret_cast<u16*>(a.p); };
   // chain variables of the in-kernel-gradient launches: vhat_1 (lin0's launch) and vhat_8 (rowdot_kernel reads it) keep their arrays, vhat_2..7
   // alternate between vh[2] / vh[3]; the reverse chain's a^_7..1 alternate between vh[4] / vh[5] (free in this mode), a^_0 lands in m[0] (lin0's gradient)
-  const bool pp = dw && g_chain_pp;
+  const bool pp = dw && g_chain_pp && !keep_a4;
   auto VH = [&](int l) -> const Arr& { return (pp && l >= 2 && l <= 7) ? w.vh[2 + (l & 1)] : w.vh[l]; };
   auto RB = [&](int l) -> const Arr& { return (pp && l >= 1 && l <= 7) ? w.vh[4 + (l & 1)] : w.m[l]; };
   auto dw_prof = [&](int N, int rowsA) {
@@ -1174,6 +1177,7 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   // step) while it is still in the 256 MB Infinity Cache instead of after all eight reverse steps.
   const bool oct = oct_operands(c);
   auto wgrad_layer = [&](int l) -> hipError_t {
+    if (!gr->dv[l]) return hipSuccess;
     WPair pr[2] = {};
     if (l == 8 && c.prec) {
       // feature rows: featc x h8 on the streaming kernel; the sdf row (cotangent abar8 row 0; its second-order part is
@@ -1310,7 +1314,7 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   const int nb2 = wgrad_batch_size(c.ldp);
-  if (oct && nb2 && g_wgrad_h3 && !dw) {
+  if (oct && nb2 && g_wgrad_h3 && !dw && gr->dv[1] && gr->dv[2] && gr->dv[3] && gr->dv[5] && gr->dv[6] && gr->dv[7]) {
     // the six hidden layers with 256 packed input columns as six problems (two (A, B) pairs each) of one launch
     const int ls[6] = {1, 2, 3, 5, 6, 7};
     WProb pb[6];
@@ -1589,6 +1593,81 @@ __global__ void build_abar8_kernel(const float* __restrict__ d_out257, const flo
   abar8[(size_t)n * ldp + p] = v * scale;
 }
 
+// x-gradient of the SDF outputs (rend_a :111-137 differentiated in x), per point, after the reverse chain and sdf_input_grad's two
+// contractions (tests/test_sdf_input_grad_math.py restates this in float64):
+//   d_x = (J^T abar_e + sum_j u_e[j] (d^2 e_j / dx^2) g^) / cot_scale  (+ the clamp terms where the sphere clamp is the output)
+// abar_e = ae0 + aes (W0^T a^_0 + W4skip^T a^_4: the PE-level cotangent of the reverse chain), u_e = e0 + es (what the forward's adjoint
+// chain left for the normal), g^ = the masked normal cotangent of the backward (gh).  abar_e and g^ carry the backward's cotangent scale,
+// u_e does not.  Where the clamp is on (mask): sdf = s (r - |x|) and grad = -s x / |x| add -s x^ d_sdf - s (I - x^ x^T) d_grad / |x|,
+// from the caller's unscaled cotangents.  PE-6 is separable per coordinate: d^2 sin(f x) / dx^2 = -f^2 sin(f x), the same for cos.
+struct InputGradArgs {
+  const float *x_fm, *ae0, *aes, *e0, *es, *gh, *mask;     // feature-major [rows][ldp]
+  const float *d_sdf, *d_grad, *cot_slot;                  // row-major caller cotangents (may be null)
+  float scale; int P, ldp;
+  float* d_x;                                              // [P,3] row-major
+};
+__global__ __launch_bounds__(256) void sdf_input_grad_kernel(InputGradArgs a) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.P) return;
+  const size_t ldp = (size_t)a.ldp;
+  const float inv = 1.0f / cot_scale_of(a.cot_slot);
+  float xv[3], dx[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float xc = a.x_fm[c * ldp + p], gc = a.gh[c * ldp + p];
+    xv[c] = xc;
+    float acc = a.ae0[c * ldp + p] + a.aes[c * ldp + p];        // identity rows: J = 1, no curvature
+    float f = 1.0f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const size_t rs = (size_t)(3 + 6 * k + c) * ldp + p, rc = (size_t)(6 + 6 * k + c) * ldp + p;
+      const float sa = a.ae0[rs] + a.aes[rs], ca = a.ae0[rc] + a.aes[rc];
+      const float su = a.e0[rs] + a.es[rs], cu = a.e0[rc] + a.es[rc];
+      const float sn = sinf(xc * f), cs = cosf(xc * f);        // libm forms: |arg| reaches ~100, where the hardware ones are ~1e-6 off
+      acc += f * (cs * sa - sn * ca) - f * f * (sn * su + cs * cu) * gc;
+      f *= 2.0f;
+    }
+    dx[c] = acc * inv;
+  }
+  if (a.mask[p] != 0.0f) {
+    const float nr = sqrtf(xv[0] * xv[0] + xv[1] * xv[1] + xv[2] * xv[2]);
+    if (nr > 0.0f) {
+      const float ds = a.d_sdf ? a.d_sdf[p] : 0.0f;
+      float cg[3] = {0.f, 0.f, 0.f};
+      if (a.d_grad) { cg[0] = a.d_grad[3 * (size_t)p]; cg[1] = a.d_grad[3 * (size_t)p + 1]; cg[2] = a.d_grad[3 * (size_t)p + 2]; }
+      const float rn = 1.0f / nr;
+      const float dot = (xv[0] * cg[0] + xv[1] * cg[1] + xv[2] * cg[2]) * rn;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float xh = xv[c] * rn;
+        dx[c] -= a.scale * (xh * ds + (cg[c] - xh * dot) * rn);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a.d_x[3 * (size_t)p + c] = dx[c];
+}
+
+// the x-gradient after sdf_backward_chains(keep_a4): two contractions onto the 39 PE rows on the matrix pipe, through the transposed packs
+// the non-fused adjoint chain uses for the same products (W0^T a^_0: lin0's pack; W4skip^T a^_4: rows 217..255 of lin4's, split off into an
+// fp32 output, rows 0..216 land in a scratch array), then the per-point epilogue.  Arrays the backward has finished with hold the results:
+// ae0 -> Eh (the PE tangent, read by lin0's weight gradient), aes -> the first 39 rows of abar8 (lin8's cotangent), scratch -> vh[6].
+hipError_t sdf_input_grad(const Ctx& c, const SdfWs& w, float scale, const float* d_sdf, const float* d_grad, const float* slot, float* d_x) {
+  const PackLayout& L = c.L();
+  hipError_t e;
+  if ((e = layer(c, L.tr[0], EPI_LINEAR, in(w.m[0], 256), NOIN, nullptr, PE_ROWS, F(w.Eh))) != hipSuccess) return e;
+  if ((e = layer(c, L.tr[4], EPI_REV, in(w.m[4], 256), NOIN, nullptr, 256, w.vh[6], F(w.abar8), 217, w.h[4])) != hipSuccess) return e;
+  InputGradArgs a{};
+  a.x_fm = w.x; a.ae0 = w.Eh; a.aes = w.abar8; a.e0 = w.e0; a.es = w.es; a.gh = w.gh; a.mask = w.mask;
+  a.d_sdf = d_sdf; a.d_grad = d_grad; a.cot_slot = slot;
+  a.scale = scale; a.P = c.P; a.ldp = c.ldp; a.d_x = d_x;
+  ProfSlot* ps = prof_begin(c.st, 0, 0.0, (double)c.P * (4 * PE_ROWS * 4.0 + 3 * 4.0 + 3 * 4.0 + 4.0 + 4.0 + 3 * 4.0 + 3 * 4.0));
+  hipLaunchKernelGGL(sdf_input_grad_kernel, grid1(c.P), dim3(256), 0, c.st, a);
+  prof_end(c.st, ps);
+  dbg_sync(c.st, "sdf input grad", c.P, 0, 0);
+  return hipGetLastError();
+}
+
 // f16 build: cotangent normalisation (kernels.hpp: cot_scale_of).  cot_scale_begin reduces max |cotangent| over the caller's arrays
 // into `slot` (a float of the workspace: the `ones` row, which only the fp32 build uses); the kernels that read the caller's
 // cotangents scale by 2^k; grad_unscale takes the factor out of the finished parameter gradients.  Other builds: slot = nullptr.
@@ -1654,7 +1733,7 @@ bool bad_prec(int p) { return p != F32 && p != BF16 && p != BF16X3 && !(NEAT_HAL
 #define NEAT_TWIN(fn) extern "C" decltype(fn) f16_##fn;
 NEAT_TWIN(neat_set_tuning) NEAT_TWIN(neat_prof_enable) NEAT_TWIN(neat_prof_collect)
 NEAT_TWIN(neat_packed_floats) NEAT_TWIN(neat_pack_weights) NEAT_TWIN(neat_sdf_ws_floats) NEAT_TWIN(neat_sdf_forward)
-NEAT_TWIN(neat_sdf_backward) NEAT_TWIN(neat_heads_ws_floats) NEAT_TWIN(neat_heads_forward) NEAT_TWIN(neat_render_ws_floats)
+NEAT_TWIN(neat_sdf_backward) NEAT_TWIN(neat_sdf_backward_x) NEAT_TWIN(neat_heads_ws_floats) NEAT_TWIN(neat_heads_forward) NEAT_TWIN(neat_render_ws_floats)
 NEAT_TWIN(neat_render_forward) NEAT_TWIN(neat_render_backward) NEAT_TWIN(neat_render_eval_ws_floats)
 NEAT_TWIN(neat_render_forward_eval) NEAT_TWIN(neat_sdf_values_gated) NEAT_TWIN(neat_sdf_values_rays) NEAT_TWIN(neat_sdf_values_laid_out)
 #define NEAT_F16_FWD(call) if (precision == 3) { precision = BF16; return f16_##call; } if (precision == HX3 || precision == HX3_FASTVALUES) return f16_##call;
@@ -1664,7 +1743,7 @@ NEAT_TWIN(neat_render_forward_eval) NEAT_TWIN(neat_sdf_values_gated) NEAT_TWIN(n
 
 extern "C" {
 
-int neat_abi_version(void) { return 13; }
+int neat_abi_version(void) { return 14; }
 
 int neat_set_tuning(int key, int value) {          /* 0: bf16 layer-kernel point tile (2 -> 64 points, 4 -> 128 points) */
 #if !NEAT_HALF
@@ -1882,10 +1961,9 @@ int neat_sdf_values_gated(const float* packed, const neat_net_params* net, const
   return rc;
 }
 
-int neat_sdf_backward(const float* packed, const neat_net_params* net, float* ws, int P, int precision,
-                      const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
-                      const neat_net_grads* grads, void* stream) {
-  NEAT_F16_FWD(neat_sdf_backward(packed, net, ws, P, precision, d_out257, d_sdf, d_feat, d_grad, grads, stream))
+static int sdf_backward_impl(const float* packed, const neat_net_params* net, float* ws, int P, int precision, float scale,
+                             const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
+                             const neat_net_grads* grads, float* d_x, void* stream) {
   const int x3 = take_x3(precision); (void)x3;
   const int hx3 = take_hx3(precision); (void)hx3;
   if (hx3 == 2) return -1;
@@ -1898,9 +1976,27 @@ int neat_sdf_backward(const float* packed, const neat_net_params* net, float* ws
   hipLaunchKernelGGL(build_abar8_kernel, dim3((c.ldp + 255) / 256, 257), dim3(256), 0, c.st, d_out257, d_sdf, d_feat, w.mask, P, c.ldp, w.abar8, slot);
   if (precision) oct_pack(c, {{w.abar8 + c.ldp, 256, w.featc}});
   const NormalCot nc{nullptr, nullptr, d_grad, P, nullptr, slot, nullptr};
-  NEAT_CHECK(sdf_backward_chains(c, w, grads, &nc));
+  NEAT_CHECK(sdf_backward_chains(c, w, grads, &nc, d_x != nullptr));
   grad_unscale(c, grads, 0, 9, slot);
+  if (d_x) NEAT_CHECK(sdf_input_grad(c, w, scale, d_sdf, d_grad, slot, d_x));
   return (int)hipGetLastError();
+}
+
+int neat_sdf_backward(const float* packed, const neat_net_params* net, float* ws, int P, int precision,
+                      const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
+                      const neat_net_grads* grads, void* stream) {
+  NEAT_F16_FWD(neat_sdf_backward(packed, net, ws, P, precision, d_out257, d_sdf, d_feat, d_grad, grads, stream))
+  return sdf_backward_impl(packed, net, ws, P, precision, 0.0f, d_out257, d_sdf, d_feat, d_grad, grads, nullptr, stream);
+}
+
+// rend_a :111-137 differentiated in x as well (neat_hip.h)
+int neat_sdf_backward_x(const float* packed, const neat_net_params* net, float* ws, int P, int precision, float scale,
+                        const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
+                        const neat_net_grads* grads, float* d_x, void* stream) {
+  NEAT_F16_FWD(neat_sdf_backward_x(packed, net, ws, P, precision, scale, d_out257, d_sdf, d_feat, d_grad, grads, d_x, stream))
+  if (P > 0 && !d_x) return -1;
+  const neat_net_grads none{};          // null grads (or null members): no weight gradient for those layers
+  return sdf_backward_impl(packed, net, ws, P, precision, scale, d_out257, d_sdf, d_feat, d_grad, grads ? grads : &none, d_x, stream);
 }
 
 size_t neat_heads_ws_floats(int P, int precision) {

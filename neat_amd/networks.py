@@ -140,7 +140,7 @@ class ImplicitNetwork(_HipModule):
         return self._outputs(input, 0.0)[0]
 
     def gradient(self, x):
-        """d raw-sdf / dx, differentiable wrt the parameters (eikonal term, rend_a :98-109)."""
+        """d raw-sdf / dx, differentiable wrt the parameters (eikonal term, rend_a :98-109) and, to first order, wrt x."""
         return self._outputs(x, 0.0)[3]
 
     def get_outputs(self, x):
@@ -148,7 +148,12 @@ class ImplicitNetwork(_HipModule):
         return sdf, feat, grad
 
     def get_sdf_vals(self, x, gate=None, fast=False):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        """Clamped sdf [P,1] (rend_a :131-137).  With autograd (grad enabled and x or a parameter requiring grad) it is get_outputs' sdf,
+        differentiable in both, and `fast` (a values-only option of the fp16x3 build) does not apply; a device `gate` (the sampler's
+        sync-free rounds, always under no_grad) cannot be honoured by a differentiable query, so x requiring grad with a gate raises."""
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if gate is not None and x.requires_grad:
+                raise ValueError("get_sdf_vals: a gated query is not differentiable in x; call it under torch.no_grad() or without gate")
             return self._outputs(x, self.sdf_bounding_sphere)[1]
         return ops.sdf_values(self.handle(), x, self.sdf_bounding_sphere, self.sphere_scale, gate=gate, fast=fast)
 

@@ -4,7 +4,6 @@ PyTorch is plumbing here (device memory, current stream, autograd graph); all P-
 happens in neat_amd/csrc.  Every op requires CUDA float32 tensors and raises if the library is absent.
 """
 import ctypes
-import warnings
 
 import torch
 
@@ -146,17 +145,14 @@ def _grad_buffers(handle, first, count, device):
 class SdfOutputsFn(torch.autograd.Function):
     """ImplicitNetwork.forward / get_outputs / gradient in one op.
     returns (forward()[P,257], clamped sdf [P,1], feature [P,256], d sdf/dx [P,3]); differentiable wrt the
-    27 SDF parameters (including the double backward through d sdf/dx); x is treated as a constant."""
+    27 SDF parameters (including the double backward through d sdf/dx) and, to first order, wrt x (rend_a :111-137 are
+    autograd in x): when x requires grad the backward is neat_sdf_backward_x, which forms the parameter gradients only if
+    a parameter requires grad (a frozen network optimising its query points runs no weight-gradient work)."""
 
     @staticmethod
     def forward(ctx, handle, x, radius, scale, *params):
         lib = _lib.lib()
         ctx.set_materialize_grads(False)
-        if x.requires_grad and torch.is_grad_enabled():
-            # the reference's get_outputs is differentiable in x (rend_a :429: points3d = sum(w p) carries the weights' graph);
-            # loss_wfr never uses that path, and this op does not implement d/dx -- say so instead of dropping it silently
-            warnings.warn("neat_amd: sdf_outputs treats its input points as constants; gradients do not flow through x "
-                          "(INTEGRATION.md, 'Restrictions')", stacklevel=3)
         x = _f32c(x.detach())
         P = x.shape[0]
         packed, netp = handle.packed()
@@ -169,6 +165,7 @@ class SdfOutputsFn(torch.autograd.Function):
         _lib.check(lib.neat_sdf_forward(_p(packed), ctypes.byref(netp), _p(x), P, 1, prec, float(radius), float(scale), _p(ws),
                                         _p(out), _p(sdf), _p(feat), _p(grad), _stream()), "neat_sdf_forward")
         ctx.handle, ctx.P, ctx.ws, ctx.packed, ctx.netp, ctx.prec = handle, P, ws, packed, netp, prec
+        ctx.scale = float(scale)
         ctx.keep = params          # netp holds raw pointers: tensors derived per forward (networks: nerf heads, inside_out) must outlive the backward
         return out, sdf, feat, grad
 
@@ -176,12 +173,33 @@ class SdfOutputsFn(torch.autograd.Function):
     def backward(ctx, d_out, d_sdf, d_feat, d_grad):
         lib = _lib.lib()
         h = ctx.handle
+        if ctx.needs_input_grad[1]:
+            d_x, views = sdf_backward_x(h, ctx.ws, ctx.packed, ctx.netp, ctx.P, ctx.prec, ctx.scale, d_out, d_sdf, d_feat, d_grad,
+                                        any(ctx.needs_input_grad[4:]))
+            ctx.ws = None
+            return (None, d_x, None, None, *views)
         gr, views, _ = _grad_buffers(h, 0, N_SDF, ctx.ws.device)
         d_out, d_sdf, d_feat, d_grad = (_f32c(t) for t in (d_out, d_sdf, d_feat, d_grad))
         _lib.check(lib.neat_sdf_backward(_p(ctx.packed), ctypes.byref(ctx.netp), _p(ctx.ws), ctx.P, ctx.prec, _p(d_out), _p(d_sdf),
                                          _p(d_feat), _p(d_grad), ctypes.byref(gr), _stream()), "neat_sdf_backward")
         ctx.ws = None
         return (None, None, None, None, *views)
+
+
+def sdf_backward_x(handle, ws, packed, netp, P, prec, scale, d_out, d_sdf, d_feat, d_grad, want_params):
+    """neat_sdf_backward_x on a mode-1 workspace -> (d_x [P,3], the 27 parameter gradients, or 27 Nones when not want_params:
+    null gradient pointers, no weight-gradient launches)."""
+    lib = _lib.lib()
+    dev = ws.device
+    if want_params:
+        gr, views, _ = _grad_buffers(handle, 0, N_SDF, dev)
+    else:
+        gr, views = _lib.NetGrads(), [None] * (3 * N_SDF)
+    d_out, d_sdf, d_feat, d_grad = (_f32c(t) for t in (d_out, d_sdf, d_feat, d_grad))
+    d_x = torch.empty(P, 3, device=dev)
+    _lib.check(lib.neat_sdf_backward_x(_p(packed), ctypes.byref(netp), _p(ws), P, prec, float(scale), _p(d_out), _p(d_sdf), _p(d_feat),
+                                       _p(d_grad), ctypes.byref(gr), _p(d_x), _stream()), "neat_sdf_backward_x")
+    return d_x, views
 
 
 def sdf_outputs(handle, x, radius, scale):

@@ -99,13 +99,31 @@ def sdf_outputs_backward(ws: Tensor, params: List[Tensor], P: int, precision: in
     return [v.clone() for v in views]       # custom-op outputs may not be views of one another: 27 small copies of one flat buffer
 
 
+@custom_op("neat_hip::sdf_outputs_backward_x", mutates_args=(), device_types="cuda")
+def sdf_outputs_backward_x(ws: Tensor, params: List[Tensor], P: int, precision: int, scale: float, want_params: bool,
+                           d_out: Optional[Tensor], d_sdf: Optional[Tensor], d_feat: Optional[Tensor],
+                           d_grad: Optional[Tensor]) -> Tuple[Tensor, List[Tensor]]:
+    """-> d_x [P,3] and the 27 parameter gradients (an empty list when not want_params: no weight-gradient work)."""
+    h = _handle(params, precision)
+    packed, netp = h.packed()
+    d_x, views = ops.sdf_backward_x(h, ws, packed, netp, P, h.precision, scale, d_out, d_sdf, d_feat, d_grad, want_params)
+    return d_x, ([v.clone() for v in views] if want_params else [])
+
+
 def _sdf_setup(ctx, inputs, output):
     x, params, radius, scale, precision = inputs
     ctx.set_materialize_grads(False)
-    ctx.ws, ctx.params, ctx.P, ctx.precision = output[4], params, x.shape[0], precision
+    ctx.ws, ctx.params, ctx.P, ctx.precision, ctx.scale = output[4], params, x.shape[0], precision, float(scale)
 
 
 def _sdf_backward(ctx, d_out, d_sdf, d_feat, d_grad, _d_ws):
+    if ctx.needs_input_grad[0]:
+        # x requires grad: first-order x-gradient (rend_a :111-137), parameter gradients only if a parameter asks for them
+        want = bool(ctx.needs_input_grad[1])
+        d_x, grads = torch.ops.neat_hip.sdf_outputs_backward_x(ctx.ws, ctx.params, ctx.P, ctx.precision, ctx.scale, want,
+                                                               d_out, d_sdf, d_feat, d_grad)
+        ctx.ws = None
+        return d_x, (grads if want else None), None, None, None
     grads = torch.ops.neat_hip.sdf_outputs_backward(ctx.ws, ctx.params, ctx.P, ctx.precision, d_out, d_sdf, d_feat, d_grad)
     ctx.ws = None
     return None, grads, None, None, None
@@ -210,5 +228,5 @@ def linear_sum_assignment(cost: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     return ops.linear_sum_assignment(cost)
 
 
-OPS = ("camera_rays", "sdf_values", "sdf_outputs", "sdf_outputs_backward", "render_rays", "render_rays_backward", "render_rays_eval",
+OPS = ("camera_rays", "sdf_values", "sdf_outputs", "sdf_outputs_backward", "sdf_outputs_backward_x", "render_rays", "render_rays_backward", "render_rays_eval",
        "volume_weights", "sample_pdf", "linear_sum_assignment")
