@@ -37,7 +37,7 @@ typedef struct neat_net_grads {
   float* db[NEAT_NUM_LAYERS];
 } neat_net_grads;
 
-int neat_abi_version(void);      /* 14 */
+int neat_abi_version(void);      /* 15 */
 
 /* `precision` selects the build of the GEMM-class kernels:
  *   NEAT_F32  (0): exact-f32 MFMA, fp32 activations  -- parity build (outputs within 1e-4 of the reference)
@@ -380,6 +380,46 @@ int neat_lsap(const float* cost, int nr, int nc, const unsigned char* row_mask, 
  * by n/2 ints of scratch; clusters in sklearn's order (by first member), padded; valid [n/2] bytes; *count = clusters. */
 size_t neat_dbscan_ws_bytes(int n);
 int neat_dbscan_means(const float* points, int n, double eps, float* centres, unsigned char* valid, int* count, void* ws, void* stream);
+
+/* ---- ABI v15: wireframe parsing of a trained model (code/neat-final-parsing.py: initial_recon :159-302,
+ * get_wireframe_from_lines_and_junctions :134-157, visibility_checking :305-336).  fp32, no float atomics, every result bit-identical
+ * from run to run.  Sizes that depend on the data (labels present, lines kept, junctions, edges) are written to device memory.
+ *
+ * neat_parse_match (:226-236): lines2d [n,4] = one view's predicted 2-D lines; row i < n is line i, row n + i its reverse (x2,y2,x1,y1).
+ *   gt: m ground-truth lines, row stride gt_stride (>= 4: (x1,y1,x2,y2,...)).  label [2n] int32 = argmin_j |row - gt_j|^2 (lowest j on
+ *   ties) if that minimum is < threshold, else -1; mindis [2n] = the minimum (+inf if m = 0; NaN for a row with a NaN distance).
+ * neat_parse_group (:237-257): the rows of each label present, in row order: lines [m,2,3] (capacity) receives, in ascending label order,
+ *   the mean of the rows' lines3d (rows >= n: the reversed line), scores [m] the mean of |(p - v0) x (p - v1)| / max(|v1 - v0|, 1e-6)
+ *   over the same rows (p = the row's l3d [n,3]); *count = L, the labels present.  ws: neat_parse_group_ws_bytes(n, m).
+ * neat_parse_vote (:259-272): cost [J, 2 mcap] = |junction - endpoint| (endpoints = lines.reshape(-1,3), the first 2 *count of them),
+ *   the assignment of neat_lsap, and one vote per pair with cost < threshold: votes[j] += 1 (votes [J] int32, zeroed by the caller before
+ *   the first view); the first vote of a junction stamps first[2j..2j+1] = (view, pair index).  ws: neat_parse_vote_ws_bytes(J, mcap).
+ * neat_parse_graph (:278-295, :134-157 with rel_matching_distance_threshold = 0): vlines [V,mcap,2,3], vscores [V,mcap], vcount [V] as
+ *   the group calls left them -> lines_out [V mcap,2,3] = the lines with score < score_threshold (view, then label order), junc_out [J,3] =
+ *   the junctions with more than one vote in the order of their first vote, graph [J,J] bytes (row stride J; the K x K block is the
+ *   reference's 0/1 graph), pairs [ecap,2] int32 + wfi [ecap,2,3] = graph.triu().nonzero() in row-major order (the diagonal included) and
+ *   the junctions it names; counts [3] = (N lines, K junctions, E edges).  ws: neat_parse_graph_ws_bytes(V, mcap, J).
+ * neat_parse_visibility (:305-336), all views in one launch: lines [ecap,2,3] (the first *n_lines of them, or ecap if n_lines is NULL);
+ *   gt: the views' ground-truth lines packed (row stride gt_stride), view v's at rows [gt_off[v], gt_off[v+1]) (gt_off [V+1] int32 on the
+ *   device); K3 [V,3,3], w2c [V,3,4] (neat_camera_mats per view).  vis_count [ecap] int32 = views in which the projected line is within
+ *   squared distance < ckdist of a ground-truth line in either orientation (a view without ground-truth lines sees nothing); checked
+ *   [ecap,2,3] = the lines with vis_count >= ckview, in order, *n_checked of them.  ws: neat_parse_visibility_ws_bytes(ecap, V). */
+int neat_parse_match(const float* lines2d, int n, const float* gt, int m, int gt_stride, float threshold, int* label, float* mindis,
+                     void* stream);
+size_t neat_parse_group_ws_bytes(int n, int m);
+int neat_parse_group(const int* label, const float* lines3d, const float* l3d, int n, int m, float* lines, float* scores, int* count,
+                     void* ws, void* stream);
+size_t neat_parse_vote_ws_bytes(int J, int mcap);
+int neat_parse_vote(const float* junctions, int J, const float* lines, const int* count, int mcap, float threshold, int view, int* votes,
+                    int* first, void* ws, void* stream);
+size_t neat_parse_graph_ws_bytes(int V, int mcap, int J);
+int neat_parse_graph(const float* vlines, const float* vscores, const int* vcount, int V, int mcap, float score_threshold,
+                     const float* junctions, const int* votes, const int* first, int J, float* lines_out, float* junc_out,
+                     unsigned char* graph, int* pairs, float* wfi, int ecap, int* counts, void* ws, void* stream);
+size_t neat_parse_visibility_ws_bytes(int ecap, int V);
+int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, const float* gt, int gt_stride, const int* gt_off,
+                          const float* K3, const float* w2c, int V, float ckdist, int ckview, int* vis_count, float* checked,
+                          int* n_checked, void* ws, void* stream);
 
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);

@@ -6,7 +6,7 @@ import ctypes
 import os
 
 NUM_LAYERS = 19
-ABI_VERSION = 14
+ABI_VERSION = 15
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2, "fp16": 3, "fp16x3": 4}
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NEAT_HIP_LIB") or os.path.join(_HERE, "csrc", "libneat_hip.so")      # NEAT_HIP_LIB: a probe build (scripts/probes/abl_build.sh)
@@ -109,6 +109,17 @@ _SIGNATURES = {
     "neat_lsap": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_dbscan_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "neat_dbscan_means": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_parse_match": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, c_fp, c_fp]),
+    "neat_parse_group_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "neat_parse_group": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_parse_vote_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "neat_parse_vote": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
+    "neat_parse_graph_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "neat_parse_graph": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, c_fp, c_fp, ctypes.c_int,
+                                        c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
+    "neat_parse_visibility_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "neat_parse_visibility": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_float,
+                                             ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

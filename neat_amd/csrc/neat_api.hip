@@ -17,6 +17,7 @@
 #include "fused_launch.hpp"
 #include "kernels_sampler.hpp"
 #include "kernels_junction.hpp"
+#include "kernels_parse.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <initializer_list>
@@ -1743,7 +1744,7 @@ NEAT_TWIN(neat_render_forward_eval) NEAT_TWIN(neat_sdf_values_gated) NEAT_TWIN(n
 
 extern "C" {
 
-int neat_abi_version(void) { return 14; }
+int neat_abi_version(void) { return 15; }
 
 int neat_set_tuning(int key, int value) {          /* 0: bf16 layer-kernel point tile (2 -> 64 points, 4 -> 128 points) */
 #if !NEAT_HALF
@@ -2597,6 +2598,123 @@ int neat_dbscan_means(const float* points, int n, double eps, float* centres, un
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream) {
   if (R <= 0 || S <= 0) return 0;
   hipLaunchKernelGGL(volume_weights_kernel, dim3((R + 3) / 4), dim3(WG), 0, (hipStream_t)stream, z, sdf, R, S, beta, weights);
+  return (int)hipGetLastError();
+}
+
+// ---- ABI v15: wireframe parsing (kernels_parse.hpp) -----------------------------------------------------------------------------
+static inline size_t parse_al(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline int parse_tiles(int n) { return (2 * n + PARSE_TILE - 1) / PARSE_TILE; }
+
+int neat_parse_match(const float* lines2d, int n, const float* gt, int m, int gt_stride, float threshold, int* label, float* mindis,
+                     void* stream) {
+  if (n < 0 || m < 0 || (m > 0 && (!gt || gt_stride < 4))) return -1;
+  if (n == 0) return 0;
+  if (!lines2d || !label || !mindis) return -1;
+  hipLaunchKernelGGL(parse_match_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, (hipStream_t)stream, lines2d, n, gt, m, gt_stride, threshold,
+                     label, mindis);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_group_ws_bytes(int n, int m) {
+  if (n < 0 || m < 0) return 0;
+  const size_t nt = (size_t)parse_tiles(n);
+  return parse_al((nt * m + 3 * (size_t)m) * sizeof(int)) + parse_al(2 * (size_t)n * sizeof(int));
+}
+
+int neat_parse_group(const int* label, const float* lines3d, const float* l3d, int n, int m, float* lines, float* scores, int* count,
+                     void* ws, void* stream) {
+  if (n < 0 || m < 0 || !count) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0 || m == 0) return (int)hipMemsetAsync(count, 0, sizeof(int), st);
+  if (!label || !lines3d || !l3d || !lines || !scores || !ws) return -1;
+  const int nt = parse_tiles(n);
+  int* run = (int*)ws;
+  int* cnt = run + (size_t)nt * m;
+  int* start = cnt + m;
+  int* slot = start + m;
+  int* order = (int*)((char*)ws + parse_al(((size_t)nt * m + 3 * (size_t)m) * sizeof(int)));
+  NEAT_CHECK(hipMemsetAsync(run, 0, (size_t)nt * m * sizeof(int), st));
+  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 0);
+  hipLaunchKernelGGL(parse_group_scan_kernel, dim3(1), dim3(1024), 0, st, run, nt, m, cnt, start, slot, count);
+  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 1);
+  hipLaunchKernelGGL(parse_group_reduce_kernel, dim3(m), dim3(PARSE_WG), 0, st, order, cnt, start, slot, lines3d, l3d, n, lines, scores);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_vote_ws_bytes(int J, int mcap) {
+  if (J <= 0 || mcap <= 0) return 0;
+  const size_t nc = 2 * (size_t)mcap, k = std::min((size_t)J, nc);
+  return parse_al((size_t)J * nc * sizeof(float)) + parse_al(nc) + 2 * parse_al(k * sizeof(long long)) + parse_al(sizeof(int)) +
+         parse_al(neat_lsap_ws_bytes(J, (int)nc));
+}
+
+int neat_parse_vote(const float* junctions, int J, const float* lines, const int* count, int mcap, float threshold, int view, int* votes,
+                    int* first, void* ws, void* stream) {
+  if (J < 0 || mcap < 0 || view < 0) return -1;
+  if (J == 0 || mcap == 0) return 0;
+  if (!junctions || !lines || !count || !votes || !first || !ws) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int nc = 2 * mcap, k = std::min(J, nc);
+  char* p = (char*)ws;
+  float* cost = (float*)p; p += parse_al((size_t)J * nc * sizeof(float));
+  unsigned char* cmask = (unsigned char*)p; p += parse_al(nc);
+  long long* rows = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
+  long long* cols = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
+  int* n_match = (int*)p; p += parse_al(sizeof(int));
+  const size_t total = (size_t)J * nc;
+  hipLaunchKernelGGL(parse_vote_cost_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, junctions, J, lines, count, nc, cost, cmask);
+  NEAT_CHECK(hipGetLastError());
+  const int e = neat_lsap(cost, J, nc, nullptr, cmask, rows, cols, n_match, p, stream);
+  if (e != 0) return e;
+  hipLaunchKernelGGL(parse_vote_apply_kernel, grid1(k), dim3(256), 0, st, rows, cols, n_match, k, cost, nc, threshold, view, votes, first);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_graph_ws_bytes(int V, int mcap, int J) {
+  if (V < 0 || mcap < 0 || J < 0) return 0;
+  return parse_al((size_t)V * mcap * sizeof(int)) + parse_al((size_t)J * sizeof(int));
+}
+
+int neat_parse_graph(const float* vlines, const float* vscores, const int* vcount, int V, int mcap, float score_threshold,
+                     const float* junctions, const int* votes, const int* first, int J, float* lines_out, float* junc_out,
+                     unsigned char* graph, int* pairs, float* wfi, int ecap, int* counts, void* ws, void* stream) {
+  if (V < 0 || mcap < 0 || J < 0 || ecap < 0 || !counts) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if ((V > 0 && mcap > 0 && (!vlines || !vscores || !vcount || !lines_out || !ws)) ||
+      (J > 0 && (!junctions || !votes || !first || !junc_out || !graph || !ws)) || (ecap > 0 && (!pairs || !wfi))) return -1;
+  NEAT_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(int), st));
+  const int ncap = V * mcap;
+  if (ncap == 0 && J == 0) return 0;
+  int* idx = (int*)ws;
+  int* rowcnt = (int*)((char*)ws + parse_al((size_t)V * mcap * sizeof(int)));
+  hipLaunchKernelGGL(parse_select_kernel, dim3(2), dim3(1024), 0, st, vlines, vscores, vcount, V, mcap, score_threshold, junctions, votes, first,
+                     J, lines_out, junc_out, idx, counts);
+  if (J == 0 || ncap == 0) return (int)hipGetLastError();
+  NEAT_CHECK(hipMemsetAsync(graph, 0, (size_t)J * J, st));
+  hipLaunchKernelGGL(parse_graph_mark_kernel, grid1(ncap, PARSE_WG), dim3(PARSE_WG), 0, st, lines_out, junc_out, counts, ncap, J, graph);
+  hipLaunchKernelGGL(parse_edge_count_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt);
+  hipLaunchKernelGGL(parse_edge_write_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt, J, junc_out, ecap, pairs, wfi);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_visibility_ws_bytes(int ecap, int V) {
+  if (ecap < 0 || V < 0) return 0;
+  return parse_al((size_t)V * ecap) + parse_al((size_t)ecap * sizeof(int));
+}
+
+int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, const float* gt, int gt_stride, const int* gt_off,
+                          const float* K3, const float* w2c, int V, float ckdist, int ckview, int* vis_count, float* checked,
+                          int* n_checked, void* ws, void* stream) {
+  if (ecap < 0 || V < 0 || !n_checked) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (ecap == 0) return (int)hipMemsetAsync(n_checked, 0, sizeof(int), st);
+  if (!lines || !vis_count || !checked || !ws || (V > 0 && (!gt_off || !K3 || !w2c || gt_stride < 4))) return -1;
+  unsigned char* vis = (unsigned char*)ws;
+  int* idx = (int*)((char*)ws + parse_al((size_t)V * ecap));
+  if (V > 0)
+    hipLaunchKernelGGL(parse_vis_kernel, dim3((ecap + PARSE_WG - 1) / PARSE_WG, V), dim3(PARSE_WG), 0, st, lines, n_lines, ecap, gt, gt_stride,
+                       gt_off, K3, w2c, ckdist, vis);
+  hipLaunchKernelGGL(parse_vis_count_kernel, dim3(1), dim3(1024), 0, st, lines, n_lines, ecap, V, vis, ckview, vis_count, idx, checked, n_checked);
   return (int)hipGetLastError();
 }
 

@@ -1059,3 +1059,105 @@ def junction_gate(rows, cols, cost, cand3d, cand2d, cand2d_calib, use_median):
                                              1 if use_median else 0, _p(median), _p(good), _p(j3d), _p(j2d), _p(j2dc), _stream()),
                "neat_junction_gate")
     return (median.reshape(()) if use_median else None), good.view(torch.bool), j3d, j2d, j2dc   # 0 / 1 bytes: reinterpret, no copy
+
+
+# ---- wireframe parsing (ABI v15; neat_amd/parsing.py): no gradient, nothing synchronises -------------------------------------------
+def _i32(t):
+    if t.dtype != torch.int32 or not t.is_cuda:
+        raise RuntimeError("neat_amd parse ops need CUDA int32 tensors: got %s on %s" % (t.dtype, t.device))
+    return t.contiguous()
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 8), device=device, dtype=torch.uint8)
+
+
+def _rows4(gt):
+    """[m, >= 4] float32 ground-truth lines -> (tensor with unit column stride, row stride)."""
+    gt = _f32c(gt.detach()) if gt.stride(-1) != 1 or gt.dtype != torch.float32 or not gt.is_cuda else gt.detach()
+    if gt.dim() != 2 or gt.shape[1] < 4:
+        raise RuntimeError("parse ops: ground-truth lines [m, >= 4]")
+    if gt.shape[0] > 1 and gt.stride(0) < 4:
+        gt = gt.contiguous()
+    return gt, (int(gt.stride(0)) if gt.shape[0] > 1 else int(gt.shape[1]))
+
+
+def parse_match(lines2d, gt, threshold):
+    """initial_recon :226-236 for one view: lines2d [n,4], gt [m, >= 4] (x1,y1,x2,y2,...) -> label [2n] int32 (-1 = no match), mindis [2n].
+    Rows n..2n hold the reversed lines; they are never materialised."""
+    lines2d = _f32c(lines2d.detach().reshape(-1, 4))
+    n, dev = lines2d.shape[0], lines2d.device
+    gt, stride = _rows4(gt)
+    label = torch.empty(2 * n, device=dev, dtype=torch.int32)
+    mindis = torch.empty(2 * n, device=dev)
+    _lib.check(_lib.lib().neat_parse_match(_p(lines2d), n, _p(gt), gt.shape[0], stride, float(threshold), _p(label), _p(mindis), _stream()),
+               "neat_parse_match")
+    return label, mindis
+
+
+def parse_group(label, lines3d, l3d, m, out=None):
+    """initial_recon :237-257: the mean line and the score of every label present, ascending.  -> lines [m,2,3], scores [m] (the first L
+    rows are valid), count int32 [1] = L (on the device).  out = (lines, scores, count) views to write into, or None."""
+    lines3d, l3d, label = _f32c(lines3d.detach().reshape(-1, 6)), _f32c(l3d.detach().reshape(-1, 3)), _i32(label)
+    n, dev = lines3d.shape[0], lines3d.device
+    if label.numel() != 2 * n or l3d.shape[0] != n:
+        raise RuntimeError("parse_group: label [2n], lines3d [n,2,3], l3d [n,3]")
+    if out is None:
+        out = (torch.empty(max(m, 1), 2, 3, device=dev), torch.empty(max(m, 1), device=dev), torch.empty(1, device=dev, dtype=torch.int32))
+    lines, scores, count = out
+    lib = _lib.lib()
+    ws = _ws(lib.neat_parse_group_ws_bytes(n, m), dev)
+    _lib.check(lib.neat_parse_group(_p(label), _p(lines3d), _p(l3d), n, m, _p(lines), _p(scores), _p(count), _p(ws), _stream()),
+               "neat_parse_group")
+    return lines, scores, count
+
+
+def parse_vote(junctions, lines, count, threshold, view, votes, first):
+    """initial_recon :259-272: assignment of the junctions [J,3] to the end points of the first `count` (int32 [1], device) lines of
+    lines [mcap,2,3]; votes [J] / first [J,2] int32 are updated in place (first vote: (view, pair index))."""
+    junctions, lines = _f32c(junctions.detach()), _f32c(lines.detach())
+    J, mcap = junctions.shape[0], lines.shape[0]
+    lib = _lib.lib()
+    ws = _ws(lib.neat_parse_vote_ws_bytes(J, mcap), junctions.device)
+    _lib.check(lib.neat_parse_vote(_p(junctions), J, _p(lines), _p(_i32(count)), mcap, float(threshold), int(view), _p(votes), _p(first),
+                                   _p(ws), _stream()), "neat_parse_vote")
+
+
+def parse_graph(vlines, vscores, vcount, score_threshold, junctions, votes, first):
+    """initial_recon :278-295 + get_wireframe_from_lines_and_junctions (:134-157) on the per-view group outputs vlines [V,mcap,2,3],
+    vscores [V,mcap], vcount [V] int32.  -> dict of padded device tensors and counts int32 [3] = (lines kept, junctions, edges)."""
+    vlines, vscores, junctions = _f32c(vlines.detach()), _f32c(vscores.detach()), _f32c(junctions.detach())
+    V, mcap, J = vlines.shape[0], vlines.shape[1], junctions.shape[0]
+    dev = junctions.device
+    ncap = V * mcap
+    ecap = min(ncap, J * (J + 1) // 2)
+    lib = _lib.lib()
+    res = {"lines": torch.empty(max(ncap, 1), 2, 3, device=dev), "junctions": torch.empty(max(J, 1), 3, device=dev),
+           "graph": torch.empty(max(J * J, 1), device=dev, dtype=torch.uint8), "pairs": torch.empty(max(ecap, 1), 2, device=dev, dtype=torch.int32),
+           "wfi": torch.empty(max(ecap, 1), 2, 3, device=dev), "counts": torch.empty(3, device=dev, dtype=torch.int32), "ecap": ecap}
+    ws = _ws(lib.neat_parse_graph_ws_bytes(V, mcap, J), dev)
+    _lib.check(lib.neat_parse_graph(_p(vlines), _p(vscores), _p(_i32(vcount)), V, mcap, float(score_threshold), _p(junctions), _p(_i32(votes)),
+                                    _p(_i32(first)), J, _p(res["lines"]), _p(res["junctions"]), _p(res["graph"]), _p(res["pairs"]),
+                                    _p(res["wfi"]), ecap, _p(res["counts"]), _p(ws), _stream()), "neat_parse_graph")
+    return res
+
+
+def parse_visibility(lines, n_lines, gt_packed, gt_off, K3, w2c, ckdist, ckview):
+    """visibility_checking (:305-336), all views in one launch.  lines [ecap,2,3] (the first n_lines (int32 [1] on the device, or None =
+    all) of them); gt_packed [sum m_v, >= 4] with view v at rows gt_off[v]:gt_off[v+1] (gt_off int32 [V+1] on the device); K3 [V,3,3],
+    w2c [V,3,4].  -> vis_count [ecap] int32, checked [ecap,2,3], n_checked int32 [1] (device)."""
+    lines = _f32c(lines.detach().reshape(-1, 6))
+    ecap, dev = lines.shape[0], lines.device
+    V = int(gt_off.shape[0]) - 1
+    gt, stride = _rows4(gt_packed) if gt_packed.shape[0] > 0 else (gt_packed, 4)
+    K3, w2c = _f32c(K3.detach()), _f32c(w2c.detach())
+    vis_count = torch.empty(max(ecap, 1), device=dev, dtype=torch.int32)
+    checked = torch.empty(max(ecap, 1), 2, 3, device=dev)
+    n_checked = torch.empty(1, device=dev, dtype=torch.int32)
+    lib = _lib.lib()
+    ws = _ws(lib.neat_parse_visibility_ws_bytes(ecap, V), dev)
+    _lib.check(lib.neat_parse_visibility(_p(lines), _p(_i32(n_lines)) if n_lines is not None else None, ecap,
+                                         _p(gt) if gt.numel() > 0 else None, stride, _p(_i32(gt_off)), _p(K3), _p(w2c), V,
+                                         float(ckdist), int(ckview), _p(vis_count), _p(checked), _p(n_checked), _p(ws), _stream()),
+               "neat_parse_visibility")
+    return vis_count[:ecap], checked[:ecap], n_checked

@@ -1,5 +1,7 @@
 """One training step of the hot path as the reference trainer runs it (code/training/volsdf_train.py:361-374,408):
 forward -> loss -> zero_grad/backward -> [gradient all-reduce] -> Adam step -> per-iteration ExponentialLR."""
+import contextlib
+import gc
 import os
 
 import torch
@@ -23,6 +25,21 @@ def _backward(loss):
             loss.backward(gradient=one)
     else:
         loss.backward()
+
+
+@contextlib.contextmanager
+def _gc_paused():
+    """No Python garbage collection while a step is captured.  A collection runs the destructors of whatever dead reference cycles hold
+    -- a dropped Trainer's graphs, private pool, streams, events -- and the HIP calls they make abort an active capture (torch.cuda.graph
+    collects on entry only under torch.compiler.config.force_cudagraph_gc).  The dead cycles are collected here, before the capture."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 class Trainer:
@@ -192,7 +209,7 @@ class Trainer:
                 self.bucket._ensure()
             graph = torch.cuda.CUDAGraph()
             # thread_local: a NCCL/RCCL watchdog thread may touch the runtime while this thread captures
-            with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
+            with _gc_paused(), torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
                 out, losses = self._fwd_bwd(entry, zero=False)
                 entry.outputs = (_detached(out), _detached(losses))
                 del out, losses
