@@ -10,6 +10,11 @@ flat-bucket gradient all-reduce only, for the CPU test of the multi-rank plumbin
 Workload (BASELINE.json configs[1], "C2"): abc-neat-a networks, 1024 rays x 128 depth samples per rank with the
 depth samples GIVEN (sorted stratified U[0,6)), one TRAIN STEP = forward + loss + backward + Adam
 (+ gradient all-reduce for N>1).  value = ray-samples/s over all ranks.  Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: set-up, warm-up, graph capture, the timed steps, `--dump-outputs`.
+`--full` adds everything measured beside it: the roofline (eager steps bracketed by HIP events after the timed region),
+the `dist` block of a process group (all-reduce alone, host time per step), the secondary legs (other precisions and
+workloads, single GPU) and the CPU oracle baseline; `--no-prof`, `--no-secondary` and `--no-cpu-baseline` drop parts of it.
 """
 import argparse
 import ctypes
@@ -425,9 +430,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (parity-grade precision, sampler step)")
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, dist block, secondary legs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU oracle baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="(with --full) skip the secondary legs (parity-grade precision, sampler step)")
+    ap.add_argument("--no-prof", action="store_true", help="do not bracket kernels with HIP events (a plain run brackets them only when "
+                                                           "its timed steps run eagerly)")
     ap.add_argument("--no-graph", action="store_true",
                     help="run the timed steps eagerly (default: forward+loss+backward of the step replayed from a HIP graph)")
     ap.add_argument("--pt", type=int, default=0, help="(tuning) bf16 layer-kernel point tile: 2 = 64 points, 4 = 128 points")
@@ -534,8 +542,10 @@ def main():
             graphed = False
             graph_note = f" (graph replay measured slower than eager here: {1e3 * t_graph:.1f} vs {1e3 * t_eager:.1f} ms per step on rank 0's clock)"
             note("graph replay slower than eager steps on this box: staying eager" + graph_note)
+    # the roofline: from the timed steps themselves when they run eagerly; a replayed run needs eager steps of its own (--full)
+    prof = not args.no_prof and (args.full or not graphed)
     barrier()
-    if not args.no_prof and not graphed:
+    if prof and not graphed:
         lib.neat_prof_enable(1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -548,7 +558,7 @@ def main():
         dump_outputs(args.dump_outputs, out, losses, tr.model)
         note(f"outputs of the last timed step written to {args.dump_outputs}")
     dist_info = None
-    if dist.is_initialized():
+    if dist.is_initialized() and args.full:
         # what a bad scaling curve would be diagnosed from, in the same line: every rank's own time per step (the headline uses the
         # MAX), how long each rank's steps take WITHOUT the exchange being waited on (its GPU work), and the gradient all-reduce alone
         # (the flat 4.9 MB bucket, 20 back-to-back calls between HIP events, after the timed region)
@@ -595,7 +605,7 @@ def main():
     if graphed:
         tr.check_nan()
     prof_elapsed, prof_note, n_prof = elapsed, "HIP events over the timed region", args.steps
-    if not args.no_prof and graphed:
+    if prof and graphed:
         # a graph replay does not pass through the library's launch code, so its kernels cannot be bracketed with events:
         # the same steps are run eagerly right after the timed region (same kernels, same arguments) for the roofline
         n_prof = min(args.steps, 10)
@@ -610,7 +620,7 @@ def main():
 
     roofline = None
     kernels = {}
-    if not args.no_prof:
+    if prof:
         # launch classes of the library's event brackets: 0 per-layer GEMM launches, 1 weight gradients, 2 fused SDF primal chain,
         # 3 fused SDF adjoint chain (the normals), 4 the heads' fused chains (forward and backward)
         for cls, name in ((0, "layer_kernel"), (1, "wgrad_kernel"), (2, "sdf_fused_kernel"), (3, "sdf_adjoint_kernel"), (4, "head_chain_kernel")):
@@ -712,9 +722,9 @@ def main():
         }
         if _lib.tuning_overrides:
             line["config"]["tuning_overrides"] = list(_lib.tuning_overrides)      # NEAT_TUNING was set: not the default kernels
-        if world == 1 and not args.no_secondary and args.workload == "c2":
+        if args.full and world == 1 and not args.no_secondary and args.workload == "c2":
             line["secondary"] = secondary_legs(dev, sd, args.precision, args.steps, note)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             note("timing the CPU oracle (cpu_baseline)")
             line["cpu_baseline"] = cpu_baseline(42)
             note("cpu_baseline done")

@@ -4,14 +4,14 @@
 R=$PWD; O=$R/gpurun_out/refresh; rm -rf $O; mkdir -p $O
 T="timeout 600"
 $T python -m pytest tests -m gpu -x -q > $O/tests_full.log 2>&1; echo "pytest rc=$?" >> $O/tests_full.log; grep -v "^Extension modules" $O/tests_full.log | tail -12 | cut -c1-300 > $O/tests.log
-$T python bench.py > $O/bench_bf16.log 2>&1; grep '^{"metric"' $O/bench_bf16.log | tail -1 > $O/bench_bf16.json
-$T python bench.py --precision fp16x3 --no-secondary > $O/bench_fp16x3.log 2>&1; grep '^{"metric"' $O/bench_fp16x3.log | tail -1 > $O/bench_fp16x3.json
-$T python bench.py --precision fp32 --no-secondary --no-cpu-baseline > $O/bench_fp32.log 2>&1; grep '^{"metric"' $O/bench_fp32.log | tail -1 > $O/bench_fp32.json
-$T python bench.py --precision bf16x3 --no-secondary --no-cpu-baseline > $O/bench_bf16x3.log 2>&1; grep '^{"metric"' $O/bench_bf16x3.log | tail -1 > $O/bench_bf16x3.json
-$T python bench.py --precision fp16 --no-secondary --no-cpu-baseline > $O/bench_fp16.log 2>&1; grep '^{"metric"' $O/bench_fp16.log | tail -1 > $O/bench_fp16.json
+$T python bench.py --full > $O/bench_bf16.log 2>&1; grep '^{"metric"' $O/bench_bf16.log | tail -1 > $O/bench_bf16.json
+$T python bench.py --full --precision fp16x3 --no-secondary > $O/bench_fp16x3.log 2>&1; grep '^{"metric"' $O/bench_fp16x3.log | tail -1 > $O/bench_fp16x3.json
+$T python bench.py --full --precision fp32 --no-secondary --no-cpu-baseline > $O/bench_fp32.log 2>&1; grep '^{"metric"' $O/bench_fp32.log | tail -1 > $O/bench_fp32.json
+$T python bench.py --full --precision bf16x3 --no-secondary --no-cpu-baseline > $O/bench_bf16x3.log 2>&1; grep '^{"metric"' $O/bench_bf16x3.log | tail -1 > $O/bench_bf16x3.json
+$T python bench.py --full --precision fp16 --no-secondary --no-cpu-baseline > $O/bench_fp16.log 2>&1; grep '^{"metric"' $O/bench_fp16.log | tail -1 > $O/bench_fp16.json
 # the RCCL path on the one GPU: world size 1 with a real nccl group; round 6: pack + all-reduce + Adam inside the step's graph
-NEAT_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 $T python bench.py --no-secondary --no-cpu-baseline > $O/bench_bf16_rccl_world1.log 2>&1; grep '^{"metric"' $O/bench_bf16_rccl_world1.log | tail -1 > $O/bench_bf16_rccl_world1.json
-NEAT_GRAPH_TAIL=0 NEAT_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29612 $T python bench.py --no-secondary --no-cpu-baseline > $O/bench_bf16_rccl_world1_eager_tail.log 2>&1; grep '^{"metric"' $O/bench_bf16_rccl_world1_eager_tail.log | tail -1 > $O/bench_bf16_rccl_world1_eager_tail.json
+NEAT_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29611 $T python bench.py --full --no-secondary --no-cpu-baseline > $O/bench_bf16_rccl_world1.log 2>&1; grep '^{"metric"' $O/bench_bf16_rccl_world1.log | tail -1 > $O/bench_bf16_rccl_world1.json
+NEAT_GRAPH_TAIL=0 NEAT_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29612 $T python bench.py --full --no-secondary --no-cpu-baseline > $O/bench_bf16_rccl_world1_eager_tail.log 2>&1; grep '^{"metric"' $O/bench_bf16_rccl_world1_eager_tail.log | tail -1 > $O/bench_bf16_rccl_world1_eager_tail.json
 $T python scripts/bench_workloads.py 2>&1 | grep workload > $O/workloads.jsonl
 $T python scripts/bench_workloads.py --precision fp16x3 2>&1 | grep workload > $O/workloads_fp16x3.jsonl
 $T python scripts/runner_rate.py 512 4 2>&1 | grep "ms per iteration" > $O/runner_rate.txt
@@ -36,5 +36,5 @@ cp profiles/traffic.json $O/traffic.json
 python scripts/check_traffic.py $O/bench_bf16.json bf16 > $O/traffic_check.txt 2>&1 || echo "TRAFFIC CHECK FAILED" >> $O/traffic_check.txt
 cat $O/traffic_check.txt
 # the bench line once more with the fresh traffic / utilisation files in place (what profiles/r06_bench_bf16.json is)
-$T python bench.py > $O/bench_bf16.log 2>&1; grep '^{"metric"' $O/bench_bf16.log | tail -1 > $O/bench_bf16.json
+$T python bench.py --full > $O/bench_bf16.log 2>&1; grep '^{"metric"' $O/bench_bf16.log | tail -1 > $O/bench_bf16.json
 find $O -name "*counter_collection.csv" -size +20M -delete; du -sh $O

@@ -56,8 +56,8 @@ def test_bench_line_with_the_collective_agrees_with_the_plain_line():
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NEAT_FORCE_DIST")}
         env.update(extra_env)
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "3", "--no-secondary",
-                            "--no-cpu-baseline", "--no-prof"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "3", "--full",
+                            "--no-secondary", "--no-cpu-baseline", "--no-prof"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1, r.stdout
@@ -88,7 +88,7 @@ def test_c4_workload_line_with_the_collective():
     env.update({"NEAT_FORCE_DIST": "1", "WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c4", "--steps", "10", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-prof"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-prof"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
