@@ -7,7 +7,7 @@
 // NEAT_HALF = 1: the same kernels with IEEE half (f16) as the 16-bit storage / MFMA operand type instead of bf16 (precision NEAT_F16,
 // BASELINE config 5 "fp16 MFMA with fp32 accumulate").  Only this block knows the format: the conversions and the MFMA opcode; every
 // kernel moves the 16-bit values as opaque u16 / packed words.  The names keep their "bf" (bf16x8, f2bf, bf_lo ...): "the 16-bit type
-// of this build".  The f16 twin of each translation unit is compiled into its own namespace (see neat_api.hip).
+// of this build".  The f16 twin of each precision-dependent translation unit is compiled into its own namespace (see neat_net.hip; neat_aux.hip has no twin).
 #ifndef NEAT_HALF
 #define NEAT_HALF 0
 #endif
@@ -23,6 +23,17 @@ struct DevOnce {
   operator bool() const { return ((mask >> dev()) & 1ull) != 0; }
   DevOnce& operator=(bool v) { if (v) mask |= 1ull << dev(); else mask &= ~(1ull << dev()); return *this; }
 };
+#define NEAT_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)      // in a host helper that returns hipError_t
+// Raise the dynamic-LDS limit of the kernel variants Kerns to `bytes`, once per device.  A host call, not a stream operation: it is
+// made in front of the launch so that it stays out of a graph capture.
+template <auto... Kerns> hipError_t lds_limit(int bytes) {
+  static DevOnce done;
+  if (done) return hipSuccess;
+  hipError_t e = hipSuccess;
+  ((e = e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(Kerns), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)), ...);
+  if (e == hipSuccess) done = true;
+  return e;
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned short u16;

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bf16_common.hpp"
+#include "device_util.hpp"
 
 namespace neat {
 
@@ -600,10 +601,6 @@ __global__ __launch_bounds__(WG) void rowscale_kernel(RowScaleArgs a) {
 // small per-point kernels (feature-major outputs)
 // ---------------------------------------------------------------------------------------------
 // x = o + z d for p = r*S + i ; also writes row-major points if requested
-// A value the compiler may not fuse into an fma with its consumer.  (HIP's __fmul_rn / __fadd_rn are plain operators under the default
-// -ffp-contract=fast and DO get contracted: the round-5 form of the two kernels below compiled to v_fmac_f32 / v_pk_fma_f32.)
-__device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
-
 __global__ void points_from_rays_kernel(const float* __restrict__ o, const float* __restrict__ d,
                                         const float* __restrict__ z, int R, int S, int ldp,
                                         float* __restrict__ x_fm, float* __restrict__ pts_rm,
@@ -919,25 +916,6 @@ __global__ void zero_tail_kernel(float* __restrict__ a, int rows, int p_from, in
 // ---------------------------------------------------------------------------------------------
 // compositing (rend_a :540-554 volume_rendering, :406-426 integrals); one wave per ray
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_incl_scan(float v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const float t = __shfl_up(v, off);
-    if (lane >= off) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-// Laplace density (density.py:21-26) and its derivative pieces
-__device__ __forceinline__ float laplace_sigma(float s, float beta) {
-  const float sg = (s > 0.0f) ? 1.0f : ((s < 0.0f) ? -1.0f : 0.0f);
-  return (1.0f / beta) * (0.5f + 0.5f * sg * expm1f(-fabsf(s) / beta));
-}
-
 struct CompositeArgs {
   const float* z; const float* sdf; const float* dirs;   // [R,S], [P], [R,3]
   const float* x_fm; const float* rgb_fm; const float* lin_fm; const float* g_fm;   // [3|3|6|3][ldp]
@@ -1127,53 +1105,6 @@ __global__ __launch_bounds__(WG) void composite_bwd_kernel(CompositeBwdArgs a) {
   }
   dbeta = wave_sum(dbeta);
   if (lane == 0 && a.dbeta_ray) a.dbeta_ray[r] = dbeta / cs;
-}
-
-// pixel -> ray (rend_util.py:55-81,95-108)
-__device__ __forceinline__ void camera_ray(const float* __restrict__ uv, const float* __restrict__ pose, const float* __restrict__ Kin,
-                                           int kstride, int r, float* __restrict__ dirs, float* __restrict__ origins) {
-  const float fx = Kin[0], sk = Kin[1], cx = Kin[2], fy = Kin[kstride + 1], cy = Kin[kstride + 2];
-  const float u = uv[r * 2], v = uv[r * 2 + 1];
-  const float xl = (u - cx + cy * sk / fy - sk * v / fy) / fx;
-  const float yl = (v - cy) / fy;
-  float w[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float wc = pose[c * 4 + 0] * xl + pose[c * 4 + 1] * yl + pose[c * 4 + 2] * 1.0f + pose[c * 4 + 3] * 1.0f;
-    w[c] = wc - pose[c * 4 + 3];
-  }
-  const float n = fmaxf(sqrtf(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), 1e-12f);
-  dirs[r * 3 + 0] = w[0] / n; dirs[r * 3 + 1] = w[1] / n; dirs[r * 3 + 2] = w[2] / n;
-  if (origins) {          // the camera centre once per ray (the callers' `cam_loc.unsqueeze(1).repeat(1, R, 1)`, rend_a :395)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) origins[r * 3 + c] = pose[c * 4 + 3];
-  }
-}
-__global__ void camera_rays_kernel(const float* __restrict__ uv, const float* __restrict__ pose, const float* __restrict__ Kin,
-                                   int kstride, int R, float* __restrict__ dirs, float* __restrict__ origins) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  camera_ray(uv, pose, Kin, kstride, r, dirs, origins);
-}
-
-// eikonal points of a training step (rend_a :515-527): [uniform draws in the bounding cube | one point per ray at its drawn depth
-// o + z d | optional extra points (the global junctions)] as one [2R + J, 3] array, one launch instead of addcmul + cat (+ cat)
-__global__ void eik_points_kernel(const float* __restrict__ uniform, const float* __restrict__ o, const float* __restrict__ d,
-                                  const float* __restrict__ z_eik, const float* __restrict__ extra, int R, int J, float* __restrict__ out,
-                                  const float* __restrict__ z, int S, const long long* __restrict__ idx) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = (2 * R + J) * 3;
-  if (i >= n) return;
-  const int p = i / 3, c = i - 3 * p;
-  float v;
-  if (p < R) v = uniform[i];
-  else if (p < 2 * R) {
-    const int r = p - R;
-    const float ze = z_eik ? z_eik[r] : z[(size_t)r * S + idx[r]];     // the drawn depth, or the draw's index into the ray's depths
-    v = o[3 * r + c] + rounded(ze * d[3 * r + c]);      // `cam_loc + z_samples_eik * ray_dirs` (rend_a :519-520): product rounded, then the sum, like the main pass's points
-  }
-  else v = extra[i - 6 * R];
-  out[i] = v;
 }
 
 // d loss / d beta_param = sgn(beta_param) * sum over the rays of composite_bwd_kernel's per-ray partials (fixed order: one workgroup,

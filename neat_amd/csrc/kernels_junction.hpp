@@ -13,6 +13,7 @@
 // with -1; *n_match = number of pairs (-1: infeasible, i.e. a non-finite cost).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "device_util.hpp"
 
 namespace neat {
 

@@ -7,7 +7,7 @@
 //  * sample_pdf + the sort of get_z_vals_fine (:16-59, :97-106): sample_pdf_kernel.
 //  * UniformSampler.get_z_vals (:61-95): uniform_depths_kernel.
 #pragma once
-#include "kernels.hpp"
+#include "device_util.hpp"
 
 namespace neat {
 
@@ -778,6 +778,34 @@ __global__ void encode_lines_kernel(const float* __restrict__ lines, int N, int 
   lmap[4 * hw + idx] = e2x; lmap[5 * hw + idx] = e2y;
   label[idx] = bi;
   if (valid) valid[idx] = best < INFINITY ? 1 : 0;      // a nearest segment exists (N > 0 and not all segments non-finite)
+}
+
+// pixel -> ray, one thread per ray (camera_ray, device_util.hpp)
+__global__ void camera_rays_kernel(const float* __restrict__ uv, const float* __restrict__ pose, const float* __restrict__ Kin,
+                                   int kstride, int R, float* __restrict__ dirs, float* __restrict__ origins) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  camera_ray(uv, pose, Kin, kstride, r, dirs, origins);
+}
+
+// eikonal points of a training step (rend_a :515-527): [uniform draws in the bounding cube | one point per ray at its drawn depth
+// o + z d | optional extra points (the global junctions)] as one [2R + J, 3] array, one launch instead of addcmul + cat (+ cat)
+__global__ void eik_points_kernel(const float* __restrict__ uniform, const float* __restrict__ o, const float* __restrict__ d,
+                                  const float* __restrict__ z_eik, const float* __restrict__ extra, int R, int J, float* __restrict__ out,
+                                  const float* __restrict__ z, int S, const long long* __restrict__ idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = (2 * R + J) * 3;
+  if (i >= n) return;
+  const int p = i / 3, c = i - 3 * p;
+  float v;
+  if (p < R) v = uniform[i];
+  else if (p < 2 * R) {
+    const int r = p - R;
+    const float ze = z_eik ? z_eik[r] : z[(size_t)r * S + idx[r]];     // the drawn depth, or the draw's index into the ray's depths
+    v = o[3 * r + c] + rounded(ze * d[3 * r + c]);      // `cam_loc + z_samples_eik * ray_dirs` (rend_a :519-520): product rounded, then the sum, like the main pass's points
+  }
+  else v = extra[i - 6 * R];
+  out[i] = v;
 }
 
 }  // namespace neat

@@ -1,0 +1,626 @@
+// C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
+// samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, volume weights.
+// Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
+// boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
+#include "kernels_sampler.hpp"
+#include "kernels_junction.hpp"
+#include "kernels_parse.hpp"
+#include "../../include/neat_hip.h"
+#include <algorithm>
+#include <math.h>
+
+using namespace neat;
+
+// tuning keys 28 and 30: neat_set_tuning (neat_net.hip) hands them over
+__attribute__((visibility("hidden"))) int neat_aux_set_tuning(int key, int value);
+
+namespace {
+
+int g_ffn_mfma = 1;         // the 256 x 256 layers of the global-junction MLP (forward and data backward) on the fp32 matrix pipe (ffn_mfma_kernel) instead
+                            // of the vector-ALU kernel (tuning key 28)
+int g_sampler_ablate = 0;   // probes: sampler_round_kernel without its bisection (1) / refine (2) / final (4) part (tuning key 30)
+
+#define NEAT_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
+inline dim3 grid1(int n, int b = 256) { return dim3((n + b - 1) / b); }
+
+__global__ void volume_weights_kernel(const float* __restrict__ z, const float* __restrict__ sdf, int R, int S,
+                                      const float* __restrict__ beta_ptr, float* __restrict__ weights) {
+  const float beta = *beta_ptr;
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  float carry = 0.0f;
+  for (int i0 = 0; i0 < S; i0 += 64) {
+    const int i = i0 + lane;
+    const bool ok = i < S;
+    const int p = r * S + (ok ? i : S - 1);
+    const float delta = (i + 1 < S) ? z[p + 1] - z[p] : 1e10f;
+    const float e = ok ? delta * laplace_sigma(sdf[p], beta) : 0.0f;
+    const float incl = wave_incl_scan(e, lane);
+    float excl = __shfl_up(incl, 1);
+    if (lane == 0) excl = 0.0f;
+    if (ok) weights[p] = (1.0f - expf(-e)) * expf(-(carry + excl));
+    carry += __shfl(incl, 63);
+  }
+}
+
+}  // namespace
+
+int neat_aux_set_tuning(int key, int value) {
+  if (key == 28 && (value == 0 || value == 1)) { g_ffn_mfma = value; return 0; }
+  if (key == 30 && value >= 0 && value <= 7) { g_sampler_ablate = value; return 0; }
+  return -1;
+}
+
+extern "C" {
+
+int neat_camera_rays(const float* uv, const float* pose, const float* K, int kstride, int R, float* dirs, float* origins, void* stream) {
+  if (R <= 0) return 0;
+  hipLaunchKernelGGL(camera_rays_kernel, grid1(R), dim3(256), 0, (hipStream_t)stream, uv, pose, K, kstride, R, dirs, origins);
+  return (int)hipGetLastError();
+}
+
+int neat_eik_points(const float* uniform, const float* origins, const float* dirs, const float* z_eik, const float* extra, int R, int J,
+                    float* out, const float* z, int S, const long long* idx, void* stream) {
+  if (R <= 0 || J < 0) return R == 0 && J == 0 ? 0 : -1;
+  if (!uniform || !origins || !dirs || !out || (J > 0 && !extra)) return -1;
+  if (!z_eik && (!z || !idx || S <= 0)) return -1;           // the depth per ray: given, or picked from the ray's S depths by idx
+  hipLaunchKernelGGL(eik_points_kernel, grid1((2 * R + J) * 3), dim3(256), 0, (hipStream_t)stream, uniform, origins, dirs, z_eik, extra, R, J, out,
+                     z, S, idx);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_bound(const float* z, int n, int R, const float* sdf_old, const float* sdf_new, const int* order, int n_old,
+                       const float* beta_in, const float* beta0, float eps, int iters, float* sdf_out, float* beta_out,
+                       int* flag, void* stream) {
+  if (R <= 0) return 0;
+  if (n < 2 || n > SMAX || !z || !sdf_new || !beta_in || !beta0 || !sdf_out || !beta_out || !flag) return -1;
+  SamplerBoundArgs a{z, n, R, sdf_old, sdf_new, order, n_old, beta_in, beta0, eps, iters, sdf_out, beta_out, flag, nullptr, 0};
+  hipLaunchKernelGGL(sampler_bound_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_resample(const float* z, const float* sdf, int n, int R, const float* beta, int refine, float add_tiny,
+                          const float* u, int u_stride, int N, float* samples, float* z_merged, int* order, void* stream) {
+  if (R <= 0) return 0;
+  if (n < 2 || n > SMAX || N < 1 || N > SMAX || !z || !sdf || !beta || !u || !samples || (refine && (!z_merged || !order))) return -1;
+  SamplerResampleArgs a{};
+  a.z = z; a.sdf = sdf; a.n = n; a.R = R; a.beta = beta; a.refine = refine; a.add_tiny = add_tiny; a.u = u; a.u_stride = u_stride; a.N = N;
+  a.samples = samples; a.z_merged = z_merged; a.order = order;
+  hipLaunchKernelGGL(sampler_resample_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_finish(const float* samples, int N, const float* z, int n, const int* pick, int n_extra, float near, float far,
+                        int R, const int* eik_idx, float* z_vals, float* z_eik, void* stream) {
+  if (R <= 0) return 0;
+  if (N + 2 + n_extra > SMAX || !samples || !z || (n_extra > 0 && !pick) || !eik_idx || !z_vals || !z_eik) return -1;
+  SamplerFinishArgs a{samples, N, z, n, pick, n_extra, near, far, R, eik_idx, z_vals, z_eik, n};
+  hipLaunchKernelGGL(sampler_finish_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sample_pdf(const float* bins, const float* weights, int nb, int R, const float* u, int u_stride, int N, float* samples,
+                    const float* z_merge, int nz, float* z_out, void* stream) {
+  if (R <= 0) return 0;
+  if (nb < 2 || nb > SMAX || N < 1 || N > SMAX || !bins || !weights || !u || !samples || (z_merge && (!z_out || nz < 0 || nz + N > SMAX))) return -1;
+  SamplePdfArgs a{bins, weights, nb, R, u, u_stride, N, samples, z_merge, nz, z_out};
+  hipLaunchKernelGGL(sample_pdf_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_uniform_depths(const float* near_r, float near_s, const float* far_r, float far_s, const float* t, const float* rnd, int R, int N,
+                        float* z, void* stream) {
+  if (R <= 0 || N <= 0) return 0;
+  if (!t || !z) return -1;
+  hipLaunchKernelGGL(uniform_depths_kernel, dim3((R * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, near_r, near_s, far_r, far_s, t, rnd, R, N, z);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_init(const float* z, int R, int n, const float* beta, float beta_min, float beta_c, float* beta0, float* beta_ray,
+                      int* ctl, int nctl, void* stream) {
+  return neat_sampler_init_rays(z, R, n, beta, beta_min, beta_c, beta0, beta_ray, ctl, nctl, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0,
+                                nullptr, stream);
+}
+
+int neat_sampler_init_rays(const float* z, int R, int n, const float* beta, float beta_min, float beta_c, float* beta0, float* beta_ray,
+                           int* ctl, int nctl, const float* origins, const float* dirs, float* x_fm, int ldp, const float* keys, int n_step,
+                           int n_cand, int n_extra, int* pick_all, void* stream) {
+  if (R <= 0 || n < 2 || n > SMAX || !z || !beta || !beta0 || !beta_ray || nctl < 0 || (nctl > 0 && !ctl)) return -1;
+  if (x_fm && (!origins || !dirs || (long long)ldp < (long long)R * n)) return -1;
+  const bool picks = keys != nullptr;
+  if (picks && (!pick_all || n_step < 1 || n_cand < 1 || n_extra < 2 || n_extra > n_step || n_step * n_cand > SMAX)) return -1;
+  SamplerInitArgs a{z, R, n, beta, beta_min, beta_c, beta0, beta_ray, ctl, nctl, origins, dirs, x_fm, ldp, keys, n_step, n_cand, n_extra, pick_all,
+                    (R + 3) / 4, picks ? (n_step * n_cand + 255) / 256 : 0};
+  hipLaunchKernelGGL(sampler_init_kernel, dim3(a.init_blocks + n_cand * a.pick_parts), dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_round(const float* z, int n, int R, const float* sdf_old, const float* sdf_new, const int* order, int n_old,
+                       const float* beta_in, const float* beta0, float eps, int iters, float* sdf_out, float* beta_out, int* ctl, int round,
+                       int max_rounds, float add_tiny, const float* u_refine, int N_refine, float* samples_refine, float* z_merged,
+                       int* order_out, const float* origins, const float* dirs, float* x_fm, int ldp, const float* u_final,
+                       int u_final_stride, int N_final, float* samples_final, float* z_final, int ld_final, void* stream) {
+  if (R <= 0) return 0;
+  const bool last = round + 1 >= max_rounds;
+  if (n < 2 || n > SMAX || !z || !sdf_new || (order && !sdf_old) || !beta_in || !beta0 || !sdf_out || !beta_out || !ctl || round < 0 ||
+      round >= max_rounds || N_final < 1 || N_final > SMAX || !u_final || !samples_final || !z_final || ld_final < n) return -1;
+  if (!last && (N_refine < 1 || n + N_refine > SMAX || !u_refine || !samples_refine || !z_merged || !order_out ||
+                (x_fm && (!origins || !dirs || (long long)ldp < (long long)R * N_refine)))) return -1;
+  SamplerRoundArgs a{z, n, R, sdf_old, sdf_new, order, n_old, beta_in, beta0, eps, iters, sdf_out, beta_out, ctl, round, max_rounds, add_tiny,
+                     u_refine, N_refine, samples_refine, z_merged, order_out, origins, dirs, x_fm, ldp, u_final, u_final_stride, N_final,
+                     samples_final, z_final, ld_final, g_sampler_ablate};
+  hipLaunchKernelGGL(sampler_round_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_finish_picked(const float* samples, int N, const float* z_final, int ld_final, const int* n_final, const int* pick_all,
+                               int n_step, int n_extra, float near, float far, int R, const int* eik_idx, float* z_vals, float* z_eik,
+                               void* stream) {
+  if (R <= 0) return 0;
+  if (N + 2 + n_extra > SMAX || ld_final > SMAX || !samples || !z_final || !n_final || n_extra == 1 || n_extra < 0 || n_step < 1 || !eik_idx ||
+      !z_vals || !z_eik) return -1;
+  SamplerFinishArgs a{samples, N, z_final, 0, pick_all, n_extra, near, far, R, eik_idx, z_vals, z_eik, ld_final};
+  a.n_final = n_final; a.n_step = n_step;
+  hipLaunchKernelGGL(sampler_finish_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_bound_dev(const float* z, int n, int R, const float* sdf_old, const float* sdf_new, const int* order, int n_old,
+                           const float* beta_in, const float* beta0, float eps, int iters, float* sdf_out, float* beta_out,
+                           int* open, const int* gate, int gate_value, void* stream) {
+  if (R <= 0) return 0;
+  if (n < 2 || n > SMAX || !z || !sdf_new || !beta_in || !beta0 || !sdf_out || !beta_out || !open) return -1;
+  SamplerBoundArgs a{z, n, R, sdf_old, sdf_new, order, n_old, beta_in, beta0, eps, iters, sdf_out, beta_out, open, gate, gate_value};
+  hipLaunchKernelGGL(sampler_bound_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_resample_dev(const float* z, const float* sdf, int n, int R, const float* beta, float add_tiny,
+                              const float* u_refine, int N_refine, float* samples_refine, float* z_merged, int* order,
+                              const float* u_final, int u_final_stride, int N_final, float* samples_final, float* z_final, int ld_final,
+                              int* n_final, const int* open, int* cont, int round, int max_rounds, void* stream) {
+  if (R <= 0) return 0;
+  if (n < 2 || n > SMAX || N_refine < 1 || N_final < 1 || n + N_refine > SMAX || ld_final < n || !z || !sdf || !beta || !u_refine || !u_final ||
+      !samples_refine || !z_merged || !order || !samples_final || !z_final || !n_final || !open || !cont || round < 0 || round >= max_rounds)
+    return -1;
+  SamplerResampleArgs a{};
+  a.z = z; a.sdf = sdf; a.n = n; a.R = R; a.beta = beta; a.refine = 1; a.add_tiny = add_tiny;
+  a.u = u_refine; a.u_stride = 0; a.N = N_refine; a.samples = samples_refine; a.z_merged = z_merged; a.order = order;
+  a.open = open; a.cont = cont; a.round = round; a.max_rounds = max_rounds;
+  a.u_final = u_final; a.u_final_stride = u_final_stride; a.N_final = N_final; a.samples_final = samples_final;
+  a.z_final = z_final; a.ld_final = ld_final; a.n_final = n_final;
+  hipLaunchKernelGGL(sampler_resample_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_sampler_finish_dev(const float* samples, int N, const float* z_final, int ld_final, const int* n_final, const float* keys,
+                            int n_extra, int* pick, float near, float far, int R, const int* eik_idx, float* z_vals, float* z_eik,
+                            void* stream) {
+  if (R <= 0) return 0;
+  if (N + 2 + n_extra > SMAX || ld_final > SMAX || !samples || !z_final || !n_final || (n_extra > 0 && !pick) || n_extra == 1 || !eik_idx ||
+      !z_vals || !z_eik) return -1;
+  if (n_extra > 0) hipLaunchKernelGGL(sampler_pick_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_final, keys, n_extra, pick);
+  SamplerFinishArgs a{samples, N, z_final, 0, pick, n_extra, near, far, R, eik_idx, z_vals, z_eik, ld_final};
+  hipLaunchKernelGGL(sampler_finish_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_encode_lines(const float* lines, int N, int H, int W, float* lmap, int* label, unsigned char* valid, void* stream) {
+  if (N < 0 || H <= 0 || W <= 0 || (N > 0 && !lines) || !lmap || !label) return -1;
+  hipLaunchKernelGGL(encode_lines_kernel, grid1(H * W), dim3(256), 0, (hipStream_t)stream, lines, N, H, W, lmap, label, valid);
+  return (int)hipGetLastError();
+}
+
+int neat_gather_batch(const int* pool, int npool, const long long* draw, int n, int W, const float* att, const float* rgb, const int* labels,
+                      const float* lines, int nlines, float* uv, float* uv_proj, float* rgb_out, float* lines_out, long long* labels_out,
+                      long long* pixel_out, void* stream) {
+  if (n < 0 || npool <= 0 || W <= 0 || nlines <= 0 || !pool || !att || !rgb || !labels || !lines) return -1;
+  if (n == 0) return 0;
+  if (!draw || !uv || !uv_proj || !rgb_out || !lines_out || !labels_out || !pixel_out) return -1;
+  GatherBatchArgs a{pool, draw, n, W, npool, att, rgb, labels, lines, nlines, uv, uv_proj, rgb_out, lines_out, labels_out, pixel_out};
+  hipLaunchKernelGGL(gather_batch_kernel, grid1(n), dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_copy_batch(const void* const* src, void* const* dst, const long long* nbytes, int n, void* stream) {
+  if (n < 0 || n > COPY_BATCH_MAX) return -1;
+  if (n == 0) return 0;
+  if (!src || !dst || !nbytes) return -1;
+  CopyBatchArgs a{};
+  long long mx = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!src[i] || !dst[i] || nbytes[i] < 0 || (nbytes[i] & 3) || ((size_t)src[i] & 3) || ((size_t)dst[i] & 3)) return -1;
+    a.src[i] = (const unsigned*)src[i]; a.dst[i] = (unsigned*)dst[i]; a.words[i] = nbytes[i] >> 2;
+    mx = nbytes[i] > mx ? nbytes[i] : mx;
+  }
+  a.n = n;
+  const int by = (int)((mx / 4 + 1023) / 1024);          // 256 threads x 4 words per block
+  hipLaunchKernelGGL(copy_batch_kernel, dim3(by < 1 ? 1 : (by > 1024 ? 1024 : by), n), dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_adam_step(float* params, const float* const* grads, const long long* seg_offsets, const int* seg_steps, int nseg,
+                   float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, void* stream) {
+  if (nseg <= 0) return 0;
+  if (!params || !grads || !seg_offsets || !seg_steps || !exp_avg || !exp_avg_sq || nseg > ADAM_MAXSEG) return -1;
+  AdamSegs segs{};
+  for (int s = 0; s < nseg; ++s) {
+    segs.g[s] = grads[s]; segs.off[s] = seg_offsets[s];
+    if (grads[s]) {
+      if (seg_steps[s] < 1) return -1;
+      const double bc1 = 1.0 - pow((double)beta1, (double)seg_steps[s]), bc2 = 1.0 - pow((double)beta2, (double)seg_steps[s]);
+      segs.lr_over_bc1[s] = (float)((double)lr / bc1); segs.inv_sqrt_bc2[s] = (float)(1.0 / sqrt(bc2));
+    }
+  }
+  segs.off[nseg] = seg_offsets[nseg];
+  segs.nseg = nseg;
+  const long long n = seg_offsets[nseg];
+  if (n <= 0) return 0;
+  const long long per_block = 1024LL * ADAM_PASSES;    // ADAM_PASSES float4 passes of 256 threads
+  const long long blocks = (n + per_block - 1) / per_block;
+  hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, segs, exp_avg,
+                     exp_avg_sq, n, beta1, beta2, eps, (const float*)nullptr);
+  return (int)hipGetLastError();
+}
+
+int neat_adam_step_coef(float* params, const float* const* grads, const long long* seg_offsets, int nseg, float* exp_avg, float* exp_avg_sq,
+                        const float* coef, float beta1, float beta2, float eps, void* stream) {
+  if (nseg <= 0) return 0;
+  if (!params || !grads || !seg_offsets || !exp_avg || !exp_avg_sq || !coef || nseg > ADAM_MAXSEG) return -1;
+  AdamSegs segs{};
+  for (int s = 0; s < nseg; ++s) { segs.g[s] = grads[s]; segs.off[s] = seg_offsets[s]; }
+  segs.off[nseg] = seg_offsets[nseg];
+  segs.nseg = nseg;
+  const long long n = seg_offsets[nseg];
+  if (n <= 0) return 0;
+  const long long per_block = 1024LL * ADAM_PASSES;
+  const long long blocks = (n + per_block - 1) / per_block;
+  hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, segs, exp_avg,
+                     exp_avg_sq, n, beta1, beta2, eps, coef);
+  return (int)hipGetLastError();
+}
+
+int neat_ffn_forward(const float* x, int J, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
+                     const float* b2, float* h1, float* h2, float* y, void* stream) {
+  if (J <= 0) return 0;
+  if (!x || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !h1 || !h2 || !y) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (J > FFN_FUSED_MIN_ROWS) {       // many rows: one fused launch, 8 rows per workgroup
+    hipLaunchKernelGGL(ffn_forward_kernel, dim3((J + FFN_RB - 1) / FFN_RB), dim3(FFN_H), 0, st, x, J, W0, b0, W1, b1, W2, b2, h1, h2, y);
+    return (int)hipGetLastError();
+  }
+  // few rows (the 64 latents of the ABC scenes): one launch per layer, each spread over rows x 32-output blocks
+  const dim3 gh((J + FFN_RB - 1) / FFN_RB, FFN_H / 32), g3((J + FFN_RB - 1) / FFN_RB, 1);
+  const float* nogate = nullptr; float* noy2 = nullptr;
+  if (g_ffn_mfma) {      // the two 256 x 256 layers on the fp32 matrix pipe (tuning key 28)
+    const dim3 gm((J + 31) / 32, FFN_H / 32);
+    hipLaunchKernelGGL(ffn_mfma_kernel<false>, gm, dim3(256), 0, st, x, J, W0, b0, nogate, 1, h1);
+    hipLaunchKernelGGL(ffn_mfma_kernel<false>, gm, dim3(256), 0, st, (const float*)h1, J, W1, b1, nogate, 1, h2);
+  } else {
+    hipLaunchKernelGGL(ffn_dense_kernel<false>, gh, dim3(256), 0, st, x, J, FFN_H, FFN_H, W0, b0, nogate, 1, h1, noy2);
+    hipLaunchKernelGGL(ffn_dense_kernel<false>, gh, dim3(256), 0, st, (const float*)h1, J, FFN_H, FFN_H, W1, b1, nogate, 1, h2, noy2);
+  }
+  hipLaunchKernelGGL(ffn_dense_kernel<false>, g3, dim3(256), 0, st, (const float*)h2, J, FFN_H, 3, W2, b2, nogate, 0, y, noy2);
+  return (int)hipGetLastError();
+}
+
+int neat_ffn_backward(const float* x, int J, const float* W0, const float* W1, const float* W2, const float* h1, const float* h2,
+                      const float* dy, float* ws2, float* dx, float* dW0, float* db0, float* dW1, float* db1, float* dW2, float* db2,
+                      void* stream) {
+  if (J <= 0) return 0;
+  if (!x || !W0 || !W1 || !W2 || !h1 || !h2 || !dy || !ws2 || !dx || !dW0 || !db0 || !dW1 || !db1 || !dW2 || !db2) return -1;
+  float* d_a1 = ws2; float* d_a2 = ws2 + (size_t)J * FFN_H;
+  hipStream_t st = (hipStream_t)stream;
+  if (J > FFN_FUSED_MIN_ROWS)
+    hipLaunchKernelGGL(ffn_backward_data_kernel, dim3((J + FFN_RB - 1) / FFN_RB), dim3(FFN_H), 0, st, dy, J, W0, W1, W2, h1, h2, d_a1, d_a2, dx);
+  else {
+    const dim3 gh((J + FFN_RB - 1) / FFN_RB, FFN_H / 32);
+    const float* nobias = nullptr; const float* nogate = nullptr; float* noy2 = nullptr;
+    hipLaunchKernelGGL(ffn_dense_kernel<true>, gh, dim3(256), 0, st, dy, J, 3, FFN_H, W2, nobias, h2, 0, d_a2, noy2);
+    if (g_ffn_mfma) {
+      const dim3 gm((J + 31) / 32, FFN_H / 32);
+      hipLaunchKernelGGL(ffn_mfma_kernel<true>, gm, dim3(256), 0, st, (const float*)d_a2, J, W1, nobias, h1, 0, d_a1);
+      hipLaunchKernelGGL(ffn_mfma_kernel<true>, gm, dim3(256), 0, st, (const float*)d_a1, J, W0, nobias, nogate, 0, dx);
+    } else {
+      hipLaunchKernelGGL(ffn_dense_kernel<true>, gh, dim3(256), 0, st, (const float*)d_a2, J, FFN_H, FFN_H, W1, nobias, h1, 0, d_a1, noy2);
+      hipLaunchKernelGGL(ffn_dense_kernel<true>, gh, dim3(256), 0, st, (const float*)d_a1, J, FFN_H, FFN_H, W0, nobias, nogate, 0, dx, noy2);
+    }
+  }
+  if (g_ffn_mfma)
+    hipLaunchKernelGGL(ffn_wgrad_mfma_kernel, dim3(FFN_H / 32, FFN_H / 32, 3), dim3(64 * FFN_WNW), 0, (hipStream_t)stream, x, h1, h2, d_a1, d_a2, dy, J, dW0, db0,
+                       dW1, db1, dW2, db2);
+  else
+  hipLaunchKernelGGL(ffn_backward_weights_kernel, dim3(FFN_H / FFN_RN, 3), dim3(64 * FFN_JG), 0, (hipStream_t)stream, x, h1, h2, d_a1, d_a2, dy, J, dW0, db0,
+                     dW1, db1, dW2, db2);
+  return (int)hipGetLastError();
+}
+
+int neat_loss_terms(const float* rgb, const float* rgb_gt, int R, const float* gtheta, int E, const float* loc3, const float* loc2c, int K,
+                    const float* glo3, const float* glo2c, int J, float* scal, float* d_rgb, float* d_gtheta, float* pair_cost,
+                    float eik_grad_scale, void* stream) {
+  if (R <= 0 || !rgb || !rgb_gt || !scal || !d_rgb || E < 0 || K < 0 || J < 0) return -1;
+  if ((E > 0 && (!gtheta || !d_gtheta)) || (K > 0 && J > 0 && (!loc3 || !loc2c || !glo3 || !glo2c || !pair_cost))) return -1;
+  LossTermsArgs a{rgb, rgb_gt, R, gtheta, E, loc3, loc2c, (J > 0 ? K : 0), glo3, glo2c, J, scal, d_rgb, d_gtheta, pair_cost, eik_grad_scale};
+  hipLaunchKernelGGL(loss_terms_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_loss_lines_terms(const float* pred_px, const float* pred_calib, const float* gt5, const float* Kmat, int L, float threshold, float* out3,
+                          float* d_pred_calib, float grad_scale, const float* rgb, const float* rgb_gt, int R, const float* gtheta, int E,
+                          const float* loc3, const float* loc2c, int K, const float* glo3, const float* glo2c, int J, float* scal, float* d_rgb,
+                          float* d_gtheta, float* pair_cost, float eik_grad_scale, const float* w2c, const float* lines3d, float* d_lines3d,
+                          void* stream) {
+  if (L <= 0 || !pred_px || !pred_calib || !gt5 || !Kmat || !out3 || !d_pred_calib) return -1;
+  if (d_lines3d && (!w2c || !lines3d)) return -1;
+  if (R <= 0 || !rgb || !rgb_gt || !scal || !d_rgb || E < 0 || K < 0 || J < 0) return -1;
+  if ((E > 0 && (!gtheta || !d_gtheta)) || (K > 0 && J > 0 && (!loc3 || !loc2c || !glo3 || !glo2c || !pair_cost))) return -1;
+  LineLossesArgs l{pred_px, pred_calib, gt5, Kmat, L, threshold, out3, d_pred_calib, grad_scale, w2c, lines3d, d_lines3d};
+  LossTermsArgs a{rgb, rgb_gt, R, gtheta, E, loc3, loc2c, (J > 0 ? K : 0), glo3, glo2c, J, scal, d_rgb, d_gtheta, pair_cost, eik_grad_scale};
+  hipLaunchKernelGGL(loss_lines_terms_kernel, dim3(2), dim3(1024), 0, (hipStream_t)stream, l, a);
+  return (int)hipGetLastError();
+}
+
+int neat_loss_pairs(const long long* ri, const long long* ci, const int* n_match, int Kmax, const float* loc3, const float* loc2c,
+                    const float* loc2, const float* glo3, const float* glo2c, const float* glo2, int J, const float* pair_cost, float* scal,
+                    float* d_glo3, float* d_glo2c, const float* line_loss, float w_eik, float w_line, float w_j3, float w_j2, int weighted_grads,
+                    float* total, const float* w2c, void* stream) {
+  if (Kmax < 0 || J <= 0 || !ri || !ci || !n_match || !loc3 || !loc2c || !loc2 || !glo3 || !glo2c || !glo2 || !pair_cost || !scal ||
+      !d_glo3 || !d_glo2c || !line_loss) return -1;
+  LossPairsArgs a{ri, ci, n_match, Kmax, loc3, loc2c, loc2, glo3, glo2c, glo2, J, pair_cost, scal, d_glo3, d_glo2c, line_loss, w_eik, w_line,
+                  w_j3, w_j2, weighted_grads, total, w2c};
+  hipLaunchKernelGGL(loss_pairs_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_l3d(const float* x, const float* o, const float* d, const float* normal, int R, float* l3d, void* stream) {
+  if (R <= 0) return 0;
+  if (!x || !o || !d || !normal || !l3d) return -1;
+  hipLaunchKernelGGL(l3d_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, o, d, normal, R, l3d);
+  return (int)hipGetLastError();
+}
+
+int neat_junction_cost(const float* cand2d, const float* gt2d, int V, int C, float* cost, void* stream) {
+  if (V <= 0 || C <= 0) return 0;
+  if (!cand2d || !gt2d || !cost) return -1;
+  hipLaunchKernelGGL(junction_cost_kernel, dim3((V * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, cand2d, gt2d, V, C, cost);
+  return (int)hipGetLastError();
+}
+
+int neat_junction_gate(const long long* rows, const long long* cols, int K, const float* cost, int C, const float* cand3d,
+                       const float* cand2d, const float* cand2d_calib, int use_median, float* median, unsigned char* good, float* j3d,
+                       float* j2d, float* j2d_calib, void* stream) {
+  if (K <= 0) return 0;
+  if (K > 2048 || !rows || !cols || !cost || !cand3d || !cand2d || !cand2d_calib || !good || !j3d || !j2d || !j2d_calib ||
+      (use_median && !median)) return -1;
+  JunctionGateArgs a{rows, cols, K, cost, C, cand3d, cand2d, cand2d_calib, use_median, median, good, j3d, j2d, j2d_calib};
+  hipLaunchKernelGGL(junction_gate_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_inv_small(const float* A, int n, int lda, float* out, void* stream) {
+  if (!A || !out || n < 1 || n > 4 || lda < n) return -1;
+  hipLaunchKernelGGL(inv_small_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, A, n, lda, out);
+  return (int)hipGetLastError();
+}
+
+int neat_camera_mats(const float* pose, const float* K, int kstride, float* w2c, float* K3, void* stream) {
+  if (!pose || !K || !w2c || !K3 || kstride < 3) return -1;
+  hipLaunchKernelGGL(camera_mats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, pose, K, kstride, w2c, K3);
+  return (int)hipGetLastError();
+}
+
+int neat_project2d(const float* K, const float* w2c, const float* X, int N, float* uv, void* stream) {
+  if (N <= 0) return 0;
+  if (!K || !w2c || !X || !uv) return -1;
+  hipLaunchKernelGGL(project2d_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, w2c, X, N, uv);
+  return (int)hipGetLastError();
+}
+
+int neat_project2d_pair(const float* K, const float* K2, const float* w2c, const float* X, int N, float* uv, float* uv2, void* stream) {
+  if (N <= 0) return 0;
+  if (!K || !K2 || !w2c || !X || !uv || !uv2) return -1;
+  hipLaunchKernelGGL(project2d_pair_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, K2, w2c, X, N, uv, uv2);
+  return (int)hipGetLastError();
+}
+
+int neat_camera_setup(const float* uv, const float* uv2, const float* pose, const float* K, int kstride, int R, float* dirs, float* origins,
+                      float* dirs2, float* w2c, float* K3, void* stream) {
+  if (R <= 0 || !uv || !pose || !K || !dirs || !origins || (uv2 && !dirs2) || !w2c || !K3 || kstride < 3) return -1;
+  hipLaunchKernelGGL(camera_setup_kernel, grid1(R), dim3(256), 0, (hipStream_t)stream, uv, uv2, pose, K, kstride, R, dirs, origins, dirs2, w2c, K3);
+  return (int)hipGetLastError();
+}
+
+int neat_project2d_backward(const float* K, const float* w2c, const float* X, int N, const float* d_uv, float* d_X, void* stream) {
+  if (N <= 0) return 0;
+  if (!K || !w2c || !X || !d_uv || !d_X) return -1;
+  hipLaunchKernelGGL(project2d_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, w2c, X, N, d_uv, d_X);
+  return (int)hipGetLastError();
+}
+
+int neat_line_loss(const float* pred, const float* gt, const float* weight, int R, float threshold, float* out2, float* per_line,
+                   float* d_pred, void* stream) {
+  if (R <= 0 || !pred || !gt || !weight || !out2 || !per_line || !d_pred) return -1;
+  hipLaunchKernelGGL(line_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, gt, weight, R, threshold, out2, per_line, d_pred);
+  return (int)hipGetLastError();
+}
+
+int neat_line_losses(const float* pred_px, const float* pred_calib, const float* gt5, const float* K, int R, float threshold, float* out3,
+                     float* d_pred_calib, float grad_scale, void* stream) {
+  if (R <= 0 || !pred_px || !pred_calib || !gt5 || !K || !out3 || !d_pred_calib) return -1;
+  hipLaunchKernelGGL(line_losses_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred_px, pred_calib, gt5, K, R, threshold, out3, d_pred_calib, grad_scale);
+  return (int)hipGetLastError();
+}
+
+size_t neat_lsap_ws_bytes(int nr, int nc) {
+  const size_t mx = (size_t)(nr > nc ? nr : nc), mn = (size_t)(nr < nc ? nr : nc);
+  return (mn + 2 * mx) * sizeof(double) + ((size_t)nr + (size_t)nc + 5 * mx + 2 * mn) * sizeof(int);
+}
+
+int neat_lsap(const float* cost, int nr, int nc, const unsigned char* row_mask, const unsigned char* col_mask, long long* row_ind,
+              long long* col_ind, int* n_match, void* ws, void* stream) {
+  if (nr < 0 || nc < 0 || !n_match) return -1;
+  if (nr == 0 || nc == 0) return (int)hipMemsetAsync(n_match, 0, sizeof(int), (hipStream_t)stream);
+  if (!cost || !row_ind || !col_ind || !ws) return -1;
+  const size_t mx = (size_t)(nr > nc ? nr : nc), mn = (size_t)(nr < nc ? nr : nc);
+  LsapArgs a{cost, nr, nc, row_mask, row_ind, col_ind, n_match, (double*)ws, (int*)((double*)ws + mn + 2 * mx)};
+  a.col_mask = col_mask;
+  const size_t dbytes = (mn + 2 * mx) * sizeof(double), ibytes = ((size_t)nr + (size_t)nc + 5 * mx + 2 * mn) * sizeof(int);
+  size_t lds = 0;
+  constexpr size_t LSAP_LDS_MAX = 156 * 1024;
+  a.cost_lds_off = -1;
+  if (dbytes + ibytes <= LSAP_LDS_MAX) {
+    NEAT_CHECK(lds_limit<&lsap_kernel>((int)LSAP_LDS_MAX));
+    a.use_lds = 1; a.lds_int_off = (int)dbytes; lds = (dbytes + ibytes + 15) & ~(size_t)15;
+    const size_t cbytes = (size_t)nr * nc * sizeof(float);
+    if (lds + cbytes <= LSAP_LDS_MAX) { a.cost_lds_off = (int)lds; lds += cbytes; }      // the cost matrix too (8 x 2048 fits)
+  }
+  // threads: two columns per thread, whole waves (a small problem does not pay 16-wave barriers; eight columns per thread measured slower)
+  int threads = (int)((mx + 1) / 2 + 63) / 64 * 64;
+  threads = threads < 64 ? 64 : (threads > LSAP_WG ? LSAP_WG : threads);
+  hipLaunchKernelGGL(lsap_kernel, dim3(1), dim3(threads), lds, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+size_t neat_dbscan_ws_bytes(int n) { return (size_t)n * 2 * sizeof(int); }
+
+int neat_dbscan_means(const float* points, int n, double eps, float* centres, unsigned char* valid, int* count, void* ws, void* stream) {
+  if (n <= 0 || n > DBSCAN_MAXN || !points || !centres || !valid || !count || !ws || !(eps > 0.0)) return -1;
+  int* parent = (int*)ws; int* has_nb = parent + n;
+  hipLaunchKernelGGL(dbscan_init_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, parent, has_nb, n);
+  hipLaunchKernelGGL(dbscan_union_kernel, dim3(n), dim3(128), 0, (hipStream_t)stream, points, n, eps * eps, parent, has_nb);
+  // mode 2 (18 n bytes of dynamic LDS fit next to the 32 KB of labels): O(n) fixed-point sums; else one wavefront per cluster over all
+  // points, read from LDS (mode 1: 12 n bytes fit) or from global memory (mode 0)
+  const size_t acc_bytes = (size_t)(n / 2) * 28 + (size_t)n * 4, pbytes = (size_t)n * 12;
+  const int mode = acc_bytes <= 96 * 1024 ? 2 : (pbytes <= 96 * 1024 ? 1 : 0);
+  if (mode) NEAT_CHECK(lds_limit<&dbscan_finish_kernel>(96 * 1024));
+  hipLaunchKernelGGL(dbscan_finish_kernel, dim3(1), dim3(1024), mode == 2 ? acc_bytes : (mode == 1 ? pbytes : 0), (hipStream_t)stream, points, n,
+                     parent, has_nb, centres, valid, count, mode);
+  return (int)hipGetLastError();
+}
+
+int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream) {
+  if (R <= 0 || S <= 0) return 0;
+  hipLaunchKernelGGL(volume_weights_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, z, sdf, R, S, beta, weights);
+  return (int)hipGetLastError();
+}
+
+// ---- ABI v15: wireframe parsing (kernels_parse.hpp) -----------------------------------------------------------------------------
+static inline size_t parse_al(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline int parse_tiles(int n) { return (2 * n + PARSE_TILE - 1) / PARSE_TILE; }
+
+int neat_parse_match(const float* lines2d, int n, const float* gt, int m, int gt_stride, float threshold, int* label, float* mindis,
+                     void* stream) {
+  if (n < 0 || m < 0 || (m > 0 && (!gt || gt_stride < 4))) return -1;
+  if (n == 0) return 0;
+  if (!lines2d || !label || !mindis) return -1;
+  hipLaunchKernelGGL(parse_match_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, (hipStream_t)stream, lines2d, n, gt, m, gt_stride, threshold,
+                     label, mindis);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_group_ws_bytes(int n, int m) {
+  if (n < 0 || m < 0) return 0;
+  const size_t nt = (size_t)parse_tiles(n);
+  return parse_al((nt * m + 3 * (size_t)m) * sizeof(int)) + parse_al(2 * (size_t)n * sizeof(int));
+}
+
+int neat_parse_group(const int* label, const float* lines3d, const float* l3d, int n, int m, float* lines, float* scores, int* count,
+                     void* ws, void* stream) {
+  if (n < 0 || m < 0 || !count) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0 || m == 0) return (int)hipMemsetAsync(count, 0, sizeof(int), st);
+  if (!label || !lines3d || !l3d || !lines || !scores || !ws) return -1;
+  const int nt = parse_tiles(n);
+  int* run = (int*)ws;
+  int* cnt = run + (size_t)nt * m;
+  int* start = cnt + m;
+  int* slot = start + m;
+  int* order = (int*)((char*)ws + parse_al(((size_t)nt * m + 3 * (size_t)m) * sizeof(int)));
+  NEAT_CHECK(hipMemsetAsync(run, 0, (size_t)nt * m * sizeof(int), st));
+  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 0);
+  hipLaunchKernelGGL(parse_group_scan_kernel, dim3(1), dim3(1024), 0, st, run, nt, m, cnt, start, slot, count);
+  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 1);
+  hipLaunchKernelGGL(parse_group_reduce_kernel, dim3(m), dim3(PARSE_WG), 0, st, order, cnt, start, slot, lines3d, l3d, n, lines, scores);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_vote_ws_bytes(int J, int mcap) {
+  if (J <= 0 || mcap <= 0) return 0;
+  const size_t nc = 2 * (size_t)mcap, k = std::min((size_t)J, nc);
+  return parse_al((size_t)J * nc * sizeof(float)) + parse_al(nc) + 2 * parse_al(k * sizeof(long long)) + parse_al(sizeof(int)) +
+         parse_al(neat_lsap_ws_bytes(J, (int)nc));
+}
+
+int neat_parse_vote(const float* junctions, int J, const float* lines, const int* count, int mcap, float threshold, int view, int* votes,
+                    int* first, void* ws, void* stream) {
+  if (J < 0 || mcap < 0 || view < 0) return -1;
+  if (J == 0 || mcap == 0) return 0;
+  if (!junctions || !lines || !count || !votes || !first || !ws) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int nc = 2 * mcap, k = std::min(J, nc);
+  char* p = (char*)ws;
+  float* cost = (float*)p; p += parse_al((size_t)J * nc * sizeof(float));
+  unsigned char* cmask = (unsigned char*)p; p += parse_al(nc);
+  long long* rows = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
+  long long* cols = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
+  int* n_match = (int*)p; p += parse_al(sizeof(int));
+  const size_t total = (size_t)J * nc;
+  hipLaunchKernelGGL(parse_vote_cost_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, junctions, J, lines, count, nc, cost, cmask);
+  NEAT_CHECK(hipGetLastError());
+  const int e = neat_lsap(cost, J, nc, nullptr, cmask, rows, cols, n_match, p, stream);
+  if (e != 0) return e;
+  hipLaunchKernelGGL(parse_vote_apply_kernel, grid1(k), dim3(256), 0, st, rows, cols, n_match, k, cost, nc, threshold, view, votes, first);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_graph_ws_bytes(int V, int mcap, int J) {
+  if (V < 0 || mcap < 0 || J < 0) return 0;
+  return parse_al((size_t)V * mcap * sizeof(int)) + parse_al((size_t)J * sizeof(int));
+}
+
+int neat_parse_graph(const float* vlines, const float* vscores, const int* vcount, int V, int mcap, float score_threshold,
+                     const float* junctions, const int* votes, const int* first, int J, float* lines_out, float* junc_out,
+                     unsigned char* graph, int* pairs, float* wfi, int ecap, int* counts, void* ws, void* stream) {
+  if (V < 0 || mcap < 0 || J < 0 || ecap < 0 || !counts) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if ((V > 0 && mcap > 0 && (!vlines || !vscores || !vcount || !lines_out || !ws)) ||
+      (J > 0 && (!junctions || !votes || !first || !junc_out || !graph || !ws)) || (ecap > 0 && (!pairs || !wfi))) return -1;
+  NEAT_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(int), st));
+  const int ncap = V * mcap;
+  if (ncap == 0 && J == 0) return 0;
+  int* idx = (int*)ws;
+  int* rowcnt = (int*)((char*)ws + parse_al((size_t)V * mcap * sizeof(int)));
+  hipLaunchKernelGGL(parse_select_kernel, dim3(2), dim3(1024), 0, st, vlines, vscores, vcount, V, mcap, score_threshold, junctions, votes, first,
+                     J, lines_out, junc_out, idx, counts);
+  if (J == 0 || ncap == 0) return (int)hipGetLastError();
+  NEAT_CHECK(hipMemsetAsync(graph, 0, (size_t)J * J, st));
+  hipLaunchKernelGGL(parse_graph_mark_kernel, grid1(ncap, PARSE_WG), dim3(PARSE_WG), 0, st, lines_out, junc_out, counts, ncap, J, graph);
+  hipLaunchKernelGGL(parse_edge_count_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt);
+  hipLaunchKernelGGL(parse_edge_write_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt, J, junc_out, ecap, pairs, wfi);
+  return (int)hipGetLastError();
+}
+
+size_t neat_parse_visibility_ws_bytes(int ecap, int V) {
+  if (ecap < 0 || V < 0) return 0;
+  return parse_al((size_t)V * ecap) + parse_al((size_t)ecap * sizeof(int));
+}
+
+int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, const float* gt, int gt_stride, const int* gt_off,
+                          const float* K3, const float* w2c, int V, float ckdist, int ckview, int* vis_count, float* checked,
+                          int* n_checked, void* ws, void* stream) {
+  if (ecap < 0 || V < 0 || !n_checked) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (ecap == 0) return (int)hipMemsetAsync(n_checked, 0, sizeof(int), st);
+  if (!lines || !vis_count || !checked || !ws || (V > 0 && (!gt_off || !K3 || !w2c || gt_stride < 4))) return -1;
+  unsigned char* vis = (unsigned char*)ws;
+  int* idx = (int*)((char*)ws + parse_al((size_t)V * ecap));
+  if (V > 0)
+    hipLaunchKernelGGL(parse_vis_kernel, dim3((ecap + PARSE_WG - 1) / PARSE_WG, V), dim3(PARSE_WG), 0, st, lines, n_lines, ecap, gt, gt_stride,
+                       gt_off, K3, w2c, ckdist, vis);
+  hipLaunchKernelGGL(parse_vis_count_kernel, dim3(1), dim3(1024), 0, st, lines, n_lines, ecap, V, vis, ckview, vis_count, idx, checked, n_checked);
+  return (int)hipGetLastError();
+}
+
+
+}  // extern "C"

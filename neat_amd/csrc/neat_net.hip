@@ -1,11 +1,12 @@
-// Host orchestration + C ABI of libneat_hip.so (see include/neat_hip.h).
+// Host orchestration + C ABI of the networks of libneat_hip.so (see include/neat_hip.h): pack layout, workspaces, the SDF / heads /
+// render launch chains.  The entry points without a 16-bit storage type (samplers, losses, junctions, parsing ...) are neat_aux.hip.
 // One stream-ordered sequence of kernel launches per entry point; no allocation, no sync.
 // Two builds of the GEMM-class kernels share the orchestration: precision 0 = exact-f32 MFMA with fp32
 // feature-major activations (parity build), precision 1 = bf16 MFMA (fp32 accumulate) with bf16 octet-major
 // hidden activations (throughput build).  Small arrays are fp32 feature-major in both.
 // NEAT_F16 (precision 3) is this same file compiled a second time with -DNEAT_HALF=1 (build.sh): namespace neat becomes neat_f16, every
-// C entry point gets the prefix f16_ (f16_symbols.h, generated from include/neat_hip.h), bf16_common.hpp switches the 16-bit format
-// to IEEE half.  The primary build's entry points forward precision 3 to that twin as ITS precision 1 (NEAT_F16_FWD below).
+// C entry point named in twin_list.h gets the prefix f16_ (f16_symbols.h, generated from that list), bf16_common.hpp switches the
+// 16-bit format to IEEE half.  The primary build's entry points forward precision 3 to that twin as ITS precision 1 (NEAT_F16_FWD below).
 #include <mutex>
 #include <unordered_map>
 #if defined(NEAT_HALF) && NEAT_HALF
@@ -15,9 +16,6 @@
 #include "kernels_bf16.hpp"
 #include "kernels_dw.hpp"
 #include "fused_launch.hpp"
-#include "kernels_sampler.hpp"
-#include "kernels_junction.hpp"
-#include "kernels_parse.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <initializer_list>
@@ -41,17 +39,22 @@ constexpr int PE_ROWS = 39, SMALL_R = 33, SMALL_A = 9;
 enum { F32 = 0, BF16 = 1, BF16X3 = 2, HX3 = 4, HX3_FASTVALUES = 5 };
 // HX3 (NEAT_F16X3, served by the f16 twin only) = the 16-bit build (layouts, backward pass) whose three FORWARD chains run with
 // 3-product hi/lo arithmetic (kernels_x3.hpp) and save lo planes where a later forward kernel needs them: every entry point maps it
-// to BF16 + Ctx::hx3 (take_hx3)
+// to BF16 + Ctx::hx3 (resolve)
 // HX3_FASTVALUES (5): values-mode calls only (neat_sdf_forward mode 0, neat_sdf_values_gated) on a NEAT_F16X3 pack: the ONE-product
 // f16 chain of the fp16 build evaluates the query (3x faster; for a sampler that may trade the reference's exact depths for speed)
-inline int take_hx3(int& precision) {
-  if (NEAT_HALF && precision == HX3) { precision = BF16; return 1; }
-  if (NEAT_HALF && precision == HX3_FASTVALUES) { precision = BF16; return 2; }
-  return 0;
-}
 // BF16X3 = the F32 build (layouts, kernels, workspaces) with split-bf16 products in its two GEMM kernels: every entry point maps it
-// to F32 + Ctx::x3 (take_x3)
-inline int take_x3(int& precision) { if (precision == BF16X3) { precision = F32; return 1; } return 0; }
+// to F32 + Ctx::x3 (resolve)
+// A precision code of the C ABI resolved to the build that serves it: prec = F32 / BF16 (layouts, kernels, workspaces), x3 / hx3 = the
+// split-product mode that rides on it, ok = a code this build knows.  Every entry point starts here.
+struct Prec { int prec, x3, hx3; bool ok; };
+inline Prec resolve(int precision) {
+  Prec r{precision, 0, 0, false};
+  if (precision == BF16X3) { r.prec = F32; r.x3 = 1; }
+  if (NEAT_HALF && precision == HX3) { r.prec = BF16; r.hx3 = 1; }
+  if (NEAT_HALF && precision == HX3_FASTVALUES) { r.prec = BF16; r.hx3 = 2; }
+  r.ok = r.prec == F32 || r.prec == BF16;
+  return r;
+}
 
 inline int padk(int k, int prec) { return prec ? (k + 63) & ~63 : (k + 7) & ~7; }   // bf16: k-steps of 16, unrolled by 4
 inline int pad8(int k) { return (k + 7) & ~7; }
@@ -166,13 +169,7 @@ inline void prof_end(hipStream_t st, ProfSlot* s) { if (s) hipEventRecord(s->e1,
 // launch helpers
 // ------------------------------------------------------------------------------------------------
 template <int EPI> hipError_t launch_layer_f(hipStream_t st, const LayerArgs& a, int ntiles_p) {
-  static DevOnce attr_set;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&layer_kernel<EPI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  NEAT_TRY(lds_limit<&layer_kernel<EPI>>(96 * 1024));
   size_t lds = (size_t)a.Kpad * BM * sizeof(float);
   if (a.NT <= 2 && lds < 32768) lds = 32768;
   hipLaunchKernelGGL(layer_kernel<EPI>, dim3(ntiles_p), dim3(WG), lds, st, a);
@@ -182,13 +179,7 @@ int g_wgrad_h3 = 1;         // bf16 weight gradient of the all-bf16 256x256 laye
 int g_pt_bf16 = 2;          // 32-point column tiles per workgroup in the bf16 layer kernel: 2 (64 pts, higher occupancy) or 4
 
 template <int EPI, int PT, bool OBF> hipError_t launch_layer_h_pt(hipStream_t st, const LayerArgsH& a) {
-  static DevOnce attr_set;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&layer_kernel_h<EPI, PT, OBF>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  NEAT_TRY((lds_limit<&layer_kernel_h<EPI, PT, OBF>>(96 * 1024)));
   constexpr int BMT = 32 * PT;
   size_t lds = (size_t)(a.Kpad / 8) * BMT * 16;
   const size_t red = (size_t)4 * PT * 16 * 64 * 4;
@@ -251,7 +242,6 @@ inline int dw_grid(int ldp) {
 int g_ws_aux_nt = 15;       // non-temporal accesses (tuning key 11): bit 0 / 1 = fetch of aux0 / aux1 of the streaming layer kernels, bit 2 =
                             // weight-gradient operands, bit 3 = `in` of the layer kernels, bit 4 = store of out1 (m_l)
 int g_ws_wide_store = 1;    // streaming layer kernels: 16-byte output stores (tuning key 12)
-int g_sampler_ablate = 0;
 const int* g_gate = nullptr; int g_gate_value = 0;      // set around one neat_sdf_forward call by neat_sdf_values_gated
 int g_fused_interleave = 0; // fused primal chain: batches interleaved over the workgroups (tuning key 10)
 int g_ws_interleave = 1;    // 1: tiles interleaved over the workgroups instead of one contiguous range each
@@ -270,18 +260,10 @@ int g_chain_pp = 1;         // with key 16: the chain variables of the tangent /
                             // instead of one array per layer: since the weight gradients are contracted in the launch that holds them no later
                             // kernel reads them, and a line rewritten while it is still in the Infinity Cache never costs an HBM write (tuning key 24)
 int g_dw_nsub = 16;         // sub-ranges of workgroup partials summed by dw_gather_kernel (= fp32 splits per layer seen by the finish; tuning key 18)
-int g_ffn_mfma = 1;         // the 256 x 256 layers of the global-junction MLP (forward and data backward) on the fp32 matrix pipe (ffn_mfma_kernel) instead
-                            // of the vector-ALU kernel (tuning key 28)
 int g_dw_segments = 1;      // with key 16: consecutive layers of a chain that share an epilogue variant run as ONE launch with a per-workgroup layer loop
                             // (tangent 1-2 | 3 | 4-7, reverse 8 | 7-5 | 4 | 3-1: 15 launches -> 7; tuning key 25)
 template <int EPI, bool FULL> hipError_t launch_layer_wsdw(hipStream_t st, const LayerArgsDW* d0, int n = 1) {
-  static DevOnce attr_set;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&layer_kernel_wsdw<EPI, FULL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, WsCfg<EPI, 16>::LDS + DW_XLDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  NEAT_TRY((lds_limit<&layer_kernel_wsdw<EPI, FULL>>(WsCfg<EPI, 16>::LDS + DW_XLDS)));
   if (n < 1 || n > DW_MAXSEG || (n > 1 && !(FULL && EPI != EPI_BWD8))) return hipErrorInvalidValue;      // (only the FULL variants carry the layer loop)
   LayerArgsDWSeg seg{};
   seg.n = n;
@@ -299,13 +281,7 @@ template <int EPI, bool FULL> hipError_t launch_layer_wsdw(hipStream_t st, const
 }
 template <int EPI, bool FULL> hipError_t launch_layer_wsdw(hipStream_t st, const LayerArgsDW& d0) { return launch_layer_wsdw<EPI, FULL>(st, &d0, 1); }
 template <int EPI, int KS = 16, bool OUTF = false> hipError_t launch_layer_ws(hipStream_t st, const LayerArgsWS& a0) {
-  static DevOnce attr_set;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&layer_kernel_ws<EPI, KS, OUTF>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, WsCfg<EPI, KS>::LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  NEAT_TRY((lds_limit<&layer_kernel_ws<EPI, KS, OUTF>>(WsCfg<EPI, KS>::LDS)));
   LayerArgsWS a = a0;
   a.ntiles = a.ldp / WSP;
   a.per_wg = (a.ntiles + g_ws_grid - 1) / g_ws_grid;
@@ -666,16 +642,9 @@ hipError_t sdf_primal(const Ctx& c, const SdfWs& w, bool full, float radius = 0.
     ProfSlot* ps = prof_begin(c.st, 2, fl, fbytes);
     if (g_fused_ws) {
       // weight-stationary persistent kernel: batches of 128 points (64 when that balances the CUs better)
-      static DevOnce attr_done;      // raise the dynamic-LDS limit of all variants once (not a stream operation: keep it out of graph capture)
-      if (!attr_done) {
-        hipError_t e0 = hipSuccess;
-        auto raise = [&](auto kern, int bytes) { if (e0 == hipSuccess) e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-        raise(&sdf_fused_ws_kernel<4, false>, FwsCfg<4>::LDS); raise(&sdf_fused_ws_kernel<4, true>, FwsCfg<4>::LDS);
-        raise(&sdf_fused_ws_kernel<3, false>, FwsCfg<3>::LDS); raise(&sdf_fused_ws_kernel<3, true>, FwsCfg<3>::LDS);
-        raise(&sdf_fused_ws_kernel<2, false>, FwsCfg<2>::LDS); raise(&sdf_fused_ws_kernel<2, true>, FwsCfg<2>::LDS);
-        if (e0 != hipSuccess) return e0;
-        attr_done = true;
-      }
+      NEAT_TRY((lds_limit<&sdf_fused_ws_kernel<4, false>, &sdf_fused_ws_kernel<4, true>>(FwsCfg<4>::LDS)));
+      NEAT_TRY((lds_limit<&sdf_fused_ws_kernel<3, false>, &sdf_fused_ws_kernel<3, true>>(FwsCfg<3>::LDS)));
+      NEAT_TRY((lds_limit<&sdf_fused_ws_kernel<2, false>, &sdf_fused_ws_kernel<2, true>>(FwsCfg<2>::LDS)));
       const int ntiles = c.ldp / 32;                 // ldp is a multiple of 64
       const int nwg = ntiles < g_ws_grid ? ntiles : g_ws_grid;
       if (g_fused_ws >= 2) {
@@ -781,10 +750,20 @@ void oct_pack(const Ctx& c, std::initializer_list<PackJob> jobs) {
 }
 inline bool oct_operands(const Ctx& c) { return c.prec && g_wgrad_h3; }
 
+// the layer's part of a reduction's arguments: shape, the permutation of its forward pack, the weight-norm operands, where the gradients
+// go; the bias gradient sits in packed column K of the partials
+void wreduce_layer(const Ctx& c, int layer_id, const neat_net_grads* gr, int K, WreduceArgs& r) {
+  const PackDesc2& d = c.L().d[c.L().fwd[layer_id]];
+  r.O = kO[layer_id]; r.I = kI[layer_id];
+  r.s0 = d.s0; r.s0p = d.s0p; r.off0 = d.off0; r.off1 = d.off1; r.rot = d.rot; r.scale = d.scale;
+  r.v = c.net->v[layer_id]; r.g = c.net->g[layer_id];
+  r.dv = gr->dv[layer_id]; r.dg = gr->dg[layer_id]; r.db = gr->db[layer_id];
+  r.bias_col = K;
+}
+
 // second half of a weight gradient: deterministic reduction of the split partials described by `r` (partial, splits, strides),
 // un-permutation of the packed columns and the weight-norm backward into dv / dg / db of `layer_id`
 hipError_t wgrad_reduce(const Ctx& c, const SdfWs& w, int layer_id, WreduceArgs r, int Nred, int N, int K, const neat_net_grads* gr) {
-  const PackDesc2& d = c.L().d[c.L().fwd[layer_id]];
   const int splits = r.splits;
   const float* partial = r.partial;
   const bool direct = c.prec && g_wreduce_direct == 1;    // bf16 build: one 16-wave pass over all split partials
@@ -799,11 +778,7 @@ hipError_t wgrad_reduce(const Ctx& c, const SdfWs& w, int layer_id, WreduceArgs 
     r.partial = stage; r.splits = (splits + per - 1) / per;
     r.row_stride = (size_t)WGROUPS * Kld; r.split_stride = Kld;
   }
-  r.O = kO[layer_id]; r.I = kI[layer_id];
-  r.s0 = d.s0; r.s0p = d.s0p; r.off0 = d.off0; r.off1 = d.off1; r.rot = d.rot; r.scale = d.scale;
-  r.v = c.net->v[layer_id]; r.g = c.net->g[layer_id];
-  r.dv = gr->dv[layer_id]; r.dg = gr->dg[layer_id]; r.db = gr->db[layer_id];
-  r.bias_col = K;
+  wreduce_layer(c, layer_id, gr, K, r);
   dbg_sync(c.st, "wgrad layer/N/K", layer_id, N, K);
   if (direct4) hipLaunchKernelGGL(wreduce_direct_kernel, dim3(r.O), dim3(WG), 0, c.st, r);
   else if (direct && splits > 2 * WGROUPS) hipLaunchKernelGGL(wreduce_wnorm_kernel<16>, dim3(r.O), dim3(1024), 0, c.st, r);
@@ -827,12 +802,7 @@ hipError_t wgrad_multi(const Ctx& c, const SdfWs& w, const WProb* pb, int nprob,
   const int splits = (c.P + chunk - 1) / chunk;
   const size_t region = (size_t)N * splits * Kld2;
   if ((size_t)nprob * region > WPARTIAL_FLOATS - WSTAGE_FLOATS) return hipErrorInvalidValue;
-  static DevOnce attr3;
-  if (!attr3) {
-    hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel_h3<4>), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES);
-    if (e0 != hipSuccess) return e0;
-    attr3 = true;
-  }
+  NEAT_TRY(lds_limit<&wgrad_kernel_h3<4>>(W3_LDS_BYTES));
   WgradArgsH3 a{};
   double flops = 0.0, bytes = 0.0;
   for (int p = 0; p < nprob; ++p)
@@ -870,8 +840,6 @@ hipError_t wgrad_multi(const Ctx& c, const SdfWs& w, const WProb* pb, int nprob,
                        (const float*)w.partial, splits, Kld2 / 4, WGROUPS, per, nprob * N, stage);
   WreduceBatch b{};
   for (int q = 0; q < nprob; ++q) {
-    const int layer_id = pb[q].layer_id;
-    const PackDesc2& d = c.L().d[c.L().fwd[layer_id]];
     WreduceArgs& r = b.a[q];
     if (direct4) {
       r.partial = w.partial + (size_t)q * region; r.splits = splits; r.row_stride = (size_t)splits * Kld2; r.split_stride = Kld2;
@@ -879,11 +847,7 @@ hipError_t wgrad_multi(const Ctx& c, const SdfWs& w, const WProb* pb, int nprob,
       r.partial = stage + (size_t)q * N * WGROUPS * Kld2; r.splits = groups_used;
       r.row_stride = (size_t)WGROUPS * Kld2; r.split_stride = Kld2;
     }
-    r.O = kO[layer_id]; r.I = kI[layer_id];
-    r.s0 = d.s0; r.s0p = d.s0p; r.off0 = d.off0; r.off1 = d.off1; r.rot = d.rot; r.scale = d.scale;
-    r.v = c.net->v[layer_id]; r.g = c.net->g[layer_id];
-    r.dv = gr->dv[layer_id]; r.dg = gr->dg[layer_id]; r.db = gr->db[layer_id];
-    r.bias_col = K;
+    wreduce_layer(c, pb[q].layer_id, gr, K, r);
   }
   if (direct4) hipLaunchKernelGGL(wreduce_direct_batch_kernel, dim3(256, nprob), dim3(WG), 0, c.st, b);
   else hipLaunchKernelGGL(wreduce_wnorm_batch_kernel, dim3(256, nprob), dim3(WG), 0, c.st, b);
@@ -929,12 +893,7 @@ hipError_t wgrad(const Ctx& c, const SdfWs& w, int layer_id, const WPair* pairs_
     prof_end(c.st, ps);
     r.row_stride = (size_t)splits * WLDK; r.split_stride = WLDK;
   } else {
-    static DevOnce attr_set;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel_h2), hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS_BYTES);
-      if (e != hipSuccess) return e;
-      attr_set = true;
-    }
+    NEAT_TRY(lds_limit<&wgrad_kernel_h2>(W2_LDS_BYTES));
     const int Kld2 = (K + 1 + 7) / 8 * 8;      // partial row length: K columns + bias, not the 320 of the widest layer (the reduction reads all of it)
     if (Kld2 > W2LDK) return hipErrorInvalidValue;
     // all-bf16 octet-major operands: the streaming tr16 kernel.  Shapes: K <= 256 in one launch (B may continue in a
@@ -954,12 +913,7 @@ hipError_t wgrad(const Ctx& c, const SdfWs& w, int layer_id, const WPair* pairs_
     if (two && (r0 != 256 || r1 == 0 || r1 > 256)) h3 = false;
     const bool narrow = h3 && g_wgrad_narrow && K <= 64 && r1 == 0;      // lin0: one 32-column block per wave (tuning key 21)
     if (h3) {
-      static DevOnce attr3_set;
-      if (!attr3_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel_h3<4>), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr3_set = true;
-      }
+      NEAT_TRY(lds_limit<&wgrad_kernel_h3<4>>(W3_LDS_BYTES));
       // (narrow: 80 KB of LDS per workgroup -> two co-resident workgroups per CU when there are twice as many splits)
       const int nsplit_target = narrow ? W2SPLIT * g_wgrad_narrow : W2SPLIT;
       int chunk = ((c.ldp + nsplit_target - 1) / nsplit_target + W3P - 1) / W3P * W3P;
@@ -967,22 +921,8 @@ hipError_t wgrad(const Ctx& c, const SdfWs& w, int layer_id, const WPair* pairs_
       splits = (c.P + chunk - 1) / chunk;
       chunk_used = chunk;
       ProfSlot* ps = prof_begin(c.st, 1, wflops, wbytes + (double)splits * N * (K + 1) * 4.0);
-      if (wide) {
-        static DevOnce attr5_set;
-        if (!attr5_set) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel_h3<5>), hipFuncAttributeMaxDynamicSharedMemorySize, W3Cfg<5>::LDS);
-          if (e != hipSuccess) return e;
-          attr5_set = true;
-        }
-      }
-      if (narrow) {
-        static DevOnce attr1_set;
-        if (!attr1_set) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel_h3<1>), hipFuncAttributeMaxDynamicSharedMemorySize, W3Cfg<1>::LDS);
-          if (e != hipSuccess) return e;
-          attr1_set = true;
-        }
-      }
+      if (wide) NEAT_TRY(lds_limit<&wgrad_kernel_h3<5>>(W3Cfg<5>::LDS));
+      if (narrow) NEAT_TRY(lds_limit<&wgrad_kernel_h3<1>>(W3Cfg<1>::LDS));
       for (int part = 0; part < (two ? 2 : 1); ++part) {
         WgradArgsH3 a{};
         for (int q = 0; q < npairs; ++q) {
@@ -1040,6 +980,27 @@ hipError_t wgrad(const Ctx& c, const SdfWs& w, int layer_id, const WPair* pairs_
   return wgrad_reduce(c, w, layer_id, r, Nred, N, K, gr);
 }
 
+// in-kernel weight gradients (kernels_dw.hpp): where job j keeps its workgroup partials.  j = 2 (l - 1) + pair for the tangent (0) /
+// reverse (1) launch of layer l = 1..7, DW_JOB8 for lin8's reverse launch
+constexpr int DW_JOB8 = DW_JOBS - 1;
+struct DwJob { uint4* partial; float* pscale; float* pbias; };
+inline DwJob dw_job_at(const SdfWs& w, int ldp, int j) {
+  const size_t o = (size_t)j * dw_slots(ldp);
+  return DwJob{reinterpret_cast<uint4*>(w.dwp) + o * DW_WG_UINT4, w.dwscale + o * 8, w.dwbias + o * 256};
+}
+// ... and where dw_gather_kernel leaves their fp32 splits in w.partial for the finish: one region per layer 1..7 (256 rows), lin8's (257
+// rows: the sdf row last), then the block partials of that row (rowdot_kernel: xn blocks of xchunk points)
+struct DwSplits {
+  static constexpr int K = 256, Kld2 = (K + 1 + 7) / 8 * 8;
+  int splits, xchunk, xn;
+  size_t region, region8;
+  DwSplits(int P, int ldp) : splits(g_dw_nsub), xchunk(((ldp + DW8_XBLOCKS - 1) / DW8_XBLOCKS + 31) / 32 * 32), xn((P + xchunk - 1) / xchunk),
+                             region((size_t)256 * splits * Kld2), region8((size_t)257 * splits * Kld2) {}
+  size_t row_stride() const { return (size_t)splits * Kld2; }
+  float* out(const SdfWs& w, int l) const { return w.partial + (size_t)(l - 1) * region; }
+  float* xrow(const SdfWs& w) const { return out(w, 8) + region8; }
+};
+
 // double backward + backward: w.gh (cotangent of normals, masked) and w.abar8 (cotangent of lin8 output) are set
 // nc: the cotangent of the normals still has to be formed (its arguments); null = w.gh is set
 struct NormalCot { const float* sc_r; const float* sc_a; const float* extra_rm; int P_main; const float* d_tail_rm; const float* slot; const float* slot_a;
@@ -1079,13 +1040,12 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   for (int l = 1; l <= 7; ++l) dw = dw && gr->dv[l] != nullptr && L.d[L.fwd[l]].Kpad == 256 && L.d[L.tr[l]].Kpad == 256;
   const int dwg = dw_grid(c.ldp);
   const bool dw8 = dw && g_dw_lin8 && gr->dv[8] != nullptr && L.d[L.tr[8]].Kpad >= 256 && w.featc.bf16;
-  auto dw_job = [&](int l, int pair, LayerArgsDW& d) {
-    const size_t j = (size_t)(2 * (l - 1) + pair);
-    d.partial = reinterpret_cast<uint4*>(w.dwp) + j * dw_slots(c.ldp) * DW_WG_UINT4;
-    d.pscale = w.dwscale + j * dw_slots(c.ldp) * 8;
-    d.pbias = pair ? w.dwbias + j * dw_slots(c.ldp) * 256 : nullptr;
+  auto dw_job = [&](int j, bool bias, LayerArgsDW& d) {
+    const DwJob jb = dw_job_at(w, c.ldp, j);
+    d.partial = jb.partial; d.pscale = jb.pscale; d.pbias = bias ? jb.pbias : nullptr;
     d.P = c.P;
   };
+  const DwSplits ds(c.P, c.ldp);
   auto u16p = [](const Arr& a) { return reinterpret_cast<u16*>(a.p); };
   // chain variables of the in-kernel-gradient launches: vhat_1 (lin0's launch) and vhat_8 (rowdot_kernel reads it) keep their arrays, vhat_2..7
   // alternate between vh[2] / vh[3]; the reverse chain's a^_7..1 alternate between vh[4] / vh[5] (free in this mode), a^_0 lands in m[0] (lin0's gradient)
@@ -1100,14 +1060,23 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   LayerArgsDW pend[DW_MAXSEG];
   int npend = 0, pend_variant = 0;
   double pend_flops = 0.0, pend_bytes = 0.0;
-  auto flush_tan = [&]() -> hipError_t {
+  // consecutive layers of a chain with the same epilogue variant go out as ONE launch (layer loop per workgroup, kernels_dw.hpp)
+  auto flush = [&](bool rev) -> hipError_t {
     if (!npend) return hipSuccess;
     ProfSlot* ps = prof_begin(c.st, 0, pend_flops, pend_bytes);
-    const hipError_t r = pend_variant == 1 ? launch_layer_wsdw<EPI_TAN_PF, false>(c.st, pend, npend) : launch_layer_wsdw<EPI_TAN, true>(c.st, pend, npend);
+    hipError_t r;
+    if (rev) r = pend_variant == 0 ? launch_layer_wsdw<EPI_BWD, true>(c.st, pend, npend) : launch_layer_wsdw<EPI_BWD, false>(c.st, pend, npend);
+    else r = pend_variant == 1 ? launch_layer_wsdw<EPI_TAN_PF, false>(c.st, pend, npend) : launch_layer_wsdw<EPI_TAN, true>(c.st, pend, npend);
     prof_end(c.st, ps);
-    dbg_sync(c.st, "tangent+dW layers", npend, 0, 0);
+    dbg_sync(c.st, rev ? "reverse+dW layers" : "tangent+dW layers", npend, 0, 0);
     npend = 0; pend_flops = pend_bytes = 0.0;
     return r;
+  };
+  auto queue = [&](bool rev, const LayerArgsDW& d, int variant, int N, bool last) -> hipError_t {
+    if (npend && (variant != pend_variant || npend == DW_MAXSEG || !g_dw_segments)) NEAT_TRY(flush(rev));
+    pend[npend++] = d; pend_variant = variant; pend_flops += 2.0 * N * 256 * (double)c.P + 2.0 * d.rowsA * 256 * (double)c.P;
+    pend_bytes += 256 * (double)c.P * 2.0 + N * (double)c.P * 2.0 * 4 + (double)dwg * DW_WG_UINT4 * 16.0;
+    return (last || !g_dw_segments) ? flush(rev) : hipSuccess;
   };
   for (int l = 0; l < 8; ++l) {
     In a = l == 0 ? in(c.prec ? w.Ehbf : F(w.Eh), PE_ROWS) : in(w.vh[l], l == 4 ? (c.prec ? 224 : 217) : 256);
@@ -1124,13 +1093,8 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
       if (l == 4) { s.in2 = u16p(w.Ehbf4); s.split_oct = 28; }
       if (l == 3) s.padfill = u16p(w.Ehbf);
       d.auxA2 = nullptr; d.auxA_split = 1 << 30; d.rowsA = kO[l];
-      dw_job(l, 0, d);
-      // consecutive layers with the same epilogue variant go out as ONE launch (layer loop per workgroup, kernels_dw.hpp): 1-2 | 3 | 4-7
-      const int variant = l == 3 ? 1 : 0;
-      if (npend && (variant != pend_variant || npend == DW_MAXSEG || !g_dw_segments)) { if ((e = flush_tan()) != hipSuccess) return e; }
-      pend[npend++] = d; pend_variant = variant; pend_flops += 2.0 * kO[l] * 256 * (double)c.P + 2.0 * kO[l] * 256 * (double)c.P;
-      pend_bytes += 256 * (double)c.P * 2.0 + kO[l] * (double)c.P * 2.0 * 4 + (double)dwg * DW_WG_UINT4 * 16.0;
-      if (l == 7 || !g_dw_segments) { if ((e = flush_tan()) != hipSuccess) return e; }
+      dw_job(2 * (l - 1), false, d);
+      if ((e = queue(false, d, l == 3 ? 1 : 0, kO[l], l == 7)) != hipSuccess) return e;      // 1-2 | 3 (pad-fill variant) | 4-7
       continue;
     }
     if ((e = layer(c, L.fwd[l], EPI_TAN, a, b, nullptr, kO[l], w.vh[l + 1], w.m[l], 1 << 30, w.h[l + 1], w.u[l], 0, 0, 1 << 30,
@@ -1140,16 +1104,9 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   if (!c.prec) e = layer(c, L.tr[8], EPI_BWD, in(F(w.abar8), 257), NOIN, nullptr, 256, w.m[7], Arr{}, 1 << 30, w.h[8], w.m[7]);
   else if (dw8) {
     // the sdf row of dW8 first: its operands h8 and vh8 are what the last tangent launch just read / wrote (Infinity Cache)
-    {
-      const int K = 256, Kld2 = (K + 1 + 7) / 8 * 8, splits = g_dw_nsub;
-      const size_t region = (size_t)256 * splits * Kld2, region8 = (size_t)257 * splits * Kld2;
-      float* xrow = w.partial + (size_t)7 * region + region8;
-      const int xchunk = ((c.ldp + DW8_XBLOCKS - 1) / DW8_XBLOCKS + 31) / 32 * 32;
-      const int xn = (c.P + xchunk - 1) / xchunk;
-      if ((size_t)7 * region + region8 + (size_t)DW8_XBLOCKS * Kld2 > WPARTIAL_FLOATS) return hipErrorInvalidValue;
-      hipLaunchKernelGGL(rowdot_kernel, dim3(xn), dim3(256), 0, c.st, w.abar8, reinterpret_cast<const u16*>(w.h[8].p),
-                         reinterpret_cast<const u16*>(w.vh[8].p), c.P, c.ldp, xchunk, xrow, (size_t)Kld2);
-    }
+    if ((size_t)7 * ds.region + ds.region8 + (size_t)DW8_XBLOCKS * ds.Kld2 > WPARTIAL_FLOATS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rowdot_kernel, dim3(ds.xn), dim3(256), 0, c.st, w.abar8, reinterpret_cast<const u16*>(w.h[8].p),
+                       reinterpret_cast<const u16*>(w.vh[8].p), c.P, c.ldp, ds.xchunk, ds.xrow(w), (size_t)ds.Kld2);
     // lin8's reverse launch contracts featc (x) h8 (the 256 feature rows of dW8) and the row sums of featc on chip as well
     LayerArgsDW d{};
     LayerArgsWS& s = d.w;
@@ -1160,11 +1117,7 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
     s.N = 256; s.ldp = c.ldp; s.kstride = pd.Kpad / 16; s.n_split = 1 << 30;
     s.in_octs = 32; s.split_oct = 32;
     d.auxA2 = nullptr; d.auxA_split = 1 << 30; d.rowsA = 256;
-    const size_t j = 14;
-    d.partial = reinterpret_cast<uint4*>(w.dwp) + j * dw_slots(c.ldp) * DW_WG_UINT4;
-    d.pscale = w.dwscale + j * dw_slots(c.ldp) * 8;
-    d.pbias = w.dwbias + j * dw_slots(c.ldp) * 256;
-    d.P = c.P;
+    dw_job(DW_JOB8, true, d);
     ProfSlot* ps = dw_prof(256, 256);
     e = launch_layer_wsdw<EPI_BWD8, true>(c.st, d);
     prof_end(c.st, ps);
@@ -1208,15 +1161,6 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   };
   const bool inter = g_wgrad_interleave != 0 && !dw;
   if (inter && (e = wgrad_layer(8)) != hipSuccess) return e;
-  auto flush_rev = [&]() -> hipError_t {
-    if (!npend) return hipSuccess;
-    ProfSlot* ps = prof_begin(c.st, 0, pend_flops, pend_bytes);
-    const hipError_t r = pend_variant == 0 ? launch_layer_wsdw<EPI_BWD, true>(c.st, pend, npend) : launch_layer_wsdw<EPI_BWD, false>(c.st, pend, npend);
-    prof_end(c.st, ps);
-    dbg_sync(c.st, "reverse+dW layers", npend, 0, 0);
-    npend = 0; pend_flops = pend_bytes = 0.0;
-    return r;
-  };
   for (int l = 7; l >= 1; --l) {
     if (inter && (e = wgrad_layer(l)) != hipSuccess) return e;
     const int N = l == 4 ? 217 : kI[l];
@@ -1233,13 +1177,9 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
       // rows of the gradient = rows of a^_l.  lin3's 217: the rows up to 223 of m[3] are zeros and the octets past them are re-reads of
       // octet 27 (finite), so rows >= 217 of the product are finite garbage that the gather never writes -- no row mask needed
       d.rowsA = 256;
-      dw_job(l, 1, d);
+      dw_job(2 * (l - 1) + 1, true, d);
       // 7-5 | 4 (217 output rows: the row-tested variant) | 3-1 as one launch each
-      const int variant = (N == 256 && d.rowsA == 256) ? 0 : 1;
-      if (npend && (variant != pend_variant || npend == DW_MAXSEG || !g_dw_segments)) { if ((e = flush_rev()) != hipSuccess) return e; }
-      pend[npend++] = d; pend_variant = variant; pend_flops += 2.0 * N * 256 * (double)c.P + 2.0 * d.rowsA * 256 * (double)c.P;
-      pend_bytes += 256 * (double)c.P * 2.0 + N * (double)c.P * 2.0 * 4 + (double)dwg * DW_WG_UINT4 * 16.0;
-      if (l == 1 || !g_dw_segments) { if ((e = flush_rev()) != hipSuccess) return e; }
+      if ((e = queue(true, d, (N == 256 && d.rowsA == 256) ? 0 : 1, N, l == 1)) != hipSuccess) return e;
       continue;
     }
     if ((e = layer(c, L.tr[l], EPI_BWD, in(w.m[l], kO[l]), NOIN, nullptr, N, w.m[l - 1], Arr{}, 1 << 30, w.h[l], w.m[l - 1])) != hipSuccess) return e;
@@ -1249,64 +1189,28 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   if (dw) {
     // one gather launch: 7 layers (tangent + reverse partial sets each) x g_dw_nsub sub-ranges of workgroups -> g_dw_nsub fp32 splits per layer in the partial-tile format;
     // then the weight-norm finish of the seven layers in one launch
-    const int K = 256, Kld2 = (K + 1 + 7) / 8 * 8, splits = g_dw_nsub;
-    const size_t region = (size_t)256 * splits * Kld2;
+    // lin8 (dw8): packed rows 0..255 = the feature rows (one partial set, reverse launch only), packed row 256 = the sdf row: cotangent abar8
+    // row 0 against h8, plus the plain row sums of vh8 (second-order part, the adjoint seed being 1), from rowdot_kernel's block partials
+    const int K = ds.K, njobs = dw8 ? 8 : 7;
     DwGatherArgs ga{};
     WreduceBatch wb{};
-    for (int l = 1; l <= 7; ++l) {
-      float* out = w.partial + (size_t)(l - 1) * region;
-      const size_t j0 = (size_t)(2 * (l - 1)), j1 = j0 + 1;          // tangent / reverse partial sets of the layer
+    for (int l = 1; l <= njobs; ++l) {
+      const DwJob tan = dw_job_at(w, c.ldp, 2 * (l - 1)), rev = dw_job_at(w, c.ldp, l == 8 ? DW_JOB8 : 2 * (l - 1) + 1);
       DwGatherJob& jb = ga.job[l - 1];
-      jb.partial = reinterpret_cast<const uint4*>(w.dwp) + j0 * dw_slots(c.ldp) * DW_WG_UINT4;
-      jb.pscale = w.dwscale + j0 * dw_slots(c.ldp) * 8;
-      jb.partial2 = reinterpret_cast<const uint4*>(w.dwp) + j1 * dw_slots(c.ldp) * DW_WG_UINT4;
-      jb.pscale2 = w.dwscale + j1 * dw_slots(c.ldp) * 8;
-      jb.pbias = w.dwbias + j1 * dw_slots(c.ldp) * 256;
+      if (l < 8) { jb.partial = tan.partial; jb.pscale = tan.pscale; jb.partial2 = rev.partial; jb.pscale2 = rev.pscale; }
+      else { jb.partial = rev.partial; jb.pscale = rev.pscale; jb.partial2 = nullptr; jb.pscale2 = nullptr; }
+      jb.pbias = rev.pbias;
       jb.nwg = dwg; jb.transposed = 0;
-      jb.out = out; jb.row_stride = (size_t)splits * Kld2; jb.split_stride = Kld2; jb.split0 = 0;
-      jb.bias_col = K; jb.rows = kO[l]; jb.cols = K;
-      const PackDesc2& pd = L.d[L.fwd[l]];
+      jb.out = ds.out(w, l); jb.row_stride = ds.row_stride(); jb.split_stride = ds.Kld2; jb.split0 = 0;
+      jb.bias_col = K; jb.rows = l == 8 ? 256 : kO[l]; jb.cols = K;
+      if (l == 8) { jb.xrow = ds.xrow(w); jb.xrow_n = ds.xn; jb.xrow_stride = ds.Kld2; }
       WreduceArgs& r = wb.a[l - 1];
-      r.partial = out; r.splits = splits; r.row_stride = (size_t)splits * Kld2; r.split_stride = Kld2;
-      r.O = kO[l]; r.I = kI[l];
-      r.s0 = pd.s0; r.s0p = pd.s0p; r.off0 = pd.off0; r.off1 = pd.off1; r.rot = pd.rot; r.scale = pd.scale;
-      r.v = c.net->v[l]; r.g = c.net->g[l];
-      r.dv = gr->dv[l]; r.dg = gr->dg[l]; r.db = gr->db[l];
-      r.bias_col = K;
+      r.partial = jb.out; r.splits = ds.splits; r.row_stride = ds.row_stride(); r.split_stride = ds.Kld2;
+      wreduce_layer(c, l, gr, K, r);
       done[l] = true;
     }
-    int njobs = 7;
-    if (dw8) {
-      // lin8: packed rows 0..255 = the feature rows (one partial set, reverse launch only), packed row 256 = the sdf row: cotangent abar8
-      // row 0 against h8, plus the plain row sums of vh8 (second-order part, the adjoint seed being 1), from rowdot_kernel's block partials
-      float* out = w.partial + (size_t)7 * region;
-      const size_t region8 = (size_t)257 * splits * Kld2;
-      float* xrow = out + region8;
-      const int xchunk = ((c.ldp + DW8_XBLOCKS - 1) / DW8_XBLOCKS + 31) / 32 * 32;
-      const int xn = (c.P + xchunk - 1) / xchunk;
-      const size_t j = 14;
-      DwGatherJob& jb = ga.job[7];
-      jb.partial = reinterpret_cast<const uint4*>(w.dwp) + j * dw_slots(c.ldp) * DW_WG_UINT4;
-      jb.pscale = w.dwscale + j * dw_slots(c.ldp) * 8;
-      jb.partial2 = nullptr; jb.pscale2 = nullptr;
-      jb.pbias = w.dwbias + j * dw_slots(c.ldp) * 256;
-      jb.nwg = dwg; jb.transposed = 0;
-      jb.out = out; jb.row_stride = (size_t)splits * Kld2; jb.split_stride = Kld2; jb.split0 = 0;
-      jb.bias_col = K; jb.rows = 256; jb.cols = K;
-      jb.xrow = xrow; jb.xrow_n = xn; jb.xrow_stride = Kld2;
-      const PackDesc2& pd = L.d[L.fwd[8]];
-      WreduceArgs& r = wb.a[7];
-      r.partial = out; r.splits = splits; r.row_stride = (size_t)splits * Kld2; r.split_stride = Kld2;
-      r.O = kO[8]; r.I = kI[8];
-      r.s0 = pd.s0; r.s0p = pd.s0p; r.off0 = pd.off0; r.off1 = pd.off1; r.rot = pd.rot; r.scale = pd.scale;
-      r.v = c.net->v[8]; r.g = c.net->g[8];
-      r.dv = gr->dv[8]; r.dg = gr->dg[8]; r.db = gr->db[8];
-      r.bias_col = K;
-      done[8] = true;
-      njobs = 8;
-    }
     // (accounted with the weight-gradient class: no flops, the partials read once + the fp32 splits written and read once)
-    ProfSlot* psg = prof_begin(c.st, 1, 0.0, (14.0 + (dw8 ? 1.0 : 0.0)) * dwg * DW_WG_UINT4 * 16.0 + 2.0 * njobs * (double)region * 4.0);
+    ProfSlot* psg = prof_begin(c.st, 1, 0.0, (14.0 + (dw8 ? 1.0 : 0.0)) * dwg * DW_WG_UINT4 * 16.0 + 2.0 * njobs * (double)ds.region * 4.0);
     hipLaunchKernelGGL(dw_gather_kernel, dim3(DW_WG_UINT4 / 256, g_dw_nsub, njobs), dim3(256), 0, c.st, ga);
     dbg_sync(c.st, "dw gather", 0, 0, 0);
     hipLaunchKernelGGL(wreduce_wnorm_batch_kernel, dim3(dw8 ? 257 : 256, njobs), dim3(WG), 0, c.st, wb);
@@ -1549,27 +1453,6 @@ hipError_t heads_backward(const Ctx& c, const HeadWs& h, const SdfWs& w, const n
   return hipSuccess;
 }
 
-__global__ void volume_weights_kernel(const float* __restrict__ z, const float* __restrict__ sdf, int R, int S,
-                                      const float* __restrict__ beta_ptr, float* __restrict__ weights) {
-  const float beta = *beta_ptr;
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  float carry = 0.0f;
-  for (int i0 = 0; i0 < S; i0 += 64) {
-    const int i = i0 + lane;
-    const bool ok = i < S;
-    const int p = r * S + (ok ? i : S - 1);
-    const float delta = (i + 1 < S) ? z[p + 1] - z[p] : 1e10f;
-    const float e = ok ? delta * laplace_sigma(sdf[p], beta) : 0.0f;
-    const float incl = wave_incl_scan(e, lane);
-    float excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0.0f;
-    if (ok) weights[p] = (1.0f - expf(-e)) * expf(-(carry + excl));
-    carry += __shfl(incl, 63);
-  }
-}
-
 __global__ void lines_from_offsets_kernel(const float* __restrict__ lin_fm, const float* __restrict__ x_fm, int P, int ldp,
                                           float* __restrict__ lines) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1723,7 +1606,11 @@ void export_out8(const Ctx& c, const SdfWs& w, float* out257, float* feat) {
   }
 }
 
-bool bad_prec(int p) { return p != F32 && p != BF16 && p != BF16X3 && !(NEAT_HALF && (p == HX3 || p == HX3_FASTVALUES)); }
+Ctx make_ctx(const Prec& pr, const float* packed, const neat_net_params* net, int P, void* stream) {
+  Ctx c{(hipStream_t)stream, packed, net, P, round_ldp(P, pr.prec), pr.prec};
+  c.x3 = pr.x3; c.hx3 = pr.hx3;
+  return c;
+}
 
 }  // namespace
 
@@ -1732,11 +1619,9 @@ bool bad_prec(int p) { return p != F32 && p != BF16 && p != BF16X3 && !(NEAT_HAL
 // ================================================================================================
 #if !NEAT_HALF
 #define NEAT_TWIN(fn) extern "C" decltype(fn) f16_##fn;
-NEAT_TWIN(neat_set_tuning) NEAT_TWIN(neat_prof_enable) NEAT_TWIN(neat_prof_collect)
-NEAT_TWIN(neat_packed_floats) NEAT_TWIN(neat_pack_weights) NEAT_TWIN(neat_sdf_ws_floats) NEAT_TWIN(neat_sdf_forward)
-NEAT_TWIN(neat_sdf_backward) NEAT_TWIN(neat_sdf_backward_x) NEAT_TWIN(neat_heads_ws_floats) NEAT_TWIN(neat_heads_forward) NEAT_TWIN(neat_render_ws_floats)
-NEAT_TWIN(neat_render_forward) NEAT_TWIN(neat_render_backward) NEAT_TWIN(neat_render_eval_ws_floats)
-NEAT_TWIN(neat_render_forward_eval) NEAT_TWIN(neat_sdf_values_gated) NEAT_TWIN(neat_sdf_values_rays) NEAT_TWIN(neat_sdf_values_laid_out)
+#include "twin_list.h"
+#undef NEAT_TWIN
+__attribute__((visibility("hidden"))) int neat_aux_set_tuning(int key, int value);      // keys 28 and 30 live in neat_aux.hip
 #define NEAT_F16_FWD(call) if (precision == 3) { precision = BF16; return f16_##call; } if (precision == HX3 || precision == HX3_FASTVALUES) return f16_##call;
 #else
 #define NEAT_F16_FWD(call)
@@ -1744,10 +1629,13 @@ NEAT_TWIN(neat_render_forward_eval) NEAT_TWIN(neat_sdf_values_gated) NEAT_TWIN(n
 
 extern "C" {
 
+#if !NEAT_HALF
 int neat_abi_version(void) { return 15; }
+#endif
 
 int neat_set_tuning(int key, int value) {          /* 0: bf16 layer-kernel point tile (2 -> 64 points, 4 -> 128 points) */
 #if !NEAT_HALF
+  if (key == 28 || key == 30) return neat_aux_set_tuning(key, value);
   f16_neat_set_tuning(key, value);                 /* the f16 twin keeps its own copies of the switches */
 #endif
   if (key == 0 && (value == 2 || value == 4)) { g_pt_bf16 = value; return 0; }
@@ -1776,8 +1664,6 @@ int neat_set_tuning(int key, int value) {          /* 0: bf16 layer-kernel point
   if (key == 23 && (value == 0 || (value >= 16 && value <= DW_MAXGRID))) { g_dw_grid = value; return 0; }
   if (key == 24 && (value == 0 || value == 1)) { g_chain_pp = value; return 0; }
   if (key == 25 && (value == 0 || value == 1)) { g_dw_segments = value; return 0; }
-  if (key == 28 && (value == 0 || value == 1)) { g_ffn_mfma = value; return 0; }
-  if (key == 30 && value >= 0 && value <= 7) { g_sampler_ablate = value; return 0; }      /* probes: sampler_round_kernel without its bisection (1) / refine (2) / final (4) part */
   return -1;
 }
 
@@ -1820,18 +1706,17 @@ int neat_prof_collect(int cls, double* total_ms, double* total_flops, int* launc
 
 size_t neat_packed_floats(int precision) {
   NEAT_F16_FWD(neat_packed_floats(precision))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision);
-  return (bad_prec(precision) || hx3 == 2) ? 0 : pack_layout(precision, hx3 != 0).total; }
+  const Prec pr = resolve(precision);
+  return (!pr.ok || pr.hx3 == 2) ? 0 : pack_layout(pr.prec, pr.hx3 != 0).total;
+}
 
 int neat_pack_weights(const neat_net_params* net, float* packed, int precision, void* stream) {
   NEAT_F16_FWD(neat_pack_weights(net, packed, precision, stream))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return -1;
-  if (!net || !packed || bad_prec(precision)) return -1;
+  const Prec pr = resolve(precision);
+  if (pr.hx3 == 2) return -1;
+  if (!net || !packed || !pr.ok) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const PackLayout& L = pack_layout(precision, hx3 != 0);
+  const PackLayout& L = pack_layout(pr.prec, pr.hx3 != 0);
   RowScaleArgs ra;
   ra.net = to_ptrs(net);
   ra.rowscale = packed + L.rowscale_off;
@@ -1852,27 +1737,10 @@ int neat_pack_weights(const neat_net_params* net, float* packed, int precision, 
   return (int)hipGetLastError();
 }
 
-int neat_camera_rays(const float* uv, const float* pose, const float* K, int kstride, int R, float* dirs, float* origins, void* stream) {
-  if (R <= 0) return 0;
-  hipLaunchKernelGGL(camera_rays_kernel, grid1(R), dim3(256), 0, (hipStream_t)stream, uv, pose, K, kstride, R, dirs, origins);
-  return (int)hipGetLastError();
-}
-
-int neat_eik_points(const float* uniform, const float* origins, const float* dirs, const float* z_eik, const float* extra, int R, int J,
-                    float* out, const float* z, int S, const long long* idx, void* stream) {
-  if (R <= 0 || J < 0) return R == 0 && J == 0 ? 0 : -1;
-  if (!uniform || !origins || !dirs || !out || (J > 0 && !extra)) return -1;
-  if (!z_eik && (!z || !idx || S <= 0)) return -1;           // the depth per ray: given, or picked from the ray's S depths by idx
-  hipLaunchKernelGGL(eik_points_kernel, grid1((2 * R + J) * 3), dim3(256), 0, (hipStream_t)stream, uniform, origins, dirs, z_eik, extra, R, J, out,
-                     z, S, idx);
-  return (int)hipGetLastError();
-}
-
 size_t neat_sdf_ws_floats(int P, int mode, int precision) {
   NEAT_F16_FWD(neat_sdf_ws_floats(P, mode, precision))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  return bad_prec(precision) ? 0 : sdf_ws(nullptr, round_ldp(P, precision), mode, precision, hx3 == 1).total;
+  const Prec pr = resolve(precision);
+  return !pr.ok ? 0 : sdf_ws(nullptr, round_ldp(P, pr.prec), mode, pr.prec, pr.hx3 == 1).total;
 }
 
 // x [P,3] row-major, or (x == null) the points o + z d of R rays x S depths (P = R S)
@@ -1880,19 +1748,17 @@ struct RayPoints { const float* origins; const float* dirs; const float* z; int 
 static int sdf_forward_impl(const float* packed, const neat_net_params* net, const float* x, const RayPoints* rp, int P, int mode, int precision,
                             float radius, float scale, float* ws, float* out257, float* sdf, float* feat, float* grad, void* stream,
                             bool laid_out = false) {
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2 && mode != 0) return -1;      // NEAT_F16X3 fast values: values-mode calls only
+  const Prec pr = resolve(precision);
+  if (pr.hx3 == 2 && mode != 0) return -1;      // NEAT_F16X3 fast values: values-mode calls only
   if (P <= 0) return 0;
-  if (!packed || !net || (!x && !rp && !laid_out) || !ws || bad_prec(precision)) return -1;
-  Ctx c{(hipStream_t)stream, packed, net, P, round_ldp(P, precision), precision};
-  c.x3 = x3; c.hx3 = hx3;
-  SdfWs w = sdf_ws(ws, c.ldp, mode, precision, hx3);
+  if (!packed || !net || (!x && !rp && !laid_out) || !ws || !pr.ok) return -1;
+  Ctx c = make_ctx(pr, packed, net, P, stream);
+  SdfWs w = sdf_ws(ws, c.ldp, mode, pr.prec, pr.hx3);
   if (laid_out) {}      // the caller (sampler_init_kernel / sampler_round_kernel) wrote w.x = the first 3 rows of the workspace
   else if (x) hipLaunchKernelGGL(rm_to_fm_kernel, grid1(c.ldp), dim3(256), 0, c.st, x, P, 3, c.ldp, w.x);
   else hipLaunchKernelGGL(points_from_rays_kernel, grid1(c.ldp), dim3(256), 0, c.st, rp->origins, rp->dirs, rp->z, rp->R, rp->S, c.ldp, w.x,
                           (float*)nullptr, (const float*)nullptr, 0);
-  if (mode == 0 && precision) {
+  if (mode == 0 && pr.prec) {
     NEAT_CHECK(sdf_primal(c, w, false, radius, scale, sdf));      // fused: PE -> 9 layers -> clamp, one launch
     return (int)hipGetLastError();
   }
@@ -1924,7 +1790,7 @@ int neat_sdf_values_rays(const float* packed, const neat_net_params* net, const 
                          void* stream) {
   NEAT_F16_FWD(neat_sdf_values_rays(packed, net, origins, dirs, z, R, S, precision, radius, scale, ws, sdf, gate, gate_value, stream))
   if (R <= 0 || S <= 0) return 0;
-  if (!packed || !net || !origins || !dirs || !z || !ws || !sdf || bad_prec(precision)) return -1;
+  if (!packed || !net || !origins || !dirs || !z || !ws || !sdf || !resolve(precision).ok) return -1;
   const RayPoints rp{origins, dirs, z, R, S};
   g_gate = gate; g_gate_value = gate_value;
   const int rc = sdf_forward_impl(packed, net, nullptr, &rp, R * S, 0, precision, radius, scale, ws, nullptr, sdf, nullptr, nullptr, stream);
@@ -1934,17 +1800,15 @@ int neat_sdf_values_rays(const float* packed, const neat_net_params* net, const 
 
 // the point stride that neat_sdf_ws_floats sized the workspace with and the forward reads: the precision code is mapped the way every
 // entry point maps it (bf16x3 runs the F32 layouts at the 64-point stride; NEAT_F16 / NEAT_F16X3 share the 16-bit granule)
-int neat_sdf_ldp(int P, int precision) {
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  return P <= 0 ? 0 : round_ldp(P, precision);
-}
+#if !NEAT_HALF
+int neat_sdf_ldp(int P, int precision) { return P <= 0 ? 0 : round_ldp(P, resolve(precision).prec); }
+#endif
 
 int neat_sdf_values_laid_out(const float* packed, const neat_net_params* net, int P, int precision, float radius, float scale, float* ws,
                              float* sdf, const int* gate, int gate_value, void* stream) {
   NEAT_F16_FWD(neat_sdf_values_laid_out(packed, net, P, precision, radius, scale, ws, sdf, gate, gate_value, stream))
   if (P <= 0) return 0;
-  if (!packed || !net || !ws || !sdf || bad_prec(precision)) return -1;
+  if (!packed || !net || !ws || !sdf || !resolve(precision).ok) return -1;
   g_gate = gate; g_gate_value = gate_value;
   const int rc = sdf_forward_impl(packed, net, nullptr, nullptr, P, 0, precision, radius, scale, ws, nullptr, sdf, nullptr, nullptr, stream, true);
   g_gate = nullptr;
@@ -1955,7 +1819,7 @@ int neat_sdf_values_gated(const float* packed, const neat_net_params* net, const
                           float scale, float* ws, float* sdf, const int* gate, int gate_value, void* stream) {
   NEAT_F16_FWD(neat_sdf_values_gated(packed, net, x, P, precision, radius, scale, ws, sdf, gate, gate_value, stream))
   if (P <= 0) return 0;
-  if (!packed || !net || !x || !ws || !sdf || bad_prec(precision)) return -1;
+  if (!packed || !net || !x || !ws || !sdf || !resolve(precision).ok) return -1;
   g_gate = gate; g_gate_value = gate_value;
   const int rc = neat_sdf_forward(packed, net, x, P, 0, precision, radius, scale, ws, nullptr, sdf, nullptr, nullptr, stream);
   g_gate = nullptr;
@@ -1965,17 +1829,15 @@ int neat_sdf_values_gated(const float* packed, const neat_net_params* net, const
 static int sdf_backward_impl(const float* packed, const neat_net_params* net, float* ws, int P, int precision, float scale,
                              const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
                              const neat_net_grads* grads, float* d_x, void* stream) {
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return -1;
+  const Prec pr = resolve(precision);
+  if (pr.hx3 == 2) return -1;
   if (P <= 0) return 0;
-  if (!packed || !net || !ws || !grads || bad_prec(precision)) return -1;
-  Ctx c{(hipStream_t)stream, packed, net, P, round_ldp(P, precision), precision};
-  c.x3 = x3; c.hx3 = hx3;
-  SdfWs w = sdf_ws(ws, c.ldp, 1, precision, hx3);
+  if (!packed || !net || !ws || !grads || !pr.ok) return -1;
+  Ctx c = make_ctx(pr, packed, net, P, stream);
+  SdfWs w = sdf_ws(ws, c.ldp, 1, pr.prec, pr.hx3);
   const float* slot = cot_scale_begin(c, w.ones, {{d_out257, 257LL * P}, {d_sdf, (long long)P}, {d_feat, 256LL * P}, {d_grad, 3LL * P}});
   hipLaunchKernelGGL(build_abar8_kernel, dim3((c.ldp + 255) / 256, 257), dim3(256), 0, c.st, d_out257, d_sdf, d_feat, w.mask, P, c.ldp, w.abar8, slot);
-  if (precision) oct_pack(c, {{w.abar8 + c.ldp, 256, w.featc}});
+  if (pr.prec) oct_pack(c, {{w.abar8 + c.ldp, 256, w.featc}});
   const NormalCot nc{nullptr, nullptr, d_grad, P, nullptr, slot, nullptr};
   NEAT_CHECK(sdf_backward_chains(c, w, grads, &nc, d_x != nullptr));
   grad_unscale(c, grads, 0, 9, slot);
@@ -2002,34 +1864,30 @@ int neat_sdf_backward_x(const float* packed, const neat_net_params* net, float* 
 
 size_t neat_heads_ws_floats(int P, int precision) {
   NEAT_F16_FWD(neat_heads_ws_floats(P, precision))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return 0;
-  if (bad_prec(precision)) return 0;
-  const int ldp = round_ldp(P, precision);
-  return head_ws(nullptr, ldp, precision).total + (size_t)(3 + 3 + 256) * ldp;
+  const Prec pr = resolve(precision);
+  if (!pr.ok || pr.hx3 == 2) return 0;
+  const int ldp = round_ldp(P, pr.prec);
+  return head_ws(nullptr, ldp, pr.prec).total + (size_t)(3 + 3 + 256) * ldp;
 }
 
 int neat_heads_forward(const float* packed, const neat_net_params* net, const float* points, const float* normals,
                        const float* view_dirs, const float* feats, int P, int precision, float* ws, float* rgb, float* lines,
                        void* stream) {
   NEAT_F16_FWD(neat_heads_forward(packed, net, points, normals, view_dirs, feats, P, precision, ws, rgb, lines, stream))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return -1;
+  const Prec pr = resolve(precision);
+  if (pr.hx3 == 2) return -1;
   if (P <= 0) return 0;
-  if (!packed || !net || !ws || bad_prec(precision)) return -1;
-  Ctx c{(hipStream_t)stream, packed, net, P, round_ldp(P, precision), precision};
-  c.x3 = x3; c.hx3 = hx3;
-  HeadWs h = head_ws(ws, c.ldp, precision);
+  if (!packed || !net || !ws || !pr.ok) return -1;
+  Ctx c = make_ctx(pr, packed, net, P, stream);
+  HeadWs h = head_ws(ws, c.ldp, pr.prec);
   float* x_fm = ws + h.total; float* g_fm = x_fm + 3 * (size_t)c.ldp; float* f_fm = g_fm + 3 * (size_t)c.ldp;
   hipLaunchKernelGGL(rm_to_fm_kernel, grid1(c.ldp), dim3(256), 0, c.st, points, P, 3, c.ldp, x_fm);
   hipLaunchKernelGGL(rm_to_fm_kernel, grid1(c.ldp), dim3(256), 0, c.st, normals, P, 3, c.ldp, g_fm);
   Arr feat;
-  feat.p = f_fm; feat.bf16 = precision;
+  feat.p = f_fm; feat.bf16 = pr.prec;
   Arr featlo;      // HX3: the lo plane of the feature rows in the second half of the same 256 float rows
-  featlo.p = hx3 ? reinterpret_cast<u16*>(f_fm) + (size_t)256 * c.ldp : nullptr; featlo.bf16 = 1;
-  if (precision) hipLaunchKernelGGL(rm_to_oct_kernel, grid1(c.ldp), dim3(256), 0, c.st, feats, P, 256, c.ldp, reinterpret_cast<u16*>(f_fm),
+  featlo.p = pr.hx3 ? reinterpret_cast<u16*>(f_fm) + (size_t)256 * c.ldp : nullptr; featlo.bf16 = 1;
+  if (pr.prec) hipLaunchKernelGGL(rm_to_oct_kernel, grid1(c.ldp), dim3(256), 0, c.st, feats, P, 256, c.ldp, reinterpret_cast<u16*>(f_fm),
                                     reinterpret_cast<u16*>(featlo.p));
   else hipLaunchKernelGGL(rm_to_fm_kernel, grid1(c.ldp), dim3(256), 0, c.st, feats, P, 256, c.ldp, f_fm);
   hipLaunchKernelGGL(head_inputs_kernel, grid1(c.ldp), dim3(256), 0, c.st, x_fm, g_fm, view_dirs, P, 1, c.ldp, h.small_r, h.small_a,
@@ -2042,29 +1900,25 @@ int neat_heads_forward(const float* packed, const neat_net_params* net, const fl
 
 size_t neat_render_ws_floats(int R, int S, int E, int precision) {
   NEAT_F16_FWD(neat_render_ws_floats(R, S, E, precision))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return 0;
-  if (bad_prec(precision)) return 0;
-  const int ldp = round_ldp(R * S + E, precision);
-  return sdf_ws(nullptr, ldp, 1, precision, hx3).total + head_ws(nullptr, ldp, precision).total;
+  const Prec pr = resolve(precision);
+  if (!pr.ok || pr.hx3 == 2) return 0;
+  const int ldp = round_ldp(R * S + E, pr.prec);
+  return sdf_ws(nullptr, ldp, 1, pr.prec, pr.hx3).total + head_ws(nullptr, ldp, pr.prec).total;
 }
 
 static int render_forward_impl(const float* packed, const neat_net_params* net, const float* origins, const float* dirs,
                                const float* z, int R, int S, int precision, const float* beta, float beta_min, float radius, float scale, float* ws,
                                float* points, float* weights, float* sdf, float* rgb, float* lines3d, float* depth,
                                float* xyz, float* normal_map, const float* eik_points, int E, float* eik_grad, void* stream, bool fwd_only) {
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return -1;
+  const Prec pr = resolve(precision);
+  if (pr.hx3 == 2) return -1;
   if (R <= 0 || S <= 0) return 0;
-  if (!packed || !net || !ws || !origins || !dirs || !z || !rgb || !lines3d || !depth || !xyz || bad_prec(precision)) return -1;
+  if (!packed || !net || !ws || !origins || !dirs || !z || !rgb || !lines3d || !depth || !xyz || !pr.ok) return -1;
   if (E < 0 || (E > 0 && (!eik_points || !eik_grad))) return -1;
   const int Pm = R * S, P = Pm + E;
-  Ctx c{(hipStream_t)stream, packed, net, P, round_ldp(P, precision), precision};
-  c.x3 = x3; c.hx3 = hx3;
-  SdfWs w = sdf_ws(ws, c.ldp, fwd_only ? 2 : 1, precision, hx3);
-  HeadWs h = head_ws(ws + w.total, c.ldp, precision, fwd_only);
+  Ctx c = make_ctx(pr, packed, net, P, stream);
+  SdfWs w = sdf_ws(ws, c.ldp, fwd_only ? 2 : 1, pr.prec, pr.hx3);
+  HeadWs h = head_ws(ws + w.total, c.ldp, pr.prec, fwd_only);
   hipLaunchKernelGGL(points_from_rays_kernel, grid1(c.ldp), dim3(256), 0, c.st, origins, dirs, z, R, S, c.ldp, w.x, points, eik_points, E);
   NEAT_CHECK(sdf_primal(c, w, true));
   NEAT_CHECK(sdf_adjoint(c, w, !fwd_only));
@@ -2094,12 +1948,10 @@ int neat_render_forward(const float* packed, const neat_net_params* net, const f
 
 size_t neat_render_eval_ws_floats(int R, int S, int precision) {
   NEAT_F16_FWD(neat_render_eval_ws_floats(R, S, precision))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return 0;
-  if (bad_prec(precision)) return 0;
-  const int ldp = round_ldp(R * S, precision);
-  return sdf_ws(nullptr, ldp, 2, precision, hx3).total + head_ws(nullptr, ldp, precision, true).total;
+  const Prec pr = resolve(precision);
+  if (!pr.ok || pr.hx3 == 2) return 0;
+  const int ldp = round_ldp(R * S, pr.prec);
+  return sdf_ws(nullptr, ldp, 2, pr.prec, pr.hx3).total + head_ws(nullptr, ldp, pr.prec, true).total;
 }
 
 int neat_render_forward_eval(const float* packed, const neat_net_params* net, const float* origins, const float* dirs,
@@ -2116,16 +1968,14 @@ int neat_render_backward(const float* packed, const neat_net_params* net, float*
                          const float* d_depth, const float* d_xyz, const float* d_eik_grad, const float* d_acc,
                          const neat_net_grads* grads, float* dbeta_ray, float* dbeta, void* stream) {
   NEAT_F16_FWD(neat_render_backward(packed, net, ws, dirs, z, R, S, E, precision, beta, beta_min, d_rgb, d_lines3d, d_depth, d_xyz, d_eik_grad, d_acc, grads, dbeta_ray, dbeta, stream))
-  const int x3 = take_x3(precision); (void)x3;
-  const int hx3 = take_hx3(precision); (void)hx3;
-  if (hx3 == 2) return -1;
+  const Prec pr = resolve(precision);
+  if (pr.hx3 == 2) return -1;
   if (R <= 0 || S <= 0) return 0;
-  if (!packed || !net || !ws || !grads || bad_prec(precision) || E < 0 || (dbeta && (!dbeta_ray || !beta))) return -1;
+  if (!packed || !net || !ws || !grads || !pr.ok || E < 0 || (dbeta && (!dbeta_ray || !beta))) return -1;
   const int Pm = R * S, P = Pm + E;
-  Ctx c{(hipStream_t)stream, packed, net, P, round_ldp(P, precision), precision};
-  c.x3 = x3; c.hx3 = hx3;
-  SdfWs w = sdf_ws(ws, c.ldp, 1, precision, hx3);
-  HeadWs h = head_ws(ws + w.total, c.ldp, precision);
+  Ctx c = make_ctx(pr, packed, net, P, stream);
+  SdfWs w = sdf_ws(ws, c.ldp, 1, pr.prec, pr.hx3);
+  HeadWs h = head_ws(ws + w.total, c.ldp, pr.prec);
   CompositeBwdArgs cb;
   cb.z = z; cb.sdf = w.sdf; cb.dirs = dirs; cb.mask = w.mask; cb.x_fm = w.x; cb.rgb_fm = h.rgb;
   cb.R = R; cb.S = S; cb.ldp = c.ldp; cb.beta_ptr = beta; cb.beta_min = beta_min;
@@ -2151,570 +2001,6 @@ int neat_render_backward(const float* packed, const neat_net_params* net, float*
   NEAT_CHECK(sdf_backward_chains(c, w, grads, &nc));
   if (slot_a) { grad_unscale(c, grads, 0, L_ATTR, slot); grad_unscale(c, grads, L_ATTR, NLAYERS - L_ATTR, slot_a); }
   else grad_unscale(c, grads, 0, NLAYERS, slot);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_bound(const float* z, int n, int R, const float* sdf_old, const float* sdf_new, const int* order, int n_old,
-                       const float* beta_in, const float* beta0, float eps, int iters, float* sdf_out, float* beta_out,
-                       int* flag, void* stream) {
-  if (R <= 0) return 0;
-  if (n < 2 || n > SMAX || !z || !sdf_new || !beta_in || !beta0 || !sdf_out || !beta_out || !flag) return -1;
-  SamplerBoundArgs a{z, n, R, sdf_old, sdf_new, order, n_old, beta_in, beta0, eps, iters, sdf_out, beta_out, flag, nullptr, 0};
-  hipLaunchKernelGGL(sampler_bound_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_resample(const float* z, const float* sdf, int n, int R, const float* beta, int refine, float add_tiny,
-                          const float* u, int u_stride, int N, float* samples, float* z_merged, int* order, void* stream) {
-  if (R <= 0) return 0;
-  if (n < 2 || n > SMAX || N < 1 || N > SMAX || !z || !sdf || !beta || !u || !samples || (refine && (!z_merged || !order))) return -1;
-  SamplerResampleArgs a{};
-  a.z = z; a.sdf = sdf; a.n = n; a.R = R; a.beta = beta; a.refine = refine; a.add_tiny = add_tiny; a.u = u; a.u_stride = u_stride; a.N = N;
-  a.samples = samples; a.z_merged = z_merged; a.order = order;
-  hipLaunchKernelGGL(sampler_resample_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_finish(const float* samples, int N, const float* z, int n, const int* pick, int n_extra, float near, float far,
-                        int R, const int* eik_idx, float* z_vals, float* z_eik, void* stream) {
-  if (R <= 0) return 0;
-  if (N + 2 + n_extra > SMAX || !samples || !z || (n_extra > 0 && !pick) || !eik_idx || !z_vals || !z_eik) return -1;
-  SamplerFinishArgs a{samples, N, z, n, pick, n_extra, near, far, R, eik_idx, z_vals, z_eik, n};
-  hipLaunchKernelGGL(sampler_finish_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sample_pdf(const float* bins, const float* weights, int nb, int R, const float* u, int u_stride, int N, float* samples,
-                    const float* z_merge, int nz, float* z_out, void* stream) {
-  if (R <= 0) return 0;
-  if (nb < 2 || nb > SMAX || N < 1 || N > SMAX || !bins || !weights || !u || !samples || (z_merge && (!z_out || nz < 0 || nz + N > SMAX))) return -1;
-  SamplePdfArgs a{bins, weights, nb, R, u, u_stride, N, samples, z_merge, nz, z_out};
-  hipLaunchKernelGGL(sample_pdf_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_uniform_depths(const float* near_r, float near_s, const float* far_r, float far_s, const float* t, const float* rnd, int R, int N,
-                        float* z, void* stream) {
-  if (R <= 0 || N <= 0) return 0;
-  if (!t || !z) return -1;
-  hipLaunchKernelGGL(uniform_depths_kernel, dim3((R * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, near_r, near_s, far_r, far_s, t, rnd, R, N, z);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_init(const float* z, int R, int n, const float* beta, float beta_min, float beta_c, float* beta0, float* beta_ray,
-                      int* ctl, int nctl, void* stream) {
-  return neat_sampler_init_rays(z, R, n, beta, beta_min, beta_c, beta0, beta_ray, ctl, nctl, nullptr, nullptr, nullptr, 0, nullptr, 0, 0, 0,
-                                nullptr, stream);
-}
-
-int neat_sampler_init_rays(const float* z, int R, int n, const float* beta, float beta_min, float beta_c, float* beta0, float* beta_ray,
-                           int* ctl, int nctl, const float* origins, const float* dirs, float* x_fm, int ldp, const float* keys, int n_step,
-                           int n_cand, int n_extra, int* pick_all, void* stream) {
-  if (R <= 0 || n < 2 || n > SMAX || !z || !beta || !beta0 || !beta_ray || nctl < 0 || (nctl > 0 && !ctl)) return -1;
-  if (x_fm && (!origins || !dirs || (long long)ldp < (long long)R * n)) return -1;
-  const bool picks = keys != nullptr;
-  if (picks && (!pick_all || n_step < 1 || n_cand < 1 || n_extra < 2 || n_extra > n_step || n_step * n_cand > SMAX)) return -1;
-  SamplerInitArgs a{z, R, n, beta, beta_min, beta_c, beta0, beta_ray, ctl, nctl, origins, dirs, x_fm, ldp, keys, n_step, n_cand, n_extra, pick_all,
-                    (R + 3) / 4, picks ? (n_step * n_cand + 255) / 256 : 0};
-  hipLaunchKernelGGL(sampler_init_kernel, dim3(a.init_blocks + n_cand * a.pick_parts), dim3(256), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_round(const float* z, int n, int R, const float* sdf_old, const float* sdf_new, const int* order, int n_old,
-                       const float* beta_in, const float* beta0, float eps, int iters, float* sdf_out, float* beta_out, int* ctl, int round,
-                       int max_rounds, float add_tiny, const float* u_refine, int N_refine, float* samples_refine, float* z_merged,
-                       int* order_out, const float* origins, const float* dirs, float* x_fm, int ldp, const float* u_final,
-                       int u_final_stride, int N_final, float* samples_final, float* z_final, int ld_final, void* stream) {
-  if (R <= 0) return 0;
-  const bool last = round + 1 >= max_rounds;
-  if (n < 2 || n > SMAX || !z || !sdf_new || (order && !sdf_old) || !beta_in || !beta0 || !sdf_out || !beta_out || !ctl || round < 0 ||
-      round >= max_rounds || N_final < 1 || N_final > SMAX || !u_final || !samples_final || !z_final || ld_final < n) return -1;
-  if (!last && (N_refine < 1 || n + N_refine > SMAX || !u_refine || !samples_refine || !z_merged || !order_out ||
-                (x_fm && (!origins || !dirs || (long long)ldp < (long long)R * N_refine)))) return -1;
-  SamplerRoundArgs a{z, n, R, sdf_old, sdf_new, order, n_old, beta_in, beta0, eps, iters, sdf_out, beta_out, ctl, round, max_rounds, add_tiny,
-                     u_refine, N_refine, samples_refine, z_merged, order_out, origins, dirs, x_fm, ldp, u_final, u_final_stride, N_final,
-                     samples_final, z_final, ld_final, g_sampler_ablate};
-  hipLaunchKernelGGL(sampler_round_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_finish_picked(const float* samples, int N, const float* z_final, int ld_final, const int* n_final, const int* pick_all,
-                               int n_step, int n_extra, float near, float far, int R, const int* eik_idx, float* z_vals, float* z_eik,
-                               void* stream) {
-  if (R <= 0) return 0;
-  if (N + 2 + n_extra > SMAX || ld_final > SMAX || !samples || !z_final || !n_final || n_extra == 1 || n_extra < 0 || n_step < 1 || !eik_idx ||
-      !z_vals || !z_eik) return -1;
-  SamplerFinishArgs a{samples, N, z_final, 0, pick_all, n_extra, near, far, R, eik_idx, z_vals, z_eik, ld_final};
-  a.n_final = n_final; a.n_step = n_step;
-  hipLaunchKernelGGL(sampler_finish_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_bound_dev(const float* z, int n, int R, const float* sdf_old, const float* sdf_new, const int* order, int n_old,
-                           const float* beta_in, const float* beta0, float eps, int iters, float* sdf_out, float* beta_out,
-                           int* open, const int* gate, int gate_value, void* stream) {
-  if (R <= 0) return 0;
-  if (n < 2 || n > SMAX || !z || !sdf_new || !beta_in || !beta0 || !sdf_out || !beta_out || !open) return -1;
-  SamplerBoundArgs a{z, n, R, sdf_old, sdf_new, order, n_old, beta_in, beta0, eps, iters, sdf_out, beta_out, open, gate, gate_value};
-  hipLaunchKernelGGL(sampler_bound_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_resample_dev(const float* z, const float* sdf, int n, int R, const float* beta, float add_tiny,
-                              const float* u_refine, int N_refine, float* samples_refine, float* z_merged, int* order,
-                              const float* u_final, int u_final_stride, int N_final, float* samples_final, float* z_final, int ld_final,
-                              int* n_final, const int* open, int* cont, int round, int max_rounds, void* stream) {
-  if (R <= 0) return 0;
-  if (n < 2 || n > SMAX || N_refine < 1 || N_final < 1 || n + N_refine > SMAX || ld_final < n || !z || !sdf || !beta || !u_refine || !u_final ||
-      !samples_refine || !z_merged || !order || !samples_final || !z_final || !n_final || !open || !cont || round < 0 || round >= max_rounds)
-    return -1;
-  SamplerResampleArgs a{};
-  a.z = z; a.sdf = sdf; a.n = n; a.R = R; a.beta = beta; a.refine = 1; a.add_tiny = add_tiny;
-  a.u = u_refine; a.u_stride = 0; a.N = N_refine; a.samples = samples_refine; a.z_merged = z_merged; a.order = order;
-  a.open = open; a.cont = cont; a.round = round; a.max_rounds = max_rounds;
-  a.u_final = u_final; a.u_final_stride = u_final_stride; a.N_final = N_final; a.samples_final = samples_final;
-  a.z_final = z_final; a.ld_final = ld_final; a.n_final = n_final;
-  hipLaunchKernelGGL(sampler_resample_kernel, dim3(R), dim3(BOUND_T), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_sampler_finish_dev(const float* samples, int N, const float* z_final, int ld_final, const int* n_final, const float* keys,
-                            int n_extra, int* pick, float near, float far, int R, const int* eik_idx, float* z_vals, float* z_eik,
-                            void* stream) {
-  if (R <= 0) return 0;
-  if (N + 2 + n_extra > SMAX || ld_final > SMAX || !samples || !z_final || !n_final || (n_extra > 0 && !pick) || n_extra == 1 || !eik_idx ||
-      !z_vals || !z_eik) return -1;
-  if (n_extra > 0) hipLaunchKernelGGL(sampler_pick_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_final, keys, n_extra, pick);
-  SamplerFinishArgs a{samples, N, z_final, 0, pick, n_extra, near, far, R, eik_idx, z_vals, z_eik, ld_final};
-  hipLaunchKernelGGL(sampler_finish_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_encode_lines(const float* lines, int N, int H, int W, float* lmap, int* label, unsigned char* valid, void* stream) {
-  if (N < 0 || H <= 0 || W <= 0 || (N > 0 && !lines) || !lmap || !label) return -1;
-  hipLaunchKernelGGL(encode_lines_kernel, grid1(H * W), dim3(256), 0, (hipStream_t)stream, lines, N, H, W, lmap, label, valid);
-  return (int)hipGetLastError();
-}
-
-int neat_gather_batch(const int* pool, int npool, const long long* draw, int n, int W, const float* att, const float* rgb, const int* labels,
-                      const float* lines, int nlines, float* uv, float* uv_proj, float* rgb_out, float* lines_out, long long* labels_out,
-                      long long* pixel_out, void* stream) {
-  if (n < 0 || npool <= 0 || W <= 0 || nlines <= 0 || !pool || !att || !rgb || !labels || !lines) return -1;
-  if (n == 0) return 0;
-  if (!draw || !uv || !uv_proj || !rgb_out || !lines_out || !labels_out || !pixel_out) return -1;
-  GatherBatchArgs a{pool, draw, n, W, npool, att, rgb, labels, lines, nlines, uv, uv_proj, rgb_out, lines_out, labels_out, pixel_out};
-  hipLaunchKernelGGL(gather_batch_kernel, grid1(n), dim3(256), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_copy_batch(const void* const* src, void* const* dst, const long long* nbytes, int n, void* stream) {
-  if (n < 0 || n > COPY_BATCH_MAX) return -1;
-  if (n == 0) return 0;
-  if (!src || !dst || !nbytes) return -1;
-  CopyBatchArgs a{};
-  long long mx = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!src[i] || !dst[i] || nbytes[i] < 0 || (nbytes[i] & 3) || ((size_t)src[i] & 3) || ((size_t)dst[i] & 3)) return -1;
-    a.src[i] = (const unsigned*)src[i]; a.dst[i] = (unsigned*)dst[i]; a.words[i] = nbytes[i] >> 2;
-    mx = nbytes[i] > mx ? nbytes[i] : mx;
-  }
-  a.n = n;
-  const int by = (int)((mx / 4 + 1023) / 1024);          // 256 threads x 4 words per block
-  hipLaunchKernelGGL(copy_batch_kernel, dim3(by < 1 ? 1 : (by > 1024 ? 1024 : by), n), dim3(256), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_adam_step(float* params, const float* const* grads, const long long* seg_offsets, const int* seg_steps, int nseg,
-                   float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, void* stream) {
-  if (nseg <= 0) return 0;
-  if (!params || !grads || !seg_offsets || !seg_steps || !exp_avg || !exp_avg_sq || nseg > ADAM_MAXSEG) return -1;
-  AdamSegs segs{};
-  for (int s = 0; s < nseg; ++s) {
-    segs.g[s] = grads[s]; segs.off[s] = seg_offsets[s];
-    if (grads[s]) {
-      if (seg_steps[s] < 1) return -1;
-      const double bc1 = 1.0 - pow((double)beta1, (double)seg_steps[s]), bc2 = 1.0 - pow((double)beta2, (double)seg_steps[s]);
-      segs.lr_over_bc1[s] = (float)((double)lr / bc1); segs.inv_sqrt_bc2[s] = (float)(1.0 / sqrt(bc2));
-    }
-  }
-  segs.off[nseg] = seg_offsets[nseg];
-  segs.nseg = nseg;
-  const long long n = seg_offsets[nseg];
-  if (n <= 0) return 0;
-  const long long per_block = 1024LL * ADAM_PASSES;    // ADAM_PASSES float4 passes of 256 threads
-  const long long blocks = (n + per_block - 1) / per_block;
-  hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, segs, exp_avg,
-                     exp_avg_sq, n, beta1, beta2, eps, (const float*)nullptr);
-  return (int)hipGetLastError();
-}
-
-int neat_adam_step_coef(float* params, const float* const* grads, const long long* seg_offsets, int nseg, float* exp_avg, float* exp_avg_sq,
-                        const float* coef, float beta1, float beta2, float eps, void* stream) {
-  if (nseg <= 0) return 0;
-  if (!params || !grads || !seg_offsets || !exp_avg || !exp_avg_sq || !coef || nseg > ADAM_MAXSEG) return -1;
-  AdamSegs segs{};
-  for (int s = 0; s < nseg; ++s) { segs.g[s] = grads[s]; segs.off[s] = seg_offsets[s]; }
-  segs.off[nseg] = seg_offsets[nseg];
-  segs.nseg = nseg;
-  const long long n = seg_offsets[nseg];
-  if (n <= 0) return 0;
-  const long long per_block = 1024LL * ADAM_PASSES;
-  const long long blocks = (n + per_block - 1) / per_block;
-  hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, segs, exp_avg,
-                     exp_avg_sq, n, beta1, beta2, eps, coef);
-  return (int)hipGetLastError();
-}
-
-int neat_ffn_forward(const float* x, int J, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
-                     const float* b2, float* h1, float* h2, float* y, void* stream) {
-  if (J <= 0) return 0;
-  if (!x || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !h1 || !h2 || !y) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  if (J > FFN_FUSED_MIN_ROWS) {       // many rows: one fused launch, 8 rows per workgroup
-    hipLaunchKernelGGL(ffn_forward_kernel, dim3((J + FFN_RB - 1) / FFN_RB), dim3(FFN_H), 0, st, x, J, W0, b0, W1, b1, W2, b2, h1, h2, y);
-    return (int)hipGetLastError();
-  }
-  // few rows (the 64 latents of the ABC scenes): one launch per layer, each spread over rows x 32-output blocks
-  const dim3 gh((J + FFN_RB - 1) / FFN_RB, FFN_H / 32), g3((J + FFN_RB - 1) / FFN_RB, 1);
-  const float* nogate = nullptr; float* noy2 = nullptr;
-  if (g_ffn_mfma) {      // the two 256 x 256 layers on the fp32 matrix pipe (tuning key 28)
-    const dim3 gm((J + 31) / 32, FFN_H / 32);
-    hipLaunchKernelGGL(ffn_mfma_kernel<false>, gm, dim3(256), 0, st, x, J, W0, b0, nogate, 1, h1);
-    hipLaunchKernelGGL(ffn_mfma_kernel<false>, gm, dim3(256), 0, st, (const float*)h1, J, W1, b1, nogate, 1, h2);
-  } else {
-    hipLaunchKernelGGL(ffn_dense_kernel<false>, gh, dim3(256), 0, st, x, J, FFN_H, FFN_H, W0, b0, nogate, 1, h1, noy2);
-    hipLaunchKernelGGL(ffn_dense_kernel<false>, gh, dim3(256), 0, st, (const float*)h1, J, FFN_H, FFN_H, W1, b1, nogate, 1, h2, noy2);
-  }
-  hipLaunchKernelGGL(ffn_dense_kernel<false>, g3, dim3(256), 0, st, (const float*)h2, J, FFN_H, 3, W2, b2, nogate, 0, y, noy2);
-  return (int)hipGetLastError();
-}
-
-int neat_ffn_backward(const float* x, int J, const float* W0, const float* W1, const float* W2, const float* h1, const float* h2,
-                      const float* dy, float* ws2, float* dx, float* dW0, float* db0, float* dW1, float* db1, float* dW2, float* db2,
-                      void* stream) {
-  if (J <= 0) return 0;
-  if (!x || !W0 || !W1 || !W2 || !h1 || !h2 || !dy || !ws2 || !dx || !dW0 || !db0 || !dW1 || !db1 || !dW2 || !db2) return -1;
-  float* d_a1 = ws2; float* d_a2 = ws2 + (size_t)J * FFN_H;
-  hipStream_t st = (hipStream_t)stream;
-  if (J > FFN_FUSED_MIN_ROWS)
-    hipLaunchKernelGGL(ffn_backward_data_kernel, dim3((J + FFN_RB - 1) / FFN_RB), dim3(FFN_H), 0, st, dy, J, W0, W1, W2, h1, h2, d_a1, d_a2, dx);
-  else {
-    const dim3 gh((J + FFN_RB - 1) / FFN_RB, FFN_H / 32);
-    const float* nobias = nullptr; const float* nogate = nullptr; float* noy2 = nullptr;
-    hipLaunchKernelGGL(ffn_dense_kernel<true>, gh, dim3(256), 0, st, dy, J, 3, FFN_H, W2, nobias, h2, 0, d_a2, noy2);
-    if (g_ffn_mfma) {
-      const dim3 gm((J + 31) / 32, FFN_H / 32);
-      hipLaunchKernelGGL(ffn_mfma_kernel<true>, gm, dim3(256), 0, st, (const float*)d_a2, J, W1, nobias, h1, 0, d_a1);
-      hipLaunchKernelGGL(ffn_mfma_kernel<true>, gm, dim3(256), 0, st, (const float*)d_a1, J, W0, nobias, nogate, 0, dx);
-    } else {
-      hipLaunchKernelGGL(ffn_dense_kernel<true>, gh, dim3(256), 0, st, (const float*)d_a2, J, FFN_H, FFN_H, W1, nobias, h1, 0, d_a1, noy2);
-      hipLaunchKernelGGL(ffn_dense_kernel<true>, gh, dim3(256), 0, st, (const float*)d_a1, J, FFN_H, FFN_H, W0, nobias, nogate, 0, dx, noy2);
-    }
-  }
-  if (g_ffn_mfma)
-    hipLaunchKernelGGL(ffn_wgrad_mfma_kernel, dim3(FFN_H / 32, FFN_H / 32, 3), dim3(64 * FFN_WNW), 0, (hipStream_t)stream, x, h1, h2, d_a1, d_a2, dy, J, dW0, db0,
-                       dW1, db1, dW2, db2);
-  else
-  hipLaunchKernelGGL(ffn_backward_weights_kernel, dim3(FFN_H / FFN_RN, 3), dim3(64 * FFN_JG), 0, (hipStream_t)stream, x, h1, h2, d_a1, d_a2, dy, J, dW0, db0,
-                     dW1, db1, dW2, db2);
-  return (int)hipGetLastError();
-}
-
-int neat_loss_terms(const float* rgb, const float* rgb_gt, int R, const float* gtheta, int E, const float* loc3, const float* loc2c, int K,
-                    const float* glo3, const float* glo2c, int J, float* scal, float* d_rgb, float* d_gtheta, float* pair_cost,
-                    float eik_grad_scale, void* stream) {
-  if (R <= 0 || !rgb || !rgb_gt || !scal || !d_rgb || E < 0 || K < 0 || J < 0) return -1;
-  if ((E > 0 && (!gtheta || !d_gtheta)) || (K > 0 && J > 0 && (!loc3 || !loc2c || !glo3 || !glo2c || !pair_cost))) return -1;
-  LossTermsArgs a{rgb, rgb_gt, R, gtheta, E, loc3, loc2c, (J > 0 ? K : 0), glo3, glo2c, J, scal, d_rgb, d_gtheta, pair_cost, eik_grad_scale};
-  hipLaunchKernelGGL(loss_terms_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_loss_lines_terms(const float* pred_px, const float* pred_calib, const float* gt5, const float* Kmat, int L, float threshold, float* out3,
-                          float* d_pred_calib, float grad_scale, const float* rgb, const float* rgb_gt, int R, const float* gtheta, int E,
-                          const float* loc3, const float* loc2c, int K, const float* glo3, const float* glo2c, int J, float* scal, float* d_rgb,
-                          float* d_gtheta, float* pair_cost, float eik_grad_scale, const float* w2c, const float* lines3d, float* d_lines3d,
-                          void* stream) {
-  if (L <= 0 || !pred_px || !pred_calib || !gt5 || !Kmat || !out3 || !d_pred_calib) return -1;
-  if (d_lines3d && (!w2c || !lines3d)) return -1;
-  if (R <= 0 || !rgb || !rgb_gt || !scal || !d_rgb || E < 0 || K < 0 || J < 0) return -1;
-  if ((E > 0 && (!gtheta || !d_gtheta)) || (K > 0 && J > 0 && (!loc3 || !loc2c || !glo3 || !glo2c || !pair_cost))) return -1;
-  LineLossesArgs l{pred_px, pred_calib, gt5, Kmat, L, threshold, out3, d_pred_calib, grad_scale, w2c, lines3d, d_lines3d};
-  LossTermsArgs a{rgb, rgb_gt, R, gtheta, E, loc3, loc2c, (J > 0 ? K : 0), glo3, glo2c, J, scal, d_rgb, d_gtheta, pair_cost, eik_grad_scale};
-  hipLaunchKernelGGL(loss_lines_terms_kernel, dim3(2), dim3(1024), 0, (hipStream_t)stream, l, a);
-  return (int)hipGetLastError();
-}
-
-int neat_loss_pairs(const long long* ri, const long long* ci, const int* n_match, int Kmax, const float* loc3, const float* loc2c,
-                    const float* loc2, const float* glo3, const float* glo2c, const float* glo2, int J, const float* pair_cost, float* scal,
-                    float* d_glo3, float* d_glo2c, const float* line_loss, float w_eik, float w_line, float w_j3, float w_j2, int weighted_grads,
-                    float* total, const float* w2c, void* stream) {
-  if (Kmax < 0 || J <= 0 || !ri || !ci || !n_match || !loc3 || !loc2c || !loc2 || !glo3 || !glo2c || !glo2 || !pair_cost || !scal ||
-      !d_glo3 || !d_glo2c || !line_loss) return -1;
-  LossPairsArgs a{ri, ci, n_match, Kmax, loc3, loc2c, loc2, glo3, glo2c, glo2, J, pair_cost, scal, d_glo3, d_glo2c, line_loss, w_eik, w_line,
-                  w_j3, w_j2, weighted_grads, total, w2c};
-  hipLaunchKernelGGL(loss_pairs_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_l3d(const float* x, const float* o, const float* d, const float* normal, int R, float* l3d, void* stream) {
-  if (R <= 0) return 0;
-  if (!x || !o || !d || !normal || !l3d) return -1;
-  hipLaunchKernelGGL(l3d_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, o, d, normal, R, l3d);
-  return (int)hipGetLastError();
-}
-
-int neat_junction_cost(const float* cand2d, const float* gt2d, int V, int C, float* cost, void* stream) {
-  if (V <= 0 || C <= 0) return 0;
-  if (!cand2d || !gt2d || !cost) return -1;
-  hipLaunchKernelGGL(junction_cost_kernel, dim3((V * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, cand2d, gt2d, V, C, cost);
-  return (int)hipGetLastError();
-}
-
-int neat_junction_gate(const long long* rows, const long long* cols, int K, const float* cost, int C, const float* cand3d,
-                       const float* cand2d, const float* cand2d_calib, int use_median, float* median, unsigned char* good, float* j3d,
-                       float* j2d, float* j2d_calib, void* stream) {
-  if (K <= 0) return 0;
-  if (K > 2048 || !rows || !cols || !cost || !cand3d || !cand2d || !cand2d_calib || !good || !j3d || !j2d || !j2d_calib ||
-      (use_median && !median)) return -1;
-  JunctionGateArgs a{rows, cols, K, cost, C, cand3d, cand2d, cand2d_calib, use_median, median, good, j3d, j2d, j2d_calib};
-  hipLaunchKernelGGL(junction_gate_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-int neat_inv_small(const float* A, int n, int lda, float* out, void* stream) {
-  if (!A || !out || n < 1 || n > 4 || lda < n) return -1;
-  hipLaunchKernelGGL(inv_small_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, A, n, lda, out);
-  return (int)hipGetLastError();
-}
-
-int neat_camera_mats(const float* pose, const float* K, int kstride, float* w2c, float* K3, void* stream) {
-  if (!pose || !K || !w2c || !K3 || kstride < 3) return -1;
-  hipLaunchKernelGGL(camera_mats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, pose, K, kstride, w2c, K3);
-  return (int)hipGetLastError();
-}
-
-int neat_project2d(const float* K, const float* w2c, const float* X, int N, float* uv, void* stream) {
-  if (N <= 0) return 0;
-  if (!K || !w2c || !X || !uv) return -1;
-  hipLaunchKernelGGL(project2d_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, w2c, X, N, uv);
-  return (int)hipGetLastError();
-}
-
-int neat_project2d_pair(const float* K, const float* K2, const float* w2c, const float* X, int N, float* uv, float* uv2, void* stream) {
-  if (N <= 0) return 0;
-  if (!K || !K2 || !w2c || !X || !uv || !uv2) return -1;
-  hipLaunchKernelGGL(project2d_pair_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, K2, w2c, X, N, uv, uv2);
-  return (int)hipGetLastError();
-}
-
-int neat_camera_setup(const float* uv, const float* uv2, const float* pose, const float* K, int kstride, int R, float* dirs, float* origins,
-                      float* dirs2, float* w2c, float* K3, void* stream) {
-  if (R <= 0 || !uv || !pose || !K || !dirs || !origins || (uv2 && !dirs2) || !w2c || !K3 || kstride < 3) return -1;
-  hipLaunchKernelGGL(camera_setup_kernel, grid1(R), dim3(256), 0, (hipStream_t)stream, uv, uv2, pose, K, kstride, R, dirs, origins, dirs2, w2c, K3);
-  return (int)hipGetLastError();
-}
-
-int neat_project2d_backward(const float* K, const float* w2c, const float* X, int N, const float* d_uv, float* d_X, void* stream) {
-  if (N <= 0) return 0;
-  if (!K || !w2c || !X || !d_uv || !d_X) return -1;
-  hipLaunchKernelGGL(project2d_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, K, w2c, X, N, d_uv, d_X);
-  return (int)hipGetLastError();
-}
-
-int neat_line_loss(const float* pred, const float* gt, const float* weight, int R, float threshold, float* out2, float* per_line,
-                   float* d_pred, void* stream) {
-  if (R <= 0 || !pred || !gt || !weight || !out2 || !per_line || !d_pred) return -1;
-  hipLaunchKernelGGL(line_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred, gt, weight, R, threshold, out2, per_line, d_pred);
-  return (int)hipGetLastError();
-}
-
-int neat_line_losses(const float* pred_px, const float* pred_calib, const float* gt5, const float* K, int R, float threshold, float* out3,
-                     float* d_pred_calib, float grad_scale, void* stream) {
-  if (R <= 0 || !pred_px || !pred_calib || !gt5 || !K || !out3 || !d_pred_calib) return -1;
-  hipLaunchKernelGGL(line_losses_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, pred_px, pred_calib, gt5, K, R, threshold, out3, d_pred_calib, grad_scale);
-  return (int)hipGetLastError();
-}
-
-size_t neat_lsap_ws_bytes(int nr, int nc) {
-  const size_t mx = (size_t)(nr > nc ? nr : nc), mn = (size_t)(nr < nc ? nr : nc);
-  return (mn + 2 * mx) * sizeof(double) + ((size_t)nr + (size_t)nc + 5 * mx + 2 * mn) * sizeof(int);
-}
-
-int neat_lsap(const float* cost, int nr, int nc, const unsigned char* row_mask, const unsigned char* col_mask, long long* row_ind,
-              long long* col_ind, int* n_match, void* ws, void* stream) {
-  if (nr < 0 || nc < 0 || !n_match) return -1;
-  if (nr == 0 || nc == 0) return (int)hipMemsetAsync(n_match, 0, sizeof(int), (hipStream_t)stream);
-  if (!cost || !row_ind || !col_ind || !ws) return -1;
-  const size_t mx = (size_t)(nr > nc ? nr : nc), mn = (size_t)(nr < nc ? nr : nc);
-  LsapArgs a{cost, nr, nc, row_mask, row_ind, col_ind, n_match, (double*)ws, (int*)((double*)ws + mn + 2 * mx)};
-  a.col_mask = col_mask;
-  const size_t dbytes = (mn + 2 * mx) * sizeof(double), ibytes = ((size_t)nr + (size_t)nc + 5 * mx + 2 * mn) * sizeof(int);
-  size_t lds = 0;
-  constexpr size_t LSAP_LDS_MAX = 156 * 1024;
-  a.cost_lds_off = -1;
-  if (dbytes + ibytes <= LSAP_LDS_MAX) {
-    static DevOnce attr_set;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lsap_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LSAP_LDS_MAX);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-    a.use_lds = 1; a.lds_int_off = (int)dbytes; lds = (dbytes + ibytes + 15) & ~(size_t)15;
-    const size_t cbytes = (size_t)nr * nc * sizeof(float);
-    if (lds + cbytes <= LSAP_LDS_MAX) { a.cost_lds_off = (int)lds; lds += cbytes; }      // the cost matrix too (8 x 2048 fits)
-  }
-  // threads: two columns per thread, whole waves (a small problem does not pay 16-wave barriers; eight columns per thread measured slower)
-  int threads = (int)((mx + 1) / 2 + 63) / 64 * 64;
-  threads = threads < 64 ? 64 : (threads > LSAP_WG ? LSAP_WG : threads);
-  hipLaunchKernelGGL(lsap_kernel, dim3(1), dim3(threads), lds, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
-}
-
-size_t neat_dbscan_ws_bytes(int n) { return (size_t)n * 2 * sizeof(int); }
-
-int neat_dbscan_means(const float* points, int n, double eps, float* centres, unsigned char* valid, int* count, void* ws, void* stream) {
-  if (n <= 0 || n > DBSCAN_MAXN || !points || !centres || !valid || !count || !ws || !(eps > 0.0)) return -1;
-  int* parent = (int*)ws; int* has_nb = parent + n;
-  hipLaunchKernelGGL(dbscan_init_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, parent, has_nb, n);
-  hipLaunchKernelGGL(dbscan_union_kernel, dim3(n), dim3(128), 0, (hipStream_t)stream, points, n, eps * eps, parent, has_nb);
-  // mode 2 (18 n bytes of dynamic LDS fit next to the 32 KB of labels): O(n) fixed-point sums; else one wavefront per cluster over all
-  // points, read from LDS (mode 1: 12 n bytes fit) or from global memory (mode 0)
-  const size_t acc_bytes = (size_t)(n / 2) * 28 + (size_t)n * 4, pbytes = (size_t)n * 12;
-  const int mode = acc_bytes <= 96 * 1024 ? 2 : (pbytes <= 96 * 1024 ? 1 : 0);
-  if (mode) {
-    static DevOnce attr_set;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dbscan_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      if (e != hipSuccess) return (int)e;
-      attr_set = true;
-    }
-  }
-  hipLaunchKernelGGL(dbscan_finish_kernel, dim3(1), dim3(1024), mode == 2 ? acc_bytes : (mode == 1 ? pbytes : 0), (hipStream_t)stream, points, n,
-                     parent, has_nb, centres, valid, count, mode);
-  return (int)hipGetLastError();
-}
-
-int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream) {
-  if (R <= 0 || S <= 0) return 0;
-  hipLaunchKernelGGL(volume_weights_kernel, dim3((R + 3) / 4), dim3(WG), 0, (hipStream_t)stream, z, sdf, R, S, beta, weights);
-  return (int)hipGetLastError();
-}
-
-// ---- ABI v15: wireframe parsing (kernels_parse.hpp) -----------------------------------------------------------------------------
-static inline size_t parse_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline int parse_tiles(int n) { return (2 * n + PARSE_TILE - 1) / PARSE_TILE; }
-
-int neat_parse_match(const float* lines2d, int n, const float* gt, int m, int gt_stride, float threshold, int* label, float* mindis,
-                     void* stream) {
-  if (n < 0 || m < 0 || (m > 0 && (!gt || gt_stride < 4))) return -1;
-  if (n == 0) return 0;
-  if (!lines2d || !label || !mindis) return -1;
-  hipLaunchKernelGGL(parse_match_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, (hipStream_t)stream, lines2d, n, gt, m, gt_stride, threshold,
-                     label, mindis);
-  return (int)hipGetLastError();
-}
-
-size_t neat_parse_group_ws_bytes(int n, int m) {
-  if (n < 0 || m < 0) return 0;
-  const size_t nt = (size_t)parse_tiles(n);
-  return parse_al((nt * m + 3 * (size_t)m) * sizeof(int)) + parse_al(2 * (size_t)n * sizeof(int));
-}
-
-int neat_parse_group(const int* label, const float* lines3d, const float* l3d, int n, int m, float* lines, float* scores, int* count,
-                     void* ws, void* stream) {
-  if (n < 0 || m < 0 || !count) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  if (n == 0 || m == 0) return (int)hipMemsetAsync(count, 0, sizeof(int), st);
-  if (!label || !lines3d || !l3d || !lines || !scores || !ws) return -1;
-  const int nt = parse_tiles(n);
-  int* run = (int*)ws;
-  int* cnt = run + (size_t)nt * m;
-  int* start = cnt + m;
-  int* slot = start + m;
-  int* order = (int*)((char*)ws + parse_al(((size_t)nt * m + 3 * (size_t)m) * sizeof(int)));
-  NEAT_CHECK(hipMemsetAsync(run, 0, (size_t)nt * m * sizeof(int), st));
-  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 0);
-  hipLaunchKernelGGL(parse_group_scan_kernel, dim3(1), dim3(1024), 0, st, run, nt, m, cnt, start, slot, count);
-  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 1);
-  hipLaunchKernelGGL(parse_group_reduce_kernel, dim3(m), dim3(PARSE_WG), 0, st, order, cnt, start, slot, lines3d, l3d, n, lines, scores);
-  return (int)hipGetLastError();
-}
-
-size_t neat_parse_vote_ws_bytes(int J, int mcap) {
-  if (J <= 0 || mcap <= 0) return 0;
-  const size_t nc = 2 * (size_t)mcap, k = std::min((size_t)J, nc);
-  return parse_al((size_t)J * nc * sizeof(float)) + parse_al(nc) + 2 * parse_al(k * sizeof(long long)) + parse_al(sizeof(int)) +
-         parse_al(neat_lsap_ws_bytes(J, (int)nc));
-}
-
-int neat_parse_vote(const float* junctions, int J, const float* lines, const int* count, int mcap, float threshold, int view, int* votes,
-                    int* first, void* ws, void* stream) {
-  if (J < 0 || mcap < 0 || view < 0) return -1;
-  if (J == 0 || mcap == 0) return 0;
-  if (!junctions || !lines || !count || !votes || !first || !ws) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  const int nc = 2 * mcap, k = std::min(J, nc);
-  char* p = (char*)ws;
-  float* cost = (float*)p; p += parse_al((size_t)J * nc * sizeof(float));
-  unsigned char* cmask = (unsigned char*)p; p += parse_al(nc);
-  long long* rows = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
-  long long* cols = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
-  int* n_match = (int*)p; p += parse_al(sizeof(int));
-  const size_t total = (size_t)J * nc;
-  hipLaunchKernelGGL(parse_vote_cost_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, junctions, J, lines, count, nc, cost, cmask);
-  NEAT_CHECK(hipGetLastError());
-  const int e = neat_lsap(cost, J, nc, nullptr, cmask, rows, cols, n_match, p, stream);
-  if (e != 0) return e;
-  hipLaunchKernelGGL(parse_vote_apply_kernel, grid1(k), dim3(256), 0, st, rows, cols, n_match, k, cost, nc, threshold, view, votes, first);
-  return (int)hipGetLastError();
-}
-
-size_t neat_parse_graph_ws_bytes(int V, int mcap, int J) {
-  if (V < 0 || mcap < 0 || J < 0) return 0;
-  return parse_al((size_t)V * mcap * sizeof(int)) + parse_al((size_t)J * sizeof(int));
-}
-
-int neat_parse_graph(const float* vlines, const float* vscores, const int* vcount, int V, int mcap, float score_threshold,
-                     const float* junctions, const int* votes, const int* first, int J, float* lines_out, float* junc_out,
-                     unsigned char* graph, int* pairs, float* wfi, int ecap, int* counts, void* ws, void* stream) {
-  if (V < 0 || mcap < 0 || J < 0 || ecap < 0 || !counts) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  if ((V > 0 && mcap > 0 && (!vlines || !vscores || !vcount || !lines_out || !ws)) ||
-      (J > 0 && (!junctions || !votes || !first || !junc_out || !graph || !ws)) || (ecap > 0 && (!pairs || !wfi))) return -1;
-  NEAT_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(int), st));
-  const int ncap = V * mcap;
-  if (ncap == 0 && J == 0) return 0;
-  int* idx = (int*)ws;
-  int* rowcnt = (int*)((char*)ws + parse_al((size_t)V * mcap * sizeof(int)));
-  hipLaunchKernelGGL(parse_select_kernel, dim3(2), dim3(1024), 0, st, vlines, vscores, vcount, V, mcap, score_threshold, junctions, votes, first,
-                     J, lines_out, junc_out, idx, counts);
-  if (J == 0 || ncap == 0) return (int)hipGetLastError();
-  NEAT_CHECK(hipMemsetAsync(graph, 0, (size_t)J * J, st));
-  hipLaunchKernelGGL(parse_graph_mark_kernel, grid1(ncap, PARSE_WG), dim3(PARSE_WG), 0, st, lines_out, junc_out, counts, ncap, J, graph);
-  hipLaunchKernelGGL(parse_edge_count_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt);
-  hipLaunchKernelGGL(parse_edge_write_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt, J, junc_out, ecap, pairs, wfi);
-  return (int)hipGetLastError();
-}
-
-size_t neat_parse_visibility_ws_bytes(int ecap, int V) {
-  if (ecap < 0 || V < 0) return 0;
-  return parse_al((size_t)V * ecap) + parse_al((size_t)ecap * sizeof(int));
-}
-
-int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, const float* gt, int gt_stride, const int* gt_off,
-                          const float* K3, const float* w2c, int V, float ckdist, int ckview, int* vis_count, float* checked,
-                          int* n_checked, void* ws, void* stream) {
-  if (ecap < 0 || V < 0 || !n_checked) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  if (ecap == 0) return (int)hipMemsetAsync(n_checked, 0, sizeof(int), st);
-  if (!lines || !vis_count || !checked || !ws || (V > 0 && (!gt_off || !K3 || !w2c || gt_stride < 4))) return -1;
-  unsigned char* vis = (unsigned char*)ws;
-  int* idx = (int*)((char*)ws + parse_al((size_t)V * ecap));
-  if (V > 0)
-    hipLaunchKernelGGL(parse_vis_kernel, dim3((ecap + PARSE_WG - 1) / PARSE_WG, V), dim3(PARSE_WG), 0, st, lines, n_lines, ecap, gt, gt_stride,
-                       gt_off, K3, w2c, ckdist, vis);
-  hipLaunchKernelGGL(parse_vis_count_kernel, dim3(1), dim3(1024), 0, st, lines, n_lines, ecap, V, vis, ckview, vis_count, idx, checked, n_checked);
   return (int)hipGetLastError();
 }
 

@@ -1177,7 +1177,7 @@ def test_x3_chains_ragged_round_as_half_batches(dev, P):
     not depend on which path it takes: the points of that round must come out bit-identical to a launch that holds them in whole
     batches (at most as many batches as workgroups), for get_outputs (save mode: sdf, features, normals) and get_sdf_vals (values
     mode), and the points before them must not change either."""
-    G = 256                                                # persistent workgroups of the chains (neat_api.hip: g_ws_grid)
+    G = 256                                                # persistent workgroups of the chains (neat_net.hip: g_ws_grid)
     m = build_model(dev, "rough", precision="fp16x3")
     x = (torch.rand(P, 3, generator=torch.Generator().manual_seed(P)) * 4 - 2).to(dev)
     nb = (P + 63) // 64
