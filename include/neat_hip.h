@@ -421,6 +421,34 @@ int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, cons
                           const float* K3, const float* w2c, int V, float ckdist, int ckview, int* vis_count, float* checked,
                           int* n_checked, void* ws, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, nothing existing changes, so the version number stays): the zero-level surface of the SDF as an indexed triangle mesh (code/utils/plots.py: get_surface_trace :101-138 and
+ * get_grid_uniform :318-329; the reference evaluates the grid through PyTorch in 100 000-point chunks and runs skimage's marching cubes
+ * on the host).  fp32 / int32, no atomics, fixed-order scans: two runs give the same bytes.  No entry point synchronises with the host.
+ *
+ * A grid has n[a] >= 2 nodes per axis over [b0[a], b1[a]], fewer than 2^31 nodes in all, x slowest and z fastest; node i of an axis sits
+ * at float(b0 + i (b1 - b0) / (n - 1)) evaluated in float64, the last node exactly at b1 (numpy.linspace, :322-324).  n, b0, b1 are HOST
+ * arrays of three.
+ * neat_grid_points : the points of `count` consecutive nodes from linear node `first_node` into x_fm [3][ldp] (feature-major, ldp >= count;
+ *   columns count..ldp are zeroed) = the x rows of a neat_sdf_ws_floats workspace at stride neat_sdf_ldp, ready for
+ *   neat_sdf_values_laid_out: no [N,3] point tensor exists.
+ * Marching tetrahedra on an fp32 grid [nx][ny][nz] (definitions: neat_amd/csrc/kernels_mesh.hpp).  A node is inside iff
+ *   v < level; an edge (7 classes per node: to the node at offset bits (4,2,1) of class + 1) carries one vertex iff its nodes differ in
+ *   that and both values are finite, at a + t (b - a), t = (level - va) / (vb - va) from the inside node a; each cell is cut into the six
+ *   tetrahedra around its main diagonal; a tetrahedron with a non-finite corner emits nothing.  Vertices ascend by (node, class), faces
+ *   by (cell, tetrahedron, triangle); triangle normals point towards increasing values.
+ * neat_mesh_ws_bytes : workspace of the two calls below (about 5 bytes per node); 0 for a grid they reject.
+ * neat_mesh_count : edge bits per node and the per-tile counts into ws; counts[0] = vertices, counts[1] = faces on the device
+ *   (-1, -1 if either exceeds int32).  The caller reads them once, allocates and calls
+ * neat_mesh_emit : verts [nv,3] fp32 and faces [nf,3] int32 for the same grid, level and ws; nv, nf as counted (writes beyond them are
+ *   dropped).  Bad arguments (an axis under 2 nodes, 2^31 nodes or more, null pointers, a NaN level) return -1 before any launch.
+ * neat_unit_rows3 : rows of g [n,3] scaled to unit length in place (vertex normals from the SDF gradient at the vertices). */
+int neat_grid_points(float* x_fm, int ldp, long long first_node, int count, const int* n, const double* b0, const double* b1, void* stream);
+size_t neat_mesh_ws_bytes(int nx, int ny, int nz);
+int neat_mesh_count(const float* grid, int nx, int ny, int nz, float level, void* ws, int* counts, void* stream);
+int neat_mesh_emit(const float* grid, int nx, int ny, int nz, const double* b0, const double* b1, float level, void* ws, float* verts, int nv,
+                   int* faces, int nf, void* stream);
+int neat_unit_rows3(float* g, int n, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

@@ -120,6 +120,13 @@ _SIGNATURES = {
     "neat_parse_visibility_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "neat_parse_visibility": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_float,
                                              ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_grid_points": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_fp]),
+    "neat_mesh_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "neat_mesh_count": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, c_fp, c_fp]),
+    "neat_mesh_emit": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_double), ctypes.c_float, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp]),
+    "neat_unit_rows3": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp]),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

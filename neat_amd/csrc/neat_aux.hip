@@ -1,12 +1,15 @@
 // C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
-// samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, volume weights.
+// samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, volume weights.
 // Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
 // boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
 #include "kernels_sampler.hpp"
 #include "kernels_junction.hpp"
 #include "kernels_parse.hpp"
+#include "kernels_mesh.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
+#include <cmath>
+#include <limits.h>
 #include <math.h>
 
 using namespace neat;
@@ -622,5 +625,81 @@ int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, cons
   return (int)hipGetLastError();
 }
 
+// ---- added to ABI v15: the SDF's level surface as a triangle mesh (kernels_mesh.hpp) -------------------------------------------------------
+static bool mesh_axes(const int* n, const double* b0, const double* b1, MeshAxes* g) {
+  if (!n || !b0 || !b1) return false;
+  for (int a = 0; a < 3; ++a) {
+    if (n[a] < 2 || !std::isfinite(b0[a]) || !std::isfinite(b1[a])) return false;
+    g->n[a] = n[a]; g->b0[a] = b0[a]; g->b1[a] = b1[a]; g->step[a] = (b1[a] - b0[a]) / (double)(n[a] - 1);
+  }
+  return true;
+}
+static inline long long mesh_nodes(int nx, int ny, int nz) {      // 0: not a grid this code indexes (an axis under 2 nodes, or 2^31 nodes and more)
+  if (nx < 2 || ny < 2 || nz < 2) return 0;
+  const long long n = (long long)nx * ny;
+  if (n > INT_MAX) return 0;
+  const long long N = n * nz;
+  return N > INT_MAX ? 0 : N;
+}
+static inline size_t mesh_tiles(long long nodes) { return (size_t)((nodes + MESH_TILE - 1) / MESH_TILE); }
+
+int neat_grid_points(float* x_fm, int ldp, long long first_node, int count, const int* n, const double* b0, const double* b1, void* stream) {
+  MeshAxes g;
+  if (!x_fm || count < 0 || ldp < count || first_node < 0 || !mesh_axes(n, b0, b1, &g)) return -1;
+  if (first_node + count > (long long)n[0] * n[1] * n[2]) return -1;
+  if (ldp == 0) return 0;
+  hipLaunchKernelGGL(grid_points_kernel, grid1(ldp), dim3(256), 0, (hipStream_t)stream, x_fm, ldp, first_node, count, g);
+  return (int)hipGetLastError();
+}
+
+size_t neat_mesh_ws_bytes(int nx, int ny, int nz) {
+  const long long N = mesh_nodes(nx, ny, nz);
+  if (N == 0) return 0;
+  return parse_al((size_t)N) + parse_al((size_t)N * sizeof(int)) + 2 * parse_al(mesh_tiles(N) * sizeof(int));
+}
+
+static MeshArgs mesh_args(const float* grid, int nx, int ny, int nz, long long N, float level, void* ws) {
+  MeshArgs a{};
+  a.grid = grid; a.nx = nx; a.ny = ny; a.nz = nz; a.nodes = (int)N; a.level = level;
+  char* p = (char*)ws;
+  a.emask = (unsigned char*)p; p += parse_al((size_t)N);
+  a.vbase = (int*)p; p += parse_al((size_t)N * sizeof(int));
+  a.tile_v = (int*)p; p += parse_al(mesh_tiles(N) * sizeof(int));
+  a.tile_f = (int*)p;
+  return a;
+}
+
+int neat_mesh_count(const float* grid, int nx, int ny, int nz, float level, void* ws, int* counts, void* stream) {
+  const long long N = mesh_nodes(nx, ny, nz);
+  if (N == 0 || !grid || !ws || !counts || level != level) return -1;
+  MeshArgs a = mesh_args(grid, nx, ny, nz, N, level, ws);
+  a.counts = counts;
+  const int tiles = (int)mesh_tiles(N);
+  hipLaunchKernelGGL(mesh_count_kernel, dim3(tiles), dim3(MESH_WG), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a.tile_v, a.tile_f, tiles, counts);
+  return (int)hipGetLastError();
+}
+
+int neat_mesh_emit(const float* grid, int nx, int ny, int nz, const double* b0, const double* b1, float level, void* ws, float* verts, int nv,
+                   int* faces, int nf, void* stream) {
+  const long long N = mesh_nodes(nx, ny, nz);
+  const int n[3] = {nx, ny, nz};
+  if (N == 0 || !grid || !ws || nv < 0 || nf < 0 || (nv > 0 && !verts) || (nf > 0 && !faces) || level != level) return -1;
+  MeshArgs a = mesh_args(grid, nx, ny, nz, N, level, ws);
+  if (!mesh_axes(n, b0, b1, &a.ax)) return -1;
+  if (nv == 0) return 0;                 // no vertex, hence no face
+  a.verts = verts; a.nv = nv; a.faces = faces; a.nf = nf;
+  const int tiles = (int)mesh_tiles(N);
+  hipLaunchKernelGGL(mesh_verts_kernel, dim3(tiles), dim3(MESH_WG), 0, (hipStream_t)stream, a);
+  if (nf > 0) hipLaunchKernelGGL(mesh_faces_kernel, dim3(tiles), dim3(MESH_WG), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int neat_unit_rows3(float* g, int n, void* stream) {
+  if (n < 0 || (n > 0 && !g)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(mesh_normalize_kernel, grid1(n), dim3(256), 0, (hipStream_t)stream, g, n);
+  return (int)hipGetLastError();
+}
 
 }  // extern "C"

@@ -549,10 +549,13 @@ def sdf_query_workspace(handle, P, device, fast=False):
     return ws, int(lib.neat_sdf_ldp(P, prec))
 
 
-def sdf_values_laid_out(handle, ws, P, radius, scale, gate=None, fast=False):
-    """sdf_values on the P points already laid out in `ws` (sdf_query_workspace) -> [P, 1]."""
+def sdf_values_laid_out(handle, ws, P, radius, scale, gate=None, fast=False, out=None):
+    """sdf_values on the P points already laid out in `ws` (sdf_query_workspace) -> [P, 1] (out: a contiguous float32 view of P values
+    to write into instead, e.g. a slice of a grid)."""
     lib = _lib.lib()
-    sdf = torch.empty(P, 1, device=ws.device)
+    if out is not None and (out.numel() != P or out.dtype != torch.float32 or not out.is_contiguous() or out.device != ws.device):
+        raise RuntimeError("sdf_values_laid_out: out must be a contiguous float32 view of P values on the workspace's device")
+    sdf = torch.empty(P, 1, device=ws.device) if out is None else out
     packed, netp = handle.packed()
     prec = 5 if (fast and handle.precision == 4) else handle.precision
     gptr, gval = (None, 0) if gate is None else (ctypes.c_void_p(gate[0].data_ptr() + 4 * gate[1]), int(gate[2]))
@@ -1161,3 +1164,51 @@ def parse_visibility(lines, n_lines, gt_packed, gt_off, K3, w2c, ckdist, ckview)
                                          float(ckdist), int(ckview), _p(vis_count), _p(checked), _p(n_checked), _p(ws), _stream()),
                "neat_parse_visibility")
     return vis_count[:ecap], checked[:ecap], n_checked
+
+
+# ---- surface mesh (neat_amd/mesh.py): no gradient; extract() reads its two counts once ------------------------------------
+def _axes3(n, b0, b1):
+    n3 = [int(v) for v in n]
+    lo = [float(v) for v in (b0 if hasattr(b0, "__len__") else (b0,) * 3)]
+    hi = [float(v) for v in (b1 if hasattr(b1, "__len__") else (b1,) * 3)]
+    if len(n3) != 3 or len(lo) != 3 or len(hi) != 3:
+        raise ValueError("a grid has three axes: n, b0, b1 of length 3 (or scalar bounds)")
+    return (ctypes.c_int * 3)(*n3), (ctypes.c_double * 3)(*lo), (ctypes.c_double * 3)(*hi), n3
+
+
+def grid_points(x_fm, ldp, first_node, count, n, b0, b1):
+    """The points of `count` consecutive grid nodes from linear node `first_node` into x_fm [3, ldp] (the x rows of an
+    sdf_query_workspace); get_grid_uniform's numpy.linspace per axis (plots.py:318-329), x slowest."""
+    cn, c0, c1, _ = _axes3(n, b0, b1)
+    _lib.check(_lib.lib().neat_grid_points(_p(x_fm), int(ldp), int(first_node), int(count), cn, c0, c1, _stream()), "neat_grid_points")
+
+
+def mesh_extract(grid, b0, b1, level=0.0):
+    """Marching tetrahedra on a float32 device grid [nx, ny, nz] over [b0, b1] -> (verts [nv,3] float32, faces [nf,3] int32)."""
+    if grid.dim() != 3:
+        raise ValueError("mesh_extract: grid [nx, ny, nz]")
+    grid = _f32c(grid.detach())
+    cn, c0, c1, (nx, ny, nz) = _axes3(grid.shape, b0, b1)
+    lib, dev = _lib.lib(), grid.device
+    nbytes = lib.neat_mesh_ws_bytes(nx, ny, nz)
+    if nbytes == 0:
+        raise ValueError("mesh_extract: every axis needs at least 2 nodes and the grid fewer than 2^31 nodes, got %s" % ((nx, ny, nz),))
+    ws = _ws(nbytes, dev)
+    counts = torch.empty(2, device=dev, dtype=torch.int32)
+    _lib.check(lib.neat_mesh_count(_p(grid), nx, ny, nz, float(level), _p(ws), _p(counts), _stream()), "neat_mesh_count")
+    nv, nf = counts.tolist()          # the one read-back: the counts size the outputs
+    if nv < 0 or nf < 0:
+        raise RuntimeError("mesh_extract: more vertices or faces than int32 indexes; extract the grid in parts")
+    verts = torch.empty(nv, 3, device=dev)
+    faces = torch.empty(nf, 3, device=dev, dtype=torch.int32)
+    _lib.check(lib.neat_mesh_emit(_p(grid), nx, ny, nz, c0, c1, float(level), _p(ws), _p(verts) if nv else None, nv,
+                                  _p(faces) if nf else None, nf, _stream()), "neat_mesh_emit")
+    return verts, faces
+
+
+def unit_rows3_(g):
+    """Rows of g [n,3] (contiguous float32, device) scaled to unit length in place."""
+    if g.dim() != 2 or g.shape[1] != 3 or g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+        raise RuntimeError("unit_rows3_: contiguous CUDA float32 [n, 3]")
+    _lib.check(_lib.lib().neat_unit_rows3(_p(g), g.shape[0], _stream()), "neat_unit_rows3")
+    return g

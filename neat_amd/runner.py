@@ -1,8 +1,8 @@
 """Training runner in the shape of the reference's `training/exp_runner.py` + `VolSDFTrainRunner`
 (code/training/volsdf_train.py:66-410): same conf files, same loop (per-iteration re-sampling of the rays and
 ExponentialLR step), same checkpoint layout (`checkpoints/{Model,Optimizer,Scheduler}Parameters/{epoch,latest}.pth` with
-the reference's dict keys), so checkpoints move between the two code bases.  Visualisation, tensorboard, git logging and
-the open3d dumps of the reference runner are out of scope.
+the reference's dict keys), so checkpoints move between the two code bases.  Tensorboard, git logging, the rendered-image plots and
+the open3d dumps of the reference runner are out of scope; the surface mesh of its `do_vis` branch is `--vis_mesh`.
 
     python -m neat_amd.runner --conf /path/to/confs/abc-neat-a.conf --data_root /path/to/data --nepoch 2000
 
@@ -38,7 +38,7 @@ SUBDIRS = ("ModelParameters", "OptimizerParameters", "SchedulerParameters")
 
 class TrainRunner:
     def __init__(self, conf, nepochs, exps_folder="exps", expname="", scan_id=-1, data_root="../data", device="cuda:0",
-                 timestamp=None, precision=None, log_freq=50, rank=0, world=1):
+                 timestamp=None, precision=None, log_freq=50, rank=0, world=1, vis_mesh=False):
         self.conf = conf_mod.parse_file(conf) if isinstance(conf, str) else conf
         self.nepochs = nepochs
         self.device = torch.device(device)
@@ -106,6 +106,10 @@ class TrainRunner:
         self.checkpoint_freq = self.conf.get_int("train.checkpoint_freq", default=100)
         self.start_epoch = 0
         self.log_freq = log_freq
+        # --vis_mesh: plots/surface_{epoch}.ply every train.plot_freq epochs (volsdf_train.py's do_vis branch, which the reference's
+        # runner forces off; off by default here too)
+        self.vis_mesh = vis_mesh
+        self.plot_freq = self.conf.get_int("train.plot_freq", default=100)
 
     def load_checkpoints(self, checkpoints_dir, checkpoint="latest"):
         """Continue from a run of this runner or of the reference's (volsdf_train.py:187-207)."""
@@ -126,12 +130,28 @@ class TrainRunner:
             for name in (str(epoch), "latest"):
                 torch.save({"epoch": epoch, key: sd}, os.path.join(self.checkpoints_path, sub, f"{name}.pth"))
 
+    def write_surface(self, epoch):
+        """`<run>/plots/surface_{epoch}.ply` from the model as it stands (neat_amd.mesh; rank 0, CUDA only) -> the path or None."""
+        if self.rank != 0 or self.device.type != "cuda":
+            return None
+        from . import mesh
+        res = mesh.surface(self.model, plot_conf=mesh.plot_block(self.conf))
+        if res is None:
+            print(f"{self.expname}/{self.timestamp} [{epoch}]: the SDF grid does not cross zero, no surface written", flush=True)
+            return None
+        path = mesh.out_path(os.path.join(self.expdir, self.timestamp), epoch)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        mesh.write_ply(path, res["verts"], res["faces"], res["normals"])
+        return path
+
     def run(self):
         history = []
         epoch = self.start_epoch
         for epoch in range(self.start_epoch, self.nepochs + 1):
             if epoch % self.checkpoint_freq == 0:
                 self.save_checkpoints(epoch)
+            if self.vis_mesh and epoch % self.plot_freq == 0:
+                self.write_surface(epoch)
             if self.batches is None:
                 self.train_dataset.change_sampling_idx(self.num_pixels)
             self.model.train()
@@ -172,6 +192,8 @@ def main():
     ap.add_argument("--checkpoint", default="latest")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks (one per GPU); > 1 re-executes under torch.distributed.run")
     ap.add_argument("--timestamp", default=None)
+    ap.add_argument("--vis_mesh", default=False, action="store_true",
+                    help="write plots/surface_{epoch}.ply (neat_amd.mesh) every train.plot_freq epochs")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import socket
@@ -196,7 +218,7 @@ def main():
     if torch.cuda.is_available():
         torch.cuda.set_device(local)      # the ctypes launches take torch.cuda.current_stream(): it must be this rank's device, whatever the backend
     runner = TrainRunner(args.conf, args.nepoch, args.exps_folder, args.expname, args.scan_id, args.data_root, device=f"cuda:{local}",
-                         timestamp=args.timestamp, precision=args.precision, rank=rank, world=world)
+                         timestamp=args.timestamp, precision=args.precision, rank=rank, world=world, vis_mesh=args.vis_mesh)
     if args.is_continue:
         runner.load_checkpoints(args.is_continue, args.checkpoint)
     runner.run()
