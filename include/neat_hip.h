@@ -461,33 +461,26 @@ int neat_volume_weights(const float* z, const float* sdf, int R, int S, const fl
  * weights once) and the launch count since neat_prof_enable(1). */
 /* A/B switches for benchmarking and for the cross-check tests (tests/test_gpu_parity.py::test_bf16_*_kernels_agree); every
  * setting computes the same result up to summation order.  Returns -1 for an unknown key / value.
- *   0 bf16 layer-kernel point tile (2 = 64 points, 4 = 128)   1 weight gradient: 1 = tr16 streaming kernel, 0 = previous
- *   2 hidden layers: 1 = weight-stationary streaming kernel   3 persistent workgroups of that kernel (default 256)
- *   4 fused primal chain: 1 = weight-stationary               5 its batch in 32-point tiles (0 = auto, 2..4)
+ * Retired keys (closed experiments; their numbers are not reused and return -1): 3, 4, 5, 7, 10, 15, 18, 19, 20, 23.
+ *   0 bf16 layer-kernel point tile (2 = 64 points (default), 4 = 128)
+ *   1 weight gradient: 1 = tr16 streaming kernel (default), 0 = previous
+ *   2 hidden layers: 1 = weight-stationary streaming kernel (default), 0 = previous
  *   6 partial reduction: 2 = one launch, 16-byte loads (default), 0 = group sums + finish, 1 = one 16-wave pass
- *   7 interleave weight gradients with the reverse chain (default 0)
  *   8 same-shaped weight gradients per launch (-1 = by problem size (default), 0 = one layer per launch, 2, 3, 6)
  *   9 point tiles of the persistent streaming kernels: 1 = interleaved over the workgroups (default), 2 = interleaved with an
  *     XCD-contiguous slot order (measured neutral), 0 = one contiguous range each
- *  10 fused primal chain: batches interleaved over the workgroups (default 0)
  *  11 non-temporal accesses, bit mask (default 15): 1 / 2 = aux0 / aux1 fetch of the layer kernels, 4 = weight-gradient operands,
  *     8 = `in` fetch of the layer kernels, 16 = out1 (m_l) store, 32 = out0 store (both stores measured neutral)
  *  12 layer kernels: 1 = 16-byte output stores through v_permlane32_swap (default; measured neutral), 0 = 8-byte stores
  *  13 16-bit builds: the adjoint chain (normals) as one fused launch (default 1), 0 = seed + eight streaming launches
  *  14 16-bit builds: the two heads as fused chains (kernels_heads.hpp): 2 = forward and backward (default), 1 = forward only,
  *     0 = one layer_kernel_ws launch per layer
- *  15 with the fused head backward: 1 = a head's weight gradients right after its backward chain (default: its cotangents are the
- *     last 270 MB written, -0.025 ms per step), 0 = after both chains, the two heads' hidden layers batched together
  *  16 16-bit builds: weight gradients of the SDF layers 1..7 contracted inside the tangent / reverse launches that hold both
  *     operands in LDS (kernels_dw.hpp): 1 = from 49 152 points on (default), 2 = always, 0 = never (separate launches)
- *  17 probe switch of those launches (4 = no partial stores: wrong results)      18 sub-ranges of their gather launch (default 16)
- *  19 16-bit builds: the heads' input layers ([256 feature | <= 64 small] columns) as ONE five-column-block weight-gradient launch
- *     (default 1; 0 = two launches that each read the whole cotangent array)
- *  20 a head's output-layer weight gradient as a fourth problem of its hidden layers' launch (default 1)
+ *  17 probe switch of those launches (default 0; 4 = no partial stores: wrong results)
  *  21 16-bit builds: lin0's weight gradient (K = 39 PE columns) on the one-column-block variant of the streaming kernel: 0 = off,
  *     n = 1..4: on, with n times the point splits (default 1; 2 and 4 measured no faster)
  *  22 with key 16: the feature rows of lin8's weight gradient contracted inside lin8's reverse launch as well (default 1)
- *  23 workgroups (= partials per set) of the launches of key 16, 16..256 (default 256; C4's shape: 192 the same, 128 +7 %)
  *  24 with keys 16 and 22: the chain variables of those launches (tangents of h_2..h_7, cotangents of a_6..a_1) alternate between two
  *     buffers each instead of one array per layer (default 1; results bit-identical, fewer HBM write-backs)
  *  25 with key 16: consecutive layers of the tangent / reverse chains that share an epilogue variant run as ONE launch in which every

@@ -158,7 +158,7 @@ def lib():
             fn.restype, fn.argtypes = res, args
         _lib = l
         # A/B switches from the environment (probe scripts; the defaults are what the tests and the bench run):
-        # NEAT_TUNING="16=0,18=4" -> neat_set_tuning(16, 0), neat_set_tuning(18, 4)
+        # NEAT_TUNING="16=0,21=2" -> neat_set_tuning(16, 0), neat_set_tuning(21, 2)
         applied = []
         for kv in filter(None, os.environ.get("NEAT_TUNING", "").split(",")):
             k, v = kv.split("=")

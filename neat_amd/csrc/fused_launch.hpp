@@ -8,12 +8,10 @@
 
 namespace neat {
 
-// fused SDF primal chain, 4 waves x 64 output rows, 128-point batches.  full: save h_1..h_8, PE, lin8 outputs for backward;
-// otherwise only the clamped sdf (sampler).  nwg persistent workgroups over ntiles 32-point tiles; interleave: batches
-// interleaved over the workgroups instead of one contiguous range each.
-// rows_per_wave: 0 = phase-staggered kernel (sdf_fused_ph_kernel); 64 / 32 = stage-pipelined kernel with four waves (one per
-// SIMD) / eight waves (two per SIMD).
-hipError_t launch_sdf_fused_w64(hipStream_t st, const FusedArgs& a, int ntiles, int nwg, bool full, bool interleave, int rows_per_wave);
+// fused SDF primal chain: the stage-pipelined kernel, eight waves (two per SIMD) x 32 output rows, 128-point batches.  full: save
+// h_1..h_8, PE, lin8 outputs for backward; otherwise only the clamped sdf (sampler).  nwg persistent workgroups over ntiles
+// 32-point tiles, one contiguous range of batches each.
+hipError_t launch_sdf_fused_w64(hipStream_t st, const FusedArgs& a, int ntiles, int nwg, bool full);
 
 // fused adjoint chain (normals): seed + 8 transposed layers in one launch; save: write u_0 .. u_7 (training)
 hipError_t launch_sdf_adjoint_w64(hipStream_t st, const AdjArgs& a, int ntiles, int nwg, bool save);

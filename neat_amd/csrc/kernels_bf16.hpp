@@ -596,453 +596,6 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ s
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused SDF primal chain (ImplicitNetwork.forward, rend_a :78-96, + get_sdf_vals' clamp :131-137):
-// PE-6 -> lin0..lin8 for a tile of 32*PT points in ONE launch.  The activation tile lives in LDS (octet-major
-// bf16) and is updated in place layer after layer; weights stream from L2 through the register ring of mma_rows_h.
-//   values mode : only the clamped sdf leaves the chip (the sampler's 128..640 queries per ray: no HBM round trips)
-//   save mode   : every post-activation h_l, the PE rows and the lin8 output are also written for the backward pass
-// ---------------------------------------------------------------------------------------------
-
-template <int PT, bool VALUES>
-__global__ __launch_bounds__(WG, 2) void sdf_fused_kernel_h(FusedArgs a) {
-  constexpr int BMT = 32 * PT;
-  if (a.gate && *a.gate != a.gate_value) return;
-  extern __shared__ __attribute__((aligned(16))) uint4 ldsq[];        // tile [32][BMT] | PE octets [8][BMT] (K padded to 64)
-  uint4* tile = ldsq;
-  uint4* pe = ldsq + 32 * BMT;
-  u16* tile16 = reinterpret_cast<u16*>(tile);
-  u16* pe16 = reinterpret_cast<u16*>(pe);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int p0 = blockIdx.x * BMT;
-  // ---- positional encoding (embedder.py:12-36) into the PE octets (rows 39..63 zero)
-  for (int idx = tid; idx < 64 * BMT; idx += WG) {
-    const int j = idx / BMT, p = idx % BMT;
-    float v = 0.0f;
-    if (j < 39) {
-      const int c = j < 3 ? j : (j - 3) % 3;
-      const float xc = a.x_fm[(size_t)c * a.ldp + p0 + p];
-      if (j < 3) v = xc;
-      else {
-        const int k = (j - 3) / 6, is_cos = ((j - 3) % 6) >= 3;
-        const float f = (float)(1 << k);
-        v = is_cos ? __cosf(xc * f) : __sinf(xc * f);      // hardware sin/cos: |arg| <= 96, abs error ~1e-6 << bf16 resolution
-      }
-      if (!VALUES && a.save) a.E[(size_t)j * a.ldp + p0 + p] = v;
-    }
-    pe16[((size_t)(j >> 3) * BMT + p) * 8 + (j & 7)] = f2bf(v);
-  }
-  __syncthreads();
-  f32x16 acc[2][PT];
-  const int hi = lane >> 5;
-  // kernarg tables are read through compile-time indices only (a runtime-indexed by-value array would be copied to scratch)
-#define FUSED_SEL(T, field, l, out)                                                                   \
-  T out = a.field[0];                                                                                \
-  _Pragma("unroll") for (int k_ = 1; k_ < 9; ++k_) if ((l) == k_) out = a.field[k_];
-  // ---- hidden layers lin0..lin7
-#pragma unroll 1
-  for (int l = 0; l < 8; ++l) {
-    const int N = (l == 3) ? 217 : 256;
-    const int NT = (N + 31) >> 5;
-    FUSED_SEL(int, KS, l, KS)
-    FUSED_SEL(const uint4*, Wp, l, Wl)
-    FUSED_SEL(const float*, bias, l, bias)
-    FUSED_SEL(u16*, h, l + 1, hsel)
-    const uint4* bl = (l == 0 ? pe : tile) + (size_t)hi * BMT + (lane & 31);
-    const int t0 = wave;
-    const int ntw = (t0 + 4 < NT) ? 2 : 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int q = 0; q < PT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][q][r] = 0.0f;
-    const uint4* wp0 = Wl + (size_t)t0 * KS * 64 + lane;
-    if (ntw == 2) mma_rows_h<2, PT>(acc, wp0, 4 * KS * 64, bl, 0, KS);
-    else mma_rows_h<1, PT>(acc, wp0, 4 * KS * 64, bl, 0, KS);
-    __syncthreads();                                               // everyone has read the tile: update it in place
-    u16* hout = (!VALUES && a.save) ? hsel : nullptr;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (i >= ntw) continue;
-      const int nt = t0 + 4 * i;
-#pragma unroll
-      for (int q = 0; q < PT; ++q) {
-        const int p = q * 32 + (lane & 31);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int n0 = nt * 32 + 8 * g + 4 * hi;
-          if (n0 >= N) continue;
-          float o[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (n0 + e < N) ? softplus100_fast(acc[i][q][4 * g + e] + bias[n0 + e]) : 0.0f;
-          const size_t li = ((size_t)(n0 >> 3) * BMT + p) * 8 + (n0 & 7);
-          if (n0 + 3 < N) {
-            const uint2 pk = make_uint2(pack2(o[0], o[1]), pack2(o[2], o[3]));
-            *reinterpret_cast<uint2*>(tile16 + li) = pk;
-            if (hout && l != 3) *reinterpret_cast<uint2*>(hout + ((size_t)(n0 >> 3) * a.ldp + p0 + p) * 8 + (n0 & 7)) = pk;
-          } else {                                                   // lin3: the quad holding row 216 (rows 217.. belong to the PE copy)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (n0 + e < N) tile16[li + e] = f2bf(o[e]);
-          }
-        }
-      }
-    }
-    if (l == 3) {
-      __syncthreads();
-      // skip connection (rend_a :87-88): rows 217..255 of lin4's input are the 39 PE rows (the 1/sqrt2 is folded into W4)
-      for (int idx = tid; idx < 39 * BMT; idx += WG) {
-        const int j = idx / BMT, p = idx % BMT, row = 217 + j;
-        tile16[((size_t)(row >> 3) * BMT + p) * 8 + (row & 7)] = pe16[((size_t)(j >> 3) * BMT + p) * 8 + (j & 7)];
-      }
-      if (hout) {                                                    // h4 as the unfused consumers expect it: 217 rows + PE[0..6] in the pad
-        __syncthreads();
-        for (int idx = tid; idx < 28 * BMT; idx += WG) {
-          const int o8 = idx / BMT, p = idx % BMT;
-          reinterpret_cast<uint4*>(hout)[(size_t)o8 * a.ldp + p0 + p] = tile[(size_t)o8 * BMT + p];
-        }
-      }
-    }
-    __syncthreads();
-  }
-#undef FUSED_SEL
-  // ---- lin8
-  const uint4* bl = tile + (size_t)hi * BMT + (lane & 31);
-  const int KS = a.KS[8];
-  if (!VALUES) {
-#pragma unroll 1
-    for (int round = 0; round < 2; ++round) {                      // tiles 0..7 = features, tile 8 = [sdf, 31 x padding]
-      const int t0 = round * 8 + wave;
-      const int ntw = (round == 0) ? 2 : (t0 < 9 ? 1 : 0);
-      if (ntw == 0) continue;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int q = 0; q < PT; ++q)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][q][r] = 0.0f;
-      const uint4* wp0 = a.Wp[8] + (size_t)t0 * KS * 64 + lane;
-      if (ntw == 2) mma_rows_h<2, PT>(acc, wp0, 4 * KS * 64, bl, 0, KS);
-      else mma_rows_h<1, PT>(acc, wp0, 4 * KS * 64, bl, 0, KS);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (i >= ntw) continue;
-        const int nt = t0 + 4 * i;
-#pragma unroll
-        for (int q = 0; q < PT; ++q) {
-          const int p = p0 + q * 32 + (lane & 31);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int n0 = nt * 32 + 8 * g + 4 * hi;
-            if (n0 >= 257) continue;
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              int bi = n0 + e + a.bias8_rot; if (bi >= a.bias8_n) bi -= a.bias8_n;
-              o[e] = (n0 + e < 257) ? acc[i][q][4 * g + e] + a.bias[8][bi] : 0.0f;
-            }
-            if (n0 < 256) *reinterpret_cast<uint2*>(a.feat + ((size_t)(n0 >> 3) * a.ldp + p) * 8 + (n0 & 7)) = make_uint2(pack2(o[0], o[1]), pack2(o[2], o[3]));
-            else a.sdfraw[p] = o[0];
-          }
-        }
-      }
-    }
-  } else {
-    // values mode: lin8 restricted to the sdf row (pack with one 32-row tile): split K over the 4 waves
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int q = 0; q < PT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][q][r] = 0.0f;
-    const int per = ((KS / 4 + 3) / 4) * 4;
-    const int sb = wave * per, se = min(KS, sb + per);
-    if (sb < se) mma_rows_h<1, PT>(acc, a.Wp[8] + lane, 0, bl, sb, se);
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(ldsq);                    // [4 waves][PT][64]: only accumulator register 0 of lanes 0..31 matters
-    if (hi == 0) {
-#pragma unroll
-      for (int q = 0; q < PT; ++q) red[(wave * PT + q) * 32 + lane] = acc[0][q][0];
-    }
-    __syncthreads();
-    if (tid < BMT) {
-      const int q = tid >> 5, ln = tid & 31;
-      float s = a.bias[8][0];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) s += red[(w * PT + q) * 32 + ln];
-      const int p = p0 + tid;
-      if (a.radius > 0.0f) {
-        const float x0 = a.x_fm[p], x1 = a.x_fm[(size_t)a.ldp + p], x2 = a.x_fm[(size_t)2 * a.ldp + p];
-        s = fminf(s, a.scale * (a.radius - sqrtf(x0 * x0 + x1 * x1 + x2 * x2)));
-      }
-      if (p < a.P) a.sdf_out[p] = s;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// sdf_fused_ws_kernel: the fused primal chain, weight-stationary.  sdf_fused_kernel_h streams every layer's weights
-// from L2 for each 64-point workgroup (9 x 128 KiB per 64 points, latency bound, ~200 TF/s); here one persistent
-// 8-wave workgroup per CU walks batches of 32*NT points layer by layer:
-//  * wave w owns output rows 32w..32w+31 of every hidden layer and holds that 32 x 256 slice of W_l as 16 A fragments
-//    in VGPRs; the slice of layer l+1 is prefetched into a second register set while layer l computes (lin0's small
-//    slice and the sdf-row fragments of lin8 stay resident for the whole launch);
-//  * activations ping-pong between two LDS buffers [32 octets][points][16 B]: one barrier per layer, no in-place
-//    hazards; biases of all layers sit in LDS;
-//  * save mode streams h_1..h_8, PE and the lin8 outputs to HBM with 8-byte stores straight from the accumulators;
-//    values mode (sampler) writes nothing but the clamped sdf.
-// ---------------------------------------------------------------------------------------------
-constexpr int FWT = 512;
-template <int NT> struct FwsCfg {
-  static constexpr int BP = 32 * NT;
-  static constexpr int XBYTES = 32 * BP * 16;            // one activation buffer
-  static constexpr int PEBYTES = 8 * BP * 16;            // PE octets (K padded to 64); reused for the sdf partial sums
-  static constexpr int BIAS_FLOATS = 9 * 256 + 8;
-  static constexpr int LDS = 2 * XBYTES + PEBYTES + BIAS_FLOATS * 4;
-};
-
-template <int NT, bool VALUES>
-__global__ __launch_bounds__(FWT, 2) void sdf_fused_ws_kernel(FusedArgs a, int ntiles, int nwg) {
-  typedef FwsCfg<NT> C;
-  constexpr int BP = C::BP;
-  if (a.gate && *a.gate != a.gate_value) return;
-  extern __shared__ __attribute__((aligned(16))) unsigned char fws[];
-  unsigned char* XA = fws;
-  unsigned char* XB = fws + C::XBYTES;
-  unsigned char* PE = fws + 2 * C::XBYTES;
-  float* biasl = reinterpret_cast<float*>(fws + 2 * C::XBYTES + C::PEBYTES);     // [l][256]; lin8 in packed row order
-  u16* pe16 = reinterpret_cast<u16*>(PE);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
-  const bool save = !VALUES && a.save;
-
-  // biases -> LDS (lin3 has 217 rows; lin8: packed row n <- bias[(n + rot) mod 257], the sdf row's bias at [8][256])
-  for (int idx = tid; idx < 8 * 256; idx += FWT) {
-    const int l = idx >> 8, n = idx & 255;
-    float v = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) if (l == k && n < (k == 3 ? 217 : 256)) v = a.bias[k][n];
-    biasl[idx] = v * SOFTPLUS_C;             // hidden layers: pre-scaled for softplus100_pk
-  }
-  for (int n = tid; n < 257; n += FWT) {
-    int bi = n + a.bias8_rot; if (bi >= a.bias8_n) bi -= a.bias8_n;
-    biasl[8 * 256 + n] = VALUES ? (n == 0 ? a.bias[8][0] : 0.0f) : a.bias[8][bi];
-  }
-  // ONE register set for the weight slice: all NT point tiles of a layer are multiplied first (NT independent accumulator
-  // chains: a single chain of 16 dependent MFMAs runs at the MFMA latency and exposes every LDS read), then the slice of
-  // the NEXT layer is loaded into the same registers and its L2 latency hides under this layer's epilogue.
-  uint4 ws8[2], wreg[16];
-  {
-    unsigned voff = (unsigned)lane * 16u;
-    asm volatile("" : "+v"(voff));
-#pragma unroll
-    for (int j = 0; j < 2; ++j)          // this wave's two k-steps of the sdf row of lin8 stay resident
-      ws8[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.Wp[8]) + voff + (((VALUES ? 0 : 8) * 16 + 2 * wave + j) * 1024));
-  }
-  auto load_w = [&](const uint4* Wl, int KS, bool on) {
-    // The per-lane offset is laundered through an empty asm: otherwise the fragment addresses of all layers are
-    // loop-invariant, get hoisted out of the batch loop and spilled (2 VGPRs each).  SGPR base + this offset + immediate.
-    unsigned voff = (unsigned)(wave * KS * 64 + lane) * 16u;
-    asm volatile("" : "+v"(voff));
-    const char* base = reinterpret_cast<const char*>(Wl);
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks)
-      if (ks < KS) wreg[ks] = on ? *reinterpret_cast<const uint4*>(base + voff + ks * 1024) : make_uint4(0u, 0u, 0u, 0u);
-  };
-  load_w(a.Wp[0], 4, true);
-
-  // the 32-point tiles are split evenly over the workgroups (tile counts differ by at most one); each workgroup walks its
-  // range in batches of NT tiles, the last batch may be shorter (its missing tiles skip MFMAs, epilogue and stores)
-  // nwg < 0: batches of NT tiles interleaved over the -nwg workgroups (batch b -> workgroup b mod grid) instead of one
-  // contiguous tile range per workgroup
-  const bool inter = nwg < 0;
-  const int ng = inter ? -nwg : nwg;
-  const int t_begin = inter ? (int)blockIdx.x * NT : (int)(((long long)blockIdx.x * ntiles) / ng);
-  const int t_end = inter ? ntiles : (int)(((long long)(blockIdx.x + 1) * ntiles) / ng);
-  const int t_step = inter ? ng * NT : NT;
-  for (int tile0 = t_begin; tile0 < t_end; tile0 += t_step) {
-    const int p0 = tile0 * 32;
-    const int nt = min(NT, t_end - tile0);
-    // ---- positional encoding (embedder.py:12-36) into the PE octets (rows 39..63 zero)
-    for (int idx = tid; idx < 64 * BP; idx += FWT) {
-      const int j = idx / BP, p = idx % BP;
-      float v = 0.0f;
-      if (j < 39 && p < nt * 32) {
-        const int c = j < 3 ? j : (j - 3) % 3;
-        const float xc = a.x_fm[(size_t)c * a.ldp + p0 + p];
-        if (j < 3) v = xc;
-        else {
-          const int k = (j - 3) / 6, is_cos = ((j - 3) % 6) >= 3;
-          const float f = (float)(1 << k);
-          v = is_cos ? __cosf(xc * f) : __sinf(xc * f);
-        }
-        if (save) a.E[(size_t)j * a.ldp + p0 + p] = v;
-      }
-      pe16[((size_t)(j >> 3) * BP + p) * 8 + (j & 7)] = f2bf(v);
-    }
-    __syncthreads();
-
-    // one hidden layer: dst[rows of this wave] = softplus(W src + b), optionally streamed to HBM; then `next` is loaded.
-    // Software pipeline over the point tiles: the 16 MFMAs of tile t are interleaved, k-step by k-step, with the epilogue
-    // of tile t-1 (bias, softplus, pack, LDS + HBM stores: ~190 VALU instructions per tile against 16 x 8 MFMA passes), so
-    // the matrix core and the vector ALU of the SIMD work at the same time instead of one after the other; only two
-    // accumulator tiles are live.  The B fragment of the next k-step is read from LDS one step ahead.
-    auto hidden = [&](int KS, const unsigned char* src, unsigned char* dst, int l, int N, u16* hout, const uint4* next, int nextKS, bool next_on) {
-      const float* bl = biasl + l * 256;
-      const unsigned char* bp = src + ((size_t)hi * BP + (lane & 31)) * 16;
-      const bool rows_live = wave * 32 < N;
-      f32x16 acc[2];
-      auto epi_quad = [&](const f32x16& ac, int t, int g) {
-        const int n0 = wave * 32 + 8 * g + 4 * hi;
-        if (!rows_live || n0 >= N) return;
-        const int pl = t * 32 + (lane & 31);
-        const float4 bb = *reinterpret_cast<const float4*>(bl + n0);
-        const v2f_t o01 = softplus100_pk(v2f_t{ac[4 * g], ac[4 * g + 1]}, v2f_t{bb.x, bb.y});
-        const v2f_t o23 = softplus100_pk(v2f_t{ac[4 * g + 2], ac[4 * g + 3]}, v2f_t{bb.z, bb.w});
-        float o[4] = {o01.x, o01.y, o23.x, o23.y};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (n0 + e >= N) o[e] = 0.0f;
-        u16* lp = reinterpret_cast<u16*>(dst) + ((n0 >> 3) * BP + pl) * 8 + (n0 & 7);
-        if (n0 + 3 < N) {
-          const uint2 pk = make_uint2(pack2(o[0], o[1]), pack2(o[2], o[3]));
-          *reinterpret_cast<uint2*>(lp) = pk;
-          if (hout) {                                    // 32-bit byte offset (arrays < 4 GiB) off the layer's base pointer
-            const unsigned go = ((unsigned)(n0 >> 3) * (unsigned)a.ldp + (unsigned)(p0 + pl)) * 16u + (unsigned)(n0 & 7) * 2u;
-            *reinterpret_cast<uint2*>(reinterpret_cast<char*>(hout) + go) = pk;
-          }
-        } else {                                         // lin3: the quad holding row 216 (rows 217.. receive the PE copy)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) if (n0 + e < N) lp[e] = f2bf(o[e]);
-        }
-      };
-#pragma unroll
-      for (int t = 0; t <= NT; ++t) {
-        const bool mma_on = t < NT && t < nt, epi_on = t >= 1 && t - 1 < nt;
-        if (t == NT) {                                   // every MFMA of this layer has been issued: the next slice may land
-          __builtin_amdgcn_sched_barrier(0);
-          if (next) load_w(next, nextKS, next_on);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        f32x16& am = acc[t & 1];
-        const f32x16& ae = acc[(t + 1) & 1];
-        if (mma_on) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) am[r] = 0.0f;
-        }
-        uint4 bv = make_uint4(0u, 0u, 0u, 0u);
-        if (mma_on) bv = *reinterpret_cast<const uint4*>(bp + t * 32 * 16);
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-          if (mma_on && ks < KS) {
-            const uint4 cur = bv;
-            if (ks + 1 < KS) bv = *reinterpret_cast<const uint4*>(bp + (size_t)(ks + 1) * 2 * BP * 16 + t * 32 * 16);
-            am = NEAT_MFMA16(*reinterpret_cast<const bf16x8*>(&wreg[ks]), *reinterpret_cast<const bf16x8*>(&cur), am, 0, 0, 0);
-          }
-          if (epi_on && (ks & 3) == 3) epi_quad(ae, t - 1, ks >> 2);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      __syncthreads();
-    };
-
-    hidden(4, PE, XA, 0, 256, save ? a.h[1] : nullptr, a.Wp[1], 16, true);
-    hidden(16, XA, XB, 1, 256, save ? a.h[2] : nullptr, a.Wp[2], 16, true);
-    hidden(16, XB, XA, 2, 256, save ? a.h[3] : nullptr, a.Wp[3], 16, wave * 32 < 217);
-    hidden(16, XA, XB, 3, 217, nullptr, a.Wp[4], 16, true);
-    // skip connection (rend_a :87-88): rows 217..255 of lin4's input are the 39 PE rows (1/sqrt2 folded into W4)
-    {
-      u16* xb16 = reinterpret_cast<u16*>(XB);
-      for (int idx = tid; idx < 39 * BP; idx += FWT) {
-        const int j = idx / BP, p = idx % BP, row = 217 + j;
-        xb16[((size_t)(row >> 3) * BP + p) * 8 + (row & 7)] = pe16[((size_t)(j >> 3) * BP + p) * 8 + (j & 7)];
-      }
-      __syncthreads();
-      if (save) {                                          // h4 as the unfused consumers expect it: 217 rows + PE[0..6] in the pad
-        for (int idx = tid; idx < 28 * nt * 32; idx += FWT) {
-          const int o8 = idx / (nt * 32), p = idx % (nt * 32);
-          reinterpret_cast<uint4*>(a.h[4])[(size_t)o8 * a.ldp + p0 + p] = reinterpret_cast<const uint4*>(XB)[(size_t)o8 * BP + p];
-        }
-      }
-    }
-    hidden(16, XB, XA, 4, 256, save ? a.h[5] : nullptr, a.Wp[5], 16, true);
-    hidden(16, XA, XB, 5, 256, save ? a.h[6] : nullptr, a.Wp[6], 16, true);
-    hidden(16, XB, XA, 6, 256, save ? a.h[7] : nullptr, a.Wp[7], 16, true);
-    hidden(16, XA, XB, 7, 256, save ? a.h[8] : nullptr, VALUES ? a.Wp[0] : a.Wp[8], VALUES ? 4 : 16, true);
-
-    // ---- lin8: 256 feature rows (save mode) + the sdf row, split over the waves' k-steps and reduced through LDS
-    float* red = reinterpret_cast<float*>(PE);             // [8 waves][BP]
-    {
-      const unsigned char* bp = XB + ((size_t)hi * BP + (lane & 31)) * 16;
-      f32x16 accs[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accs[t][r] = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          if (t >= nt) break;
-          const uint4 bv = *reinterpret_cast<const uint4*>(bp + (size_t)(2 * wave + j) * 2 * BP * 16 + t * 32 * 16);
-          accs[t] = NEAT_MFMA16(*reinterpret_cast<const bf16x8*>(&ws8[j]), *reinterpret_cast<const bf16x8*>(&bv), accs[t], 0, 0, 0);
-        }
-      if (hi == 0) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) red[wave * BP + t * 32 + lane] = accs[t][0];
-      }
-      if (!VALUES) {
-        f32x16 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-#pragma unroll
-          for (int t = 0; t < NT; ++t) {
-            if (t >= nt) break;
-            const uint4 bv = *reinterpret_cast<const uint4*>(bp + (size_t)ks * 2 * BP * 16 + t * 32 * 16);
-            acc[t] = NEAT_MFMA16(*reinterpret_cast<const bf16x8*>(&wreg[ks]), *reinterpret_cast<const bf16x8*>(&bv), acc[t], 0, 0, 0);
-          }
-          if ((ks & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (tile0 + t_step < t_end) load_w(a.Wp[0], 4, true);  // next batch's lin0 slice
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          if (t >= nt) break;
-          const int pl = t * 32 + (lane & 31);
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int n0 = wave * 32 + 8 * g + 4 * hi;
-            const float4 bb = *reinterpret_cast<const float4*>(biasl + 8 * 256 + n0);
-            const unsigned go = ((unsigned)(n0 >> 3) * (unsigned)a.ldp + (unsigned)(p0 + pl)) * 16u + (unsigned)(n0 & 7) * 2u;
-            *reinterpret_cast<uint2*>(reinterpret_cast<char*>(a.feat) + go) =
-                make_uint2(pack2(acc[t][4 * g] + bb.x, acc[t][4 * g + 1] + bb.y), pack2(acc[t][4 * g + 2] + bb.z, acc[t][4 * g + 3] + bb.w));
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (tid < nt * 32) {
-      float sv = biasl[8 * 256 + (VALUES ? 0 : 256)];
-#pragma unroll
-      for (int w = 0; w < 8; ++w) sv += red[w * BP + tid];
-      const int p = p0 + tid;
-      if (VALUES) {
-        if (a.radius > 0.0f) {
-          const float x0 = a.x_fm[p], x1 = a.x_fm[(size_t)a.ldp + p], x2 = a.x_fm[(size_t)2 * a.ldp + p];
-          sv = fminf(sv, a.scale * (a.radius - sqrtf(x0 * x0 + x1 * x1 + x2 * x2)));
-        }
-        if (p < a.P) a.sdf_out[p] = sv;
-      } else {
-        a.sdfraw[p] = sv;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // bf16 weight gradient: dW[n][k] = sum_p A[n][p] B[k][p], fp32 partial tiles as in the fp32 build
 // ---------------------------------------------------------------------------------------------
 struct WgradPairH {

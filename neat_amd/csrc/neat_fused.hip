@@ -8,24 +8,13 @@
 
 namespace neat {
 
-template <int RT> hipError_t launch_rt(hipStream_t st, const FusedArgs& a, int ntiles, int nwg, bool full, bool interleave) {
-  typedef F6Cfg<4, RT> C;
-  NEAT_TRY((lds_limit<&sdf_fused_w64_kernel<4, false, RT>, &sdf_fused_w64_kernel<4, true, RT>>(C::LDS)));
-  if (full) hipLaunchKernelGGL((sdf_fused_w64_kernel<4, false, RT>), dim3(nwg), dim3(C::THREADS), C::LDS, st, a, ntiles, interleave ? -nwg : nwg);
-  else hipLaunchKernelGGL((sdf_fused_w64_kernel<4, true, RT>), dim3(nwg), dim3(C::THREADS), C::LDS, st, a, ntiles, interleave ? -nwg : nwg);
+hipError_t launch_sdf_fused_w64(hipStream_t st, const FusedArgs& a, int ntiles, int nwg, bool full) {
+  typedef F6Cfg<4, 1> C;
+  // (the kernel's last argument: a negative workgroup count would interleave the batches over the workgroups; not used)
+  NEAT_TRY((lds_limit<&sdf_fused_w64_kernel<4, false, 1>, &sdf_fused_w64_kernel<4, true, 1>>(C::LDS)));
+  if (full) hipLaunchKernelGGL((sdf_fused_w64_kernel<4, false, 1>), dim3(nwg), dim3(C::THREADS), C::LDS, st, a, ntiles, nwg);
+  else hipLaunchKernelGGL((sdf_fused_w64_kernel<4, true, 1>), dim3(nwg), dim3(C::THREADS), C::LDS, st, a, ntiles, nwg);
   return hipGetLastError();
-}
-
-hipError_t launch_ph(hipStream_t st, const FusedArgs& a, int ntiles, int nwg, bool full, bool interleave) {
-  NEAT_TRY((lds_limit<&sdf_fused_ph_kernel<false>, &sdf_fused_ph_kernel<true>>(PhCfg::LDS)));
-  if (full) hipLaunchKernelGGL((sdf_fused_ph_kernel<false>), dim3(nwg), dim3(PHT), PhCfg::LDS, st, a, ntiles, interleave ? -nwg : nwg);
-  else hipLaunchKernelGGL((sdf_fused_ph_kernel<true>), dim3(nwg), dim3(PHT), PhCfg::LDS, st, a, ntiles, interleave ? -nwg : nwg);
-  return hipGetLastError();
-}
-
-hipError_t launch_sdf_fused_w64(hipStream_t st, const FusedArgs& a, int ntiles, int nwg, bool full, bool interleave, int rows_per_wave) {
-  if (rows_per_wave == 0) return launch_ph(st, a, ntiles, nwg, full, interleave);
-  return rows_per_wave == 64 ? launch_rt<2>(st, a, ntiles, nwg, full, interleave) : launch_rt<1>(st, a, ntiles, nwg, full, interleave);
 }
 
 hipError_t launch_sdf_adjoint_w64(hipStream_t st, const AdjArgs& a, int ntiles, int nwg, bool save) {

@@ -201,53 +201,28 @@ inline int wgrad_batch_size(int ldp) {
   if (g_wgrad_batch >= 0) return g_wgrad_batch;
   return ldp <= 200000 ? 3 : (ldp <= 400000 ? 2 : 0);
 }
-int g_wgrad_interleave = 0; // 1: launch each SDF layer's weight gradient right after the reverse step that produced its cotangent (Infinity-Cache reuse; measured neutral)
 int g_wreduce_direct = 2;   // bf16 weight-gradient reduction: 2 = one launch per layer / batch with 16-byte loads (wreduce_direct_kernel), 0 = group
                             // sums + finish (two launches, stage buffer), 1 = one 16-wave pass with 4-byte loads (slowest)
 int g_head_chain = 2;       // 16-bit builds: the heads as fused chains (kernels_heads.hpp): 2 = forward and backward, 1 = forward only, 0 = per-layer
                             // launches of layer_kernel_ws (tuning key 14)
-int g_head_wgrad_order = 1; // fused head backward: a head's weight gradients right after its backward chain (tuning key 15; 0 = after both chains, hidden layers of the two heads batched together)
 int g_fused_adj = 1;        // bf16 build: adjoint chain (normals) as one fused launch (sdf_adjoint_w64_kernel); 0 = seed + eight streaming EPI_REV launches (tuning key 13)
-int g_fused_ws = 3;         // fused primal chain: 4 = phase-staggered kernel (sdf_fused_ph_kernel; measured slower: a matrix wave and a
-                            // vector wave on one SIMD do not overlap on this machine, scripts/probes/probe_roles.hip), 3 / 2 = stage-pipelined kernel of kernels_fused.hpp with 8 waves x 32 rows / 4 waves x 64 rows,
-                            // 1 = first weight-stationary kernel (8 waves x 32 rows), 0 = sdf_fused_kernel_h
-int g_fused_nt = 0;         // its batch: 4 = 128 points, 2 = 64 points, 0 = whichever balances the CUs better
 int g_layer_ws = 1;         // hidden 256x256 bf16 layers: 1 = weight-stationary streaming kernel, 0 = layer_kernel_h
-int g_ws_grid = 256;        // persistent workgroups of layer_kernel_ws (one per CU)
+constexpr int WS_GRID = 256;        // persistent workgroups of layer_kernel_ws and of the fused chains (one per CU; the tests' comments call it g_ws_grid)
 constexpr int DW_MAXGRID = 256;     // workgroup partials the workspace holds per (layer, pair)
-int g_dw_grid = DW_MAXGRID;  // workgroups (= partials per set) of the launches that contract weight gradients on chip (tuning key 23); 0 = balanced (dw_grid)
 inline int dw_slots(int ldp) {          // workgroup partials the workspace holds per (layer, pair): what dw_grid() can reach at this size
   const int nt = ldp / WSP;
   return nt < DW_MAXGRID ? (nt > 0 ? nt : 1) : DW_MAXGRID;
 }
-inline int dw_grid(int ldp) {
-  int g = g_ws_grid < DW_MAXGRID ? g_ws_grid : DW_MAXGRID;
+inline int dw_grid(int ldp) {           // workgroups (= partials per set) of the launches that contract weight gradients on chip
   const int nt = ldp / WSP;
-  if (g_dw_grid > 0) g = g < g_dw_grid ? g : g_dw_grid;
-  else if (nt > g) {
-    // key 23 = 0 (round 6, measured, NOT the default): the persistent workgroups walk ceil(nt / g) tiles, so 4160 tiles over 256 workgroups cost
-    // 17 rounds for 16.25 of work; this takes the grid in [208, 256] (multiples of 8) that leaves the fewest idle tile slots -- 208 at C2 (20 tiles
-    // each) and at C4's rank shape (10 each), with 19 % fewer partials for the gather.  Same-box A/B, two passes, 256 vs balanced: C2 2.721 / 2.709
-    // vs 2.726 / 2.718 ms, C4 rank 1.764 / 1.774 vs 1.761 / 1.760, real step 3.350 / 3.378 vs 3.403 / 3.350, C3 4.954 / 4.995 vs 5.015 / 5.005:
-    // what the balance wins the 48 idle compute units lose in bandwidth.  (160 workgroups: +4 % on C2, 128: +12 %.)
-    int best = g, waste = ((nt + g - 1) / g) * g - nt;
-    for (int c = g - 8; c >= 208; c -= 8) {
-      const int w = ((nt + c - 1) / c) * c - nt;
-      if (w < waste) { waste = w; best = c; }
-    }
-    g = best;
-  }
-  return nt < g ? nt : g;
+  return nt < DW_MAXGRID ? nt : DW_MAXGRID;
 }
 int g_ws_aux_nt = 15;       // non-temporal accesses (tuning key 11): bit 0 / 1 = fetch of aux0 / aux1 of the streaming layer kernels, bit 2 =
                             // weight-gradient operands, bit 3 = `in` of the layer kernels, bit 4 = store of out1 (m_l)
 int g_ws_wide_store = 1;    // streaming layer kernels: 16-byte output stores (tuning key 12)
 const int* g_gate = nullptr; int g_gate_value = 0;      // set around one neat_sdf_forward call by neat_sdf_values_gated
-int g_fused_interleave = 0; // fused primal chain: batches interleaved over the workgroups (tuning key 10)
 int g_ws_interleave = 1;    // 1: tiles interleaved over the workgroups instead of one contiguous range each
 int g_wgrad_narrow = 1;     // 16-bit builds: lin0's weight gradient (K = 39) on the one-column-block variant of wgrad_kernel_h3 (tuning key 21)
-int g_wgrad_k320 = 1;       // 16-bit builds: the heads' input layers (K = 256 + <= 64) as one five-column-block weight-gradient launch (tuning key 19)
-int g_head_l4_batched = 1;  // a head's output-layer weight gradient as a fourth problem of its hidden layers' launch (tuning key 20)
 int g_dw_ablate = 0;        // probe runs (tuning key 17): see LayerArgsDW::ablate
 int g_dw_fused = 1;         // 16-bit builds: weight gradients of the SDF layers 1..7 accumulated inside the tangent / reverse launches
                             // (kernels_dw.hpp; tuning key 16): 1 = where it pays (>= DW_MIN_POINTS points: the partials and their gather cost
@@ -259,7 +234,7 @@ int g_dw_lin8 = 1;          // with key 16: lin8's feature-row gradient (featc x
 int g_chain_pp = 1;         // with key 16: the chain variables of the tangent / reverse launches (vhat_2..7, a^_6..1) ping-pong between two buffers each
                             // instead of one array per layer: since the weight gradients are contracted in the launch that holds them no later
                             // kernel reads them, and a line rewritten while it is still in the Infinity Cache never costs an HBM write (tuning key 24)
-int g_dw_nsub = 16;         // sub-ranges of workgroup partials summed by dw_gather_kernel (= fp32 splits per layer seen by the finish; tuning key 18)
+constexpr int DW_NSUB = 16; // sub-ranges of workgroup partials summed by dw_gather_kernel (= fp32 splits per layer seen by the finish)
 int g_dw_segments = 1;      // with key 16: consecutive layers of a chain that share an epilogue variant run as ONE launch with a per-workgroup layer loop
                             // (tangent 1-2 | 3 | 4-7, reverse 8 | 7-5 | 4 | 3-1: 15 launches -> 7; tuning key 25)
 template <int EPI, bool FULL> hipError_t launch_layer_wsdw(hipStream_t st, const LayerArgsDW* d0, int n = 1) {
@@ -284,13 +259,13 @@ template <int EPI, int KS = 16, bool OUTF = false> hipError_t launch_layer_ws(hi
   NEAT_TRY((lds_limit<&layer_kernel_ws<EPI, KS, OUTF>>(WsCfg<EPI, KS>::LDS)));
   LayerArgsWS a = a0;
   a.ntiles = a.ldp / WSP;
-  a.per_wg = (a.ntiles + g_ws_grid - 1) / g_ws_grid;
+  a.per_wg = (a.ntiles + WS_GRID - 1) / WS_GRID;
   int grid = (a.ntiles + a.per_wg - 1) / a.per_wg;
   a.tile_stride = 1;
   a.wide_store = g_ws_wide_store;
   a.aux_nt = (g_ws_aux_nt & 3) | ((g_ws_aux_nt >> 1) & 28);      // key bits 3 / 4 / 5 -> kernel bits 2 / 3 / 4
   a.xcd_major = g_ws_interleave == 2;
-  if (g_ws_interleave) { grid = a.ntiles < g_ws_grid ? a.ntiles : g_ws_grid; a.tile_stride = grid; }
+  if (g_ws_interleave) { grid = a.ntiles < WS_GRID ? a.ntiles : WS_GRID; a.tile_stride = grid; }
   hipLaunchKernelGGL((layer_kernel_ws<EPI, KS, OUTF>), dim3(grid), dim3(WST), (WsCfg<EPI, KS>::LDS), st, a);
   return hipGetLastError();
 }
@@ -629,53 +604,19 @@ hipError_t sdf_primal(const Ctx& c, const SdfWs& w, bool full, float radius = 0.
       for (int l = 0; l < 8; ++l) fl3 += 2.0 * kO[l] * kI[l] * (double)c.P;
       fl3 += 2.0 * (full ? 257 : 1) * 256 * (double)c.P;
       ProfSlot* ps3 = prof_begin(c.st, 2, fl3, (double)c.P * (12.0 + 39 * 4.0 + (full ? 2.0 * (7 * 256 + 224 + 256) * 2.0 + 4.0 : 4.0)) + 4.0 * 589000.0);
-      hipError_t e3 = launch_sdf_chain_x3(c.st, a, c.ldp / X3_BATCH, g_ws_grid, full);
+      hipError_t e3 = launch_sdf_chain_x3(c.st, a, c.ldp / X3_BATCH, WS_GRID, full);
       prof_end(c.st, ps3);
       return e3;
     }
-    constexpr int PT = 2;
-    const size_t lds = (size_t)(32 + 8) * (32 * PT) * 16;
     double fl = 0.0;
     for (int l = 0; l < 8; ++l) fl += 2.0 * kO[l] * kI[l] * (double)c.P;
     fl += 2.0 * (full ? 257 : 1) * 256 * (double)c.P;
     const double fbytes = (double)c.P * (12.0 + (full ? (39 * 4.0 + (7 * 256 + 224 + 256) * 2.0 + 4.0) : 4.0)) + 2.0 * 589000.0;
     ProfSlot* ps = prof_begin(c.st, 2, fl, fbytes);
-    if (g_fused_ws) {
-      // weight-stationary persistent kernel: batches of 128 points (64 when that balances the CUs better)
-      NEAT_TRY((lds_limit<&sdf_fused_ws_kernel<4, false>, &sdf_fused_ws_kernel<4, true>>(FwsCfg<4>::LDS)));
-      NEAT_TRY((lds_limit<&sdf_fused_ws_kernel<3, false>, &sdf_fused_ws_kernel<3, true>>(FwsCfg<3>::LDS)));
-      NEAT_TRY((lds_limit<&sdf_fused_ws_kernel<2, false>, &sdf_fused_ws_kernel<2, true>>(FwsCfg<2>::LDS)));
-      const int ntiles = c.ldp / 32;                 // ldp is a multiple of 64
-      const int nwg = ntiles < g_ws_grid ? ntiles : g_ws_grid;
-      if (g_fused_ws >= 2) {
-        hipError_t e6 = launch_sdf_fused_w64(c.st, a, ntiles, nwg, full, g_fused_interleave != 0, g_fused_ws == 2 ? 64 : (g_fused_ws == 3 ? 32 : 0));
-        prof_end(c.st, ps);
-        return e6;
-      }
-      auto go = [&](auto kern, int BP, int lds_bytes) -> hipError_t {
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(FWT), lds_bytes, c.st, a, ntiles, g_fused_interleave ? -nwg : nwg);
-        return hipGetLastError();
-      };
-      // batch = up to 32*NT points: larger batches re-read the weights from L2 less often.  The tiles are split evenly over
-      // the workgroups; the busiest one walks ceil(ntiles / nwg) tiles as full batches + one shorter batch
-      auto cost = [&](int BP) {
-        const int tiles = (ntiles + nwg - 1) / nwg, nt = BP / 32, rem = tiles % nt;
-        return (tiles / nt) * (BP + 48.0) + (rem ? rem * 32 + 48.0 : 0.0);     // per-point work + per-batch weight streaming, in point units
-      };
-      int nt_sel = g_fused_nt;
-      // (NT = 4 has fewer batches still, but its save-mode variant spills registers and measures slower: tuning key 5 only)
-      if (nt_sel == 0) nt_sel = cost(96) < cost(64) ? 3 : 2;
-      hipError_t e;
-      if (nt_sel == 4) e = full ? go(&sdf_fused_ws_kernel<4, false>, 128, FwsCfg<4>::LDS) : go(&sdf_fused_ws_kernel<4, true>, 128, FwsCfg<4>::LDS);
-      else if (nt_sel == 3) e = full ? go(&sdf_fused_ws_kernel<3, false>, 96, FwsCfg<3>::LDS) : go(&sdf_fused_ws_kernel<3, true>, 96, FwsCfg<3>::LDS);
-      else e = full ? go(&sdf_fused_ws_kernel<2, false>, 64, FwsCfg<2>::LDS) : go(&sdf_fused_ws_kernel<2, true>, 64, FwsCfg<2>::LDS);
-      prof_end(c.st, ps);
-      return e;
-    }
-    if (full) hipLaunchKernelGGL((sdf_fused_kernel_h<PT, false>), dim3(c.ldp / (32 * PT)), dim3(WG), lds, c.st, a);
-    else hipLaunchKernelGGL((sdf_fused_kernel_h<PT, true>), dim3(c.ldp / (32 * PT)), dim3(WG), lds, c.st, a);
+    const int ntiles = c.ldp / 32;                 // ldp is a multiple of 64
+    hipError_t e6 = launch_sdf_fused_w64(c.st, a, ntiles, ntiles < WS_GRID ? ntiles : WS_GRID, full);
     prof_end(c.st, ps);
-    return hipGetLastError();
+    return e6;
   }
   hipLaunchKernelGGL(posenc6_kernel, grid1(c.ldp), dim3(256), 0, c.st, w.x, c.ldp, w.E);
   hipError_t e;
@@ -705,14 +646,14 @@ hipError_t sdf_adjoint(const Ctx& c, const SdfWs& w, bool save = true) {
     for (int l = 1; l <= 8; ++l) a.h[l] = reinterpret_cast<const u16*>(w.h[l].p);
     a.w8 = c.net->v[8]; a.rs8 = c.rowscale(8); a.es = w.es; a.e0 = w.e0;
     const int ntiles = c.ldp / 32;
-    const int nwg = ntiles < g_ws_grid ? ntiles : g_ws_grid;
+    const int nwg = ntiles < WS_GRID ? ntiles : WS_GRID;
     double fl = 0.0;
     for (int l = 0; l < 8; ++l) fl += 2.0 * kO[l] * kI[l] * (double)c.P;
     if (c.hx3) {
       for (int l = 0; l < 8; ++l) a.Wlo[l] = reinterpret_cast<const uint4*>(c.packed + L.d[L.tr_lo[l]].offset);
       for (int l = 1; l <= 8; ++l) a.hlo[l] = reinterpret_cast<const u16*>(w.hlo[l].p);
       ProfSlot* ps3 = prof_begin(c.st, 3, fl, (double)c.P * (2 * 8 * 512.0 + (save ? 8 * 512.0 : 0.0) + 2 * 39 * 4.0) + 4.0 * 589000.0);
-      hipError_t e3 = launch_sdf_adjoint_x3(c.st, a, c.ldp / X3_BATCH, g_ws_grid, save);
+      hipError_t e3 = launch_sdf_adjoint_x3(c.st, a, c.ldp / X3_BATCH, WS_GRID, save);
       prof_end(c.st, ps3);
       return e3;
     }
@@ -906,9 +847,9 @@ hipError_t wgrad(const Ctx& c, const SdfWs& w, int layer_id, const WPair* pairs_
            s.rowsB[0] == pairs_in[0].rowsB[0] && s.rowsB[1] == pairs_in[0].rowsB[1];
     }
     const int r0 = pairs_in[0].rowsB[0], r1 = pairs_in[0].rowsB[1];
-    // [256 | r1 <= 64 rows] (the heads' input layers): ONE launch of the five-column-block variant (g_wgrad_k320, tuning key 19) -- two
+    // [256 | r1 <= 64 rows] (the heads' input layers): ONE launch of the five-column-block variant -- two
     // launches, [256] and [r1] into disjoint partial columns, each read the whole A operand
-    const bool wide = h3 && g_wgrad_k320 && K > 256 && K <= 320 && r0 == 256 && r1 > 0 && r1 <= 64;
+    const bool wide = h3 && K > 256 && K <= 320 && r0 == 256 && r1 > 0 && r1 <= 64;
     const bool two = K > 256 && !wide;
     if (two && (r0 != 256 || r1 == 0 || r1 > 256)) h3 = false;
     const bool narrow = h3 && g_wgrad_narrow && K <= 64 && r1 == 0;      // lin0: one 32-column block per wave (tuning key 21)
@@ -994,7 +935,7 @@ struct DwSplits {
   static constexpr int K = 256, Kld2 = (K + 1 + 7) / 8 * 8;
   int splits, xchunk, xn;
   size_t region, region8;
-  DwSplits(int P, int ldp) : splits(g_dw_nsub), xchunk(((ldp + DW8_XBLOCKS - 1) / DW8_XBLOCKS + 31) / 32 * 32), xn((P + xchunk - 1) / xchunk),
+  DwSplits(int P, int ldp) : splits(DW_NSUB), xchunk(((ldp + DW8_XBLOCKS - 1) / DW8_XBLOCKS + 31) / 32 * 32), xn((P + xchunk - 1) / xchunk),
                              region((size_t)256 * splits * Kld2), region8((size_t)257 * splits * Kld2) {}
   size_t row_stride() const { return (size_t)splits * Kld2; }
   float* out(const SdfWs& w, int l) const { return w.partial + (size_t)(l - 1) * region; }
@@ -1126,9 +1067,7 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
   else if (g_layer_ws) e = layer_ws(c, L.tr[8], EPI_BWD8, w.featc, 256, w.m[7], w.h[8], w.m[7], w.abar8, c.net->v[8], c.rowscale(8));
   else e = layer(c, L.tr[8], EPI_BWD, in(w.featc, 256), in(F(w.abar8), 1), nullptr, 256, w.m[7], Arr{}, 1 << 30, w.h[8], w.m[7]);
   if (e != hipSuccess) return e;
-  // weight gradients: dW_l = a^_l in_l^T + u_l vhat_l^T  (+ bias column).  The gradient of layer l is launched right
-  // after the reverse step that produced a^_l (g_wgrad_interleave): a^_l is then read twice (weight gradient, next reverse
-  // step) while it is still in the 256 MB Infinity Cache instead of after all eight reverse steps.
+  // weight gradients: dW_l = a^_l in_l^T + u_l vhat_l^T  (+ bias column), launched after all eight reverse steps
   const bool oct = oct_operands(c);
   auto wgrad_layer = [&](int l) -> hipError_t {
     if (!gr->dv[l]) return hipSuccess;
@@ -1159,10 +1098,7 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
     }
     return wgrad(c, w, l, pr, 2, kO[l], gr);
   };
-  const bool inter = g_wgrad_interleave != 0 && !dw;
-  if (inter && (e = wgrad_layer(8)) != hipSuccess) return e;
   for (int l = 7; l >= 1; --l) {
-    if (inter && (e = wgrad_layer(l)) != hipSuccess) return e;
     const int N = l == 4 ? 217 : kI[l];
     if (dw) {
       LayerArgsDW d{};
@@ -1184,10 +1120,9 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
     }
     if ((e = layer(c, L.tr[l], EPI_BWD, in(w.m[l], kO[l]), NOIN, nullptr, N, w.m[l - 1], Arr{}, 1 << 30, w.h[l], w.m[l - 1])) != hipSuccess) return e;
   }
-  if (inter) return wgrad_layer(0);
   bool done[9] = {};
   if (dw) {
-    // one gather launch: 7 layers (tangent + reverse partial sets each) x g_dw_nsub sub-ranges of workgroups -> g_dw_nsub fp32 splits per layer in the partial-tile format;
+    // one gather launch: 7 layers (tangent + reverse partial sets each) x DW_NSUB sub-ranges of workgroups -> DW_NSUB fp32 splits per layer in the partial-tile format;
     // then the weight-norm finish of the seven layers in one launch
     // lin8 (dw8): packed rows 0..255 = the feature rows (one partial set, reverse launch only), packed row 256 = the sdf row: cotangent abar8
     // row 0 against h8, plus the plain row sums of vh8 (second-order part, the adjoint seed being 1), from rowdot_kernel's block partials
@@ -1211,7 +1146,7 @@ hipError_t sdf_backward_chains(const Ctx& c, const SdfWs& w, const neat_net_grad
     }
     // (accounted with the weight-gradient class: no flops, the partials read once + the fp32 splits written and read once)
     ProfSlot* psg = prof_begin(c.st, 1, 0.0, (14.0 + (dw8 ? 1.0 : 0.0)) * dwg * DW_WG_UINT4 * 16.0 + 2.0 * njobs * (double)ds.region * 4.0);
-    hipLaunchKernelGGL(dw_gather_kernel, dim3(DW_WG_UINT4 / 256, g_dw_nsub, njobs), dim3(256), 0, c.st, ga);
+    hipLaunchKernelGGL(dw_gather_kernel, dim3(DW_WG_UINT4 / 256, DW_NSUB, njobs), dim3(256), 0, c.st, ga);
     dbg_sync(c.st, "dw gather", 0, 0, 0);
     hipLaunchKernelGGL(wreduce_wnorm_batch_kernel, dim3(dw8 ? 257 : 256, njobs), dim3(WG), 0, c.st, wb);
     prof_end(c.st, psg);
@@ -1292,7 +1227,7 @@ hipError_t heads_forward(const Ctx& c, const HeadWs& h, Arr feat, Arr featlo = A
       double fl3 = 0.0;
       for (int l = 0; l < 5; ++l) fl3 += 2.0 * kO[base + l] * kI[base + l] * (double)c.P;
       ProfSlot* ps3 = prof_begin(c.st, 4, fl3, (double)c.P * (2 * 512.0 + a.srows * 4.0 + (save ? 4 * 512.0 : 0.0) + (head ? 24.0 : 12.0)) + 4.0 * 540000.0);
-      e = launch_head_chain_x3(c.st, a, head, c.ldp / X3_BATCH, g_ws_grid, save);
+      e = launch_head_chain_x3(c.st, a, head, c.ldp / X3_BATCH, WS_GRID, save);
       prof_end(c.st, ps3);
       if (e != hipSuccess) return e;
     }
@@ -1319,7 +1254,7 @@ hipError_t heads_forward(const Ctx& c, const HeadWs& h, Arr feat, Arr featlo = A
       double fl = 0.0;
       for (int l = 0; l < 5; ++l) fl += 2.0 * kO[base + l] * kI[base + l] * (double)c.P;
       ProfSlot* ps = prof_begin(c.st, 4, fl, (double)c.P * (512.0 + a.srows * 2.0 + (save ? 4 * (512.0 + 64.0) : 0.0) + (head ? 24.0 : 12.0)) + 2.0 * 540000.0);
-      e = launch_head_chain(c.st, a, head, c.ldp / 64, g_ws_grid, save);
+      e = launch_head_chain(c.st, a, head, c.ldp / 64, WS_GRID, save);
       prof_end(c.st, ps);
       if (e != hipSuccess) return e;
     }
@@ -1363,19 +1298,17 @@ hipError_t heads_backward(const Ctx& c, const HeadWs& h, const SdfWs& w, const n
     const int srows = head ? SMALL_A : SMALL_R;
     hipError_t e2;
     const bool hb = per_head_batch && batch;
-    bool l4_batched = false;
     if (hb) {
-      // the three hidden layers and (16-bit operands) the output layer -- 3 / 6 rows against the same kind of 256-row B operand -- as
-      // problems of one launch: one weight-gradient launch and one finish less per head
+      // (batch implies 16-bit octet operands) the three hidden layers and the output layer -- 3 / 6 rows against the same kind of
+      // 256-row B operand -- as problems of one launch: one weight-gradient launch and one finish less per head
       WProb pb[4];
       for (int l = 1; l <= 3; ++l) pb[l - 1] = WProb{base + l, {ab[l], Arr{}}, {256, 0}, {hh[l], Arr{}}};
-      l4_batched = oct && g_head_l4_batched;
-      if (l4_batched) pb[3] = WProb{base + 4, {head ? h.topbf_a : h.topbf_r, Arr{}}, {kO[base + 4], 0}, {hh[4], Arr{}}};
-      if ((e2 = wgrad_multi(c, w, pb, l4_batched ? 4 : 3, 1, gr)) != hipSuccess) return e2;
+      pb[3] = WProb{base + 4, {head ? h.topbf_a : h.topbf_r, Arr{}}, {kO[base + 4], 0}, {hh[4], Arr{}}};
+      if ((e2 = wgrad_multi(c, w, pb, 4, 1, gr)) != hipSuccess) return e2;
     }
     for (int l = 0; l <= 4; ++l) {
       if ((hb || (!per_head_batch && batch)) && l >= 1 && l <= 3) continue;
-      if (l == 4 && l4_batched) continue;
+      if (l == 4 && hb) continue;
       WPair pr[1] = {};
       pr[0].A = l == 4 ? (oct ? (head ? h.topbf_a : h.topbf_r) : F(top)) : ab[l]; pr[0].rowsA = kO[base + l];
       if (l == 0) {
@@ -1417,12 +1350,12 @@ hipError_t heads_backward(const Ctx& c, const HeadWs& h, const SdfWs& w, const n
       double fl = 0.0;
       for (int l = 0; l < 5; ++l) fl += 2.0 * kO[base + l] * kI[base + l] * (double)c.P;
       ProfSlot* ps = prof_begin(c.st, 4, fl, (double)c.P * (16.0 + 4 * (512.0 + 64.0) + (head ? 1024.0 : 512.0) + srows * 4.0) + 2.0 * 540000.0);
-      e = launch_head_bwd_chain(c.st, a, head, c.ldp / 64, g_ws_grid);
+      e = launch_head_bwd_chain(c.st, a, head, c.ldp / 64, WS_GRID);
       prof_end(c.st, ps);
       if (e != hipSuccess) return e;
       // ... while its cotangents are the last thing written (unless the batch size in force splits three problems 2 + 1: a multi-problem
       // launch takes at least two, and the batch of two is what large point counts want)
-      if (g_head_wgrad_order && (!batch || nb1 >= 3) && (e = head_wgrads(head, true)) != hipSuccess) return e;
+      if ((!batch || nb1 >= 3) && (e = head_wgrads(head, true)) != hipSuccess) return e;
       continue;
     }
     if ((e = layer(c, L.tr[base + 4], EPI_BWD_RELU, in(oct ? (head ? h.topbf_a : h.topbf_r) : F(top), top_rows), NOIN, nullptr, 256, ab[3], Arr{}, 1 << 30, hh[4])) != hipSuccess) return e;
@@ -1641,30 +1574,20 @@ int neat_set_tuning(int key, int value) {          /* 0: bf16 layer-kernel point
   if (key == 0 && (value == 2 || value == 4)) { g_pt_bf16 = value; return 0; }
   if (key == 1 && (value == 0 || value == 1)) { g_wgrad_h3 = value; return 0; }
   if (key == 2 && (value == 0 || value == 1)) { g_layer_ws = value; return 0; }
-  if (key == 3 && value >= 1 && value <= 4096) { g_ws_grid = value; return 0; }
-  if (key == 4 && value >= 0 && value <= 4) { g_fused_ws = value; return 0; }
   if (key == 6 && value >= 0 && value <= 2) { g_wreduce_direct = value; return 0; }
-  if (key == 7 && (value == 0 || value == 1)) { g_wgrad_interleave = value; return 0; }
   if (key == 8 && (value == -1 || value == 0 || value == 2 || value == 3 || value == 6)) { g_wgrad_batch = value; return 0; }
-  if (key == 5 && (value == 0 || (value >= 2 && value <= 4))) { g_fused_nt = value; return 0; }
   if (key == 9 && value >= 0 && value <= 2) { g_ws_interleave = value; return 0; }
-  if (key == 10 && (value == 0 || value == 1)) { g_fused_interleave = value; return 0; }
   if (key == 11 && value >= 0 && value <= 63) { g_ws_aux_nt = value; return 0; }
   if (key == 12 && (value == 0 || value == 1)) { g_ws_wide_store = value; return 0; }
   if (key == 13 && (value == 0 || value == 1)) { g_fused_adj = value; return 0; }
   if (key == 14 && value >= 0 && value <= 2) { g_head_chain = value; return 0; }
-  if (key == 15 && (value == 0 || value == 1)) { g_head_wgrad_order = value; return 0; }
   if (key == 16 && value >= 0 && value <= 2) { g_dw_fused = value; return 0; }
   if (key == 17 && value >= 0 && value <= 7) { g_dw_ablate = value; return 0; }
-  if (key == 18 && value >= 1 && value <= 16) { g_dw_nsub = value; return 0; }
-  if (key == 19 && (value == 0 || value == 1)) { g_wgrad_k320 = value; return 0; }
-  if (key == 20 && (value == 0 || value == 1)) { g_head_l4_batched = value; return 0; }
   if (key == 21 && value >= 0 && value <= 4) { g_wgrad_narrow = value; return 0; }
   if (key == 22 && (value == 0 || value == 1)) { g_dw_lin8 = value; return 0; }
-  if (key == 23 && (value == 0 || (value >= 16 && value <= DW_MAXGRID))) { g_dw_grid = value; return 0; }
   if (key == 24 && (value == 0 || value == 1)) { g_chain_pp = value; return 0; }
   if (key == 25 && (value == 0 || value == 1)) { g_dw_segments = value; return 0; }
-  return -1;
+  return -1;                                       /* unknown, and the retired keys 3, 4, 5, 7, 10, 15, 18, 19, 20, 23 */
 }
 
 int neat_prof_enable(int on) {

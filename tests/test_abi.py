@@ -62,6 +62,31 @@ def test_workspace_queries_are_consistent():
     assert lib.neat_sdf_ldp(0, 2) == 0
 
 
+def test_tuning_keys_retired_and_surviving():
+    """neat_set_tuning only writes host switches, so this runs without a GPU.  Every retired key (closed experiments: the key list in
+    include/neat_hip.h) is rejected with -1 for every value it once took, its old default included; every surviving key accepts its
+    documented default.  Setting a key to its default is also what leaves it there: the switches of this process stay as the other
+    tests expect them."""
+    from neat_amd import _lib
+    lib = _lib.lib()
+    retired = (3, 4, 5, 7, 10, 15, 18, 19, 20, 23)
+    for key in retired:
+        for value in (0, 1, 2, 3, 4, 16, 256):
+            assert lib.neat_set_tuning(key, value) == -1, (key, value)
+    # key -> documented default (include/neat_hip.h); 17 and 28 are the probe switch and the junction-MLP switch
+    defaults = {0: 2, 1: 1, 2: 1, 6: 2, 8: -1, 9: 1, 11: 15, 12: 1, 13: 1, 14: 2, 16: 1, 17: 0, 21: 1, 22: 1, 24: 1, 25: 1, 28: 1}
+    assert not set(defaults) & set(retired)
+    for key, value in defaults.items():
+        assert lib.neat_set_tuning(key, value) == 0, (key, value)
+    # the header's key list names exactly these keys, and the retired numbers on one line
+    text = open(os.path.join(ROOT, "include", "neat_hip.h")).read()
+    doc = text[text.index("A/B switches for benchmarking"):text.index("int neat_set_tuning")]
+    listed = {int(m) for m in re.findall(r"^ \* {1,3}(\d+) \S", doc, flags=re.M)}
+    assert listed == set(defaults), sorted(listed ^ set(defaults))
+    assert "Retired keys" in doc and ", ".join(map(str, retired)) in doc
+    assert lib.neat_set_tuning(99, 0) == -1
+
+
 def test_copy_batch_rejects_bad_arguments_before_any_launch():
     """neat_copy_batch validates on the host: more than 16 copies, null tables, misaligned pointers and sizes that are not multiples of 4
     return -1 without touching a device (so this runs without a GPU); zero copies is a no-op."""
