@@ -449,6 +449,54 @@ int neat_mesh_emit(const float* grid, int nx, int ny, int nz, const double* b0, 
                    int* faces, int nf, void* stream);
 int neat_unit_rows3(float* g, int n, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, nothing existing changes, so the version number stays): scoring a reconstruction against
+ * ground truth on the device (code/evaluation/eval-dtu.py, eval-lsr-dtu.py, eval-wfr-dtu.py, eval-abc.py; the reference uses an sklearn
+ * kd-tree on the host and a sequential thinning loop).  Points are float64 [n,3] row-major; every decision (keep / remove, inside /
+ * outside, nearer / farther) compares float64 quantities computed in the reference's order, squared distances as ((dx dx) + dy dy) + dz dz
+ * without fused multiply-adds (definitions: neat_amd/csrc/kernels_eval.hpp).  Asynchronous on the stream, no allocation; only
+ * integer atomics, and no result depends on their order.  Bad arguments return -1 before any launch.
+ *
+ * neat_eval_grid_t describes a uniform cell grid over a cloud of n points: the cell of a point is floor((p - origin) / cell) per axis,
+ *   clamped into dim; its bucket is the cell's linear index (dense = 1, buckets = dim[0] dim[1] dim[2]) or a hash of the cell modulo
+ *   `buckets` (dense = 0).  start [buckets + 1], sidx [n] (the point of every slot) and spts [n,3] (the points in slot order) are the
+ *   caller's device arrays; neat_eval_grid fills them (ws: neat_eval_grid_ws_bytes(n, buckets)) and the queries below read them.
+ * neat_eval_thin_round : one round of radius thinning in index order (point c stays iff no earlier staying point lies within radius,
+ *   <=): state [n] bytes (0 undecided, 1 kept, 2 removed; zeroed by the caller before the first round); every undecided point whose
+ *   earlier neighbours are all decided is decided, and the number still undecided is ADDED to *undecided.  Needs radius <= grid->cell.
+ *   The caller repeats rounds until a round adds nothing; the lowest undecided point is always decidable, so n rounds suffice.
+ * neat_eval_nearest : per query the nearest cloud point (ties: the lowest index) among those within max_dist (widened by 1e-12
+ *   relative; the caller takes the `< max_dist` decision): dist [m] = its distance, idx [m] its index; inf and -1 if there is none.
+ * neat_eval_obs_mask (eval-dtu.py:98-110): flags [n] bytes, bit 0 = lo <= p < hi on all axes, bit 1 = bit 0 and the voxel
+ *   rint((p - bb0) / res) lies inside mask [shape[0]][shape[1]][shape[2]] (bytes) and is non-zero there; f32_quotient = 1 rounds the
+ *   quotient to float32 first (eval-lsr-dtu.py:106, eval-wfr-dtu.py:55).  lo, hi, bb0, shape are HOST arrays of three.
+ * neat_eval_tri_count / neat_eval_tri_emit (eval-dtu.py:48-71): the lattice samples of every triangle of faces [nf,3] int32 over
+ *   verts [nv,3], triangle-major, then i, then j.  count writes *total on the device (-1: a vertex index out of range, a triangle with
+ *   more than 30000 lattice steps on a side, or more samples than int32 holds); the caller reads it once, allocates out [total,3] and
+ *   calls emit with the same arguments and ws (neat_eval_tri_ws_bytes(nf)).
+ * neat_eval_line_cost (eval-abc.py:43, :86-88): cost [n_pred, n_gt]; ends = 1: point sets [n,3], the Euclidean distance; ends = 2:
+ *   lines [n,2,3], the lower of the two endpoint orders' mean endpoint distance. */
+typedef struct {
+  double origin[3];
+  double cell;
+  int dim[3];
+  int buckets;
+  int dense;
+  int n;
+  const int* start;
+  const int* sidx;
+  const double* spts;
+} neat_eval_grid_t;
+size_t neat_eval_grid_ws_bytes(int n, int buckets);
+int neat_eval_grid(const double* points, const neat_eval_grid_t* grid, int* start, int* sidx, double* spts, void* ws, void* stream);
+int neat_eval_thin_round(const double* points, const neat_eval_grid_t* grid, double radius, unsigned char* state, int* undecided, void* stream);
+int neat_eval_nearest(const neat_eval_grid_t* grid, const double* queries, int m, double max_dist, double* dist, int* idx, void* stream);
+int neat_eval_obs_mask(const double* points, int n, const double* lo, const double* hi, const double* bb0, double res, const unsigned char* mask,
+                       const int* shape, int f32_quotient, unsigned char* flags, void* stream);
+size_t neat_eval_tri_ws_bytes(int nf);
+int neat_eval_tri_count(const double* verts, int nv, const int* faces, int nf, double density, void* ws, int* total, void* stream);
+int neat_eval_tri_emit(const double* verts, int nv, const int* faces, int nf, double density, void* ws, double* out, int total, void* stream);
+int neat_eval_line_cost(const double* pred, int n_pred, const double* gt, int n_gt, int ends, double* cost, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

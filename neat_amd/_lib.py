@@ -22,6 +22,12 @@ class NetGrads(ctypes.Structure):
     _fields_ = [("dv", c_fp * NUM_LAYERS), ("dg", c_fp * NUM_LAYERS), ("db", c_fp * NUM_LAYERS)]
 
 
+class EvalGrid(ctypes.Structure):
+    """neat_eval_grid_t: a uniform cell grid over a cloud (neat_amd/evaluate.py builds it)."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("cell", ctypes.c_double), ("dim", ctypes.c_int * 3), ("buckets", ctypes.c_int),
+                ("dense", ctypes.c_int), ("n", ctypes.c_int), ("start", c_fp), ("sidx", c_fp), ("spts", c_fp)]
+
+
 _SIGNATURES = {
     "neat_abi_version": (ctypes.c_int, []),
     "neat_packed_floats": (ctypes.c_size_t, [ctypes.c_int]),
@@ -127,6 +133,17 @@ _SIGNATURES = {
     "neat_mesh_emit": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_double), ctypes.c_float, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp]),
     "neat_unit_rows3": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp]),
+    "neat_eval_grid_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "neat_eval_grid": (ctypes.c_int, [c_fp, ctypes.POINTER(EvalGrid), c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_eval_thin_round": (ctypes.c_int, [c_fp, ctypes.POINTER(EvalGrid), ctypes.c_double, c_fp, c_fp, c_fp]),
+    "neat_eval_nearest": (ctypes.c_int, [ctypes.POINTER(EvalGrid), c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, c_fp]),
+    "neat_eval_obs_mask": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_fp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                          c_fp, c_fp]),
+    "neat_eval_tri_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "neat_eval_tri_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, c_fp]),
+    "neat_eval_tri_emit": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, ctypes.c_int, c_fp]),
+    "neat_eval_line_cost": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

@@ -8,6 +8,7 @@ namespace neat {
 // A value the compiler may not fuse into an fma with its consumer.  (HIP's __fmul_rn / __fadd_rn are plain operators under the default
 // -ffp-contract=fast and DO get contracted: the round-5 form of points_from_rays_kernel and eik_points_kernel compiled to v_fmac_f32 / v_pk_fma_f32.)
 __device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ double rounded(double x) { asm volatile("" : "+v"(x)); return x; }      // the float64 decisions of kernels_eval.hpp
 
 __device__ __forceinline__ float wave_incl_scan(float v, int lane) {
 #pragma unroll

@@ -1,11 +1,13 @@
 // C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
-// samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, volume weights.
+// samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, the evaluation
+// of a reconstruction, volume weights.
 // Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
 // boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
 #include "kernels_sampler.hpp"
 #include "kernels_junction.hpp"
 #include "kernels_parse.hpp"
 #include "kernels_mesh.hpp"
+#include "kernels_eval.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -699,6 +701,109 @@ int neat_unit_rows3(float* g, int n, void* stream) {
   if (n < 0 || (n > 0 && !g)) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(mesh_normalize_kernel, grid1(n), dim3(256), 0, (hipStream_t)stream, g, n);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: scoring a reconstruction against ground truth (kernels_eval.hpp) ------------------------------------------------
+static bool eval_grid_args(const neat_eval_grid_t* h, EvalGrid* g) {
+  if (!h || h->n < 0 || h->buckets < 1 || !(h->cell > 0.0) || !std::isfinite(h->cell) || !h->start) return false;
+  long long cells = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (h->dim[a] < 1 || h->dim[a] > (1 << 20) || !std::isfinite(h->origin[a])) return false;
+    g->o[a] = h->origin[a]; g->dim[a] = h->dim[a];
+    cells = cells > INT_MAX ? cells : cells * h->dim[a];
+  }
+  if (h->dense && cells != (long long)h->buckets) return false;
+  if (h->n > 0 && (!h->sidx || !h->spts)) return false;
+  g->cell = h->cell; g->buckets = h->buckets; g->dense = h->dense ? 1 : 0; g->n = h->n;
+  g->start = h->start; g->sidx = h->sidx; g->spts = h->spts;
+  return true;
+}
+
+size_t neat_eval_grid_ws_bytes(int n, int buckets) {
+  if (n < 0 || buckets < 1) return 0;
+  return parse_al((size_t)buckets * sizeof(int)) + parse_al((size_t)std::max(n, 1) * sizeof(int));
+}
+
+int neat_eval_grid(const double* points, const neat_eval_grid_t* grid, int* start, int* sidx, double* spts, void* ws, void* stream) {
+  EvalGrid g;
+  if (!eval_grid_args(grid, &g) || !ws || start != grid->start || sidx != grid->sidx || spts != grid->spts || (g.n > 0 && !points)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  int* cnt = (int*)ws;
+  int* bucket_of = (int*)((char*)ws + parse_al((size_t)g.buckets * sizeof(int)));
+  NEAT_CHECK(hipMemsetAsync(cnt, 0, (size_t)g.buckets * sizeof(int), st));
+  if (g.n > 0) hipLaunchKernelGGL(eval_grid_bin_kernel, grid1(g.n, EVAL_WG), dim3(EVAL_WG), 0, st, points, g, bucket_of, cnt);
+  hipLaunchKernelGGL(eval_exscan_kernel, dim3(1), dim3(EVAL_SCAN_WG), 0, st, (const int*)cnt, start, g.buckets, (int*)nullptr);
+  if (g.n > 0) hipLaunchKernelGGL(eval_grid_scatter_kernel, grid1(g.n, EVAL_WG), dim3(EVAL_WG), 0, st, points, g.n, (const int*)bucket_of, cnt,
+                                  (const int*)start, sidx, spts);
+  return (int)hipGetLastError();
+}
+
+int neat_eval_thin_round(const double* points, const neat_eval_grid_t* grid, double radius, unsigned char* state, int* undecided, void* stream) {
+  EvalGrid g;
+  if (!eval_grid_args(grid, &g) || !(radius >= 0.0) || !(radius <= grid->cell) || !undecided || (g.n > 0 && (!points || !state))) return -1;
+  if (g.n == 0) return 0;
+  hipLaunchKernelGGL(eval_thin_round_kernel, grid1(g.n, EVAL_WG), dim3(EVAL_WG), 0, (hipStream_t)stream, points, g, radius * radius, state, undecided);
+  return (int)hipGetLastError();
+}
+
+int neat_eval_nearest(const neat_eval_grid_t* grid, const double* queries, int m, double max_dist, double* dist, int* idx, void* stream) {
+  EvalGrid g;
+  if (!eval_grid_args(grid, &g) || m < 0 || !(max_dist >= 0.0) || (m > 0 && (!queries || !dist || !idx))) return -1;
+  if (m == 0) return 0;
+  const double cap = max_dist * (1.0 + 1e-12);       // the `< max_dist` decision is the caller's, on the distance
+  hipLaunchKernelGGL(eval_nearest_kernel, grid1(m, EVAL_WG), dim3(EVAL_WG), 0, (hipStream_t)stream, g, queries, m, cap, cap * cap, dist, idx);
+  return (int)hipGetLastError();
+}
+
+int neat_eval_obs_mask(const double* points, int n, const double* lo, const double* hi, const double* bb0, double res, const unsigned char* mask,
+                       const int* shape, int f32_quotient, unsigned char* flags, void* stream) {
+  if (n < 0 || !lo || !hi || !bb0 || !shape || !mask || !(res > 0.0) || !std::isfinite(res) || (n > 0 && (!points || !flags))) return -1;
+  EvalObs a;
+  for (int c = 0; c < 3; ++c) {
+    if (shape[c] < 1) return -1;
+    a.lo[c] = lo[c]; a.hi[c] = hi[c]; a.bb0[c] = bb0[c]; a.shape[c] = shape[c];
+  }
+  a.res = res; a.f32_quotient = f32_quotient ? 1 : 0;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(eval_obs_mask_kernel, grid1(n, EVAL_WG), dim3(EVAL_WG), 0, (hipStream_t)stream, points, n, a, mask, flags);
+  return (int)hipGetLastError();
+}
+
+size_t neat_eval_tri_ws_bytes(int nf) {
+  if (nf < 0) return 0;
+  return 2 * parse_al(((size_t)nf + 1) * sizeof(int));
+}
+
+static inline bool eval_tri_ok(const double* verts, int nv, const int* faces, int nf, double density, void* ws) {
+  return nv >= 0 && nf >= 0 && ws && density > 0.0 && std::isfinite(density) && (nf == 0 || (verts && faces && nv > 0));
+}
+
+int neat_eval_tri_count(const double* verts, int nv, const int* faces, int nf, double density, void* ws, int* total, void* stream) {
+  if (!eval_tri_ok(verts, nv, faces, nf, density, ws) || !total) return -1;
+  int* counts = (int*)ws;
+  int* offs = (int*)((char*)ws + parse_al(((size_t)nf + 1) * sizeof(int)));
+  hipStream_t st = (hipStream_t)stream;
+  if (nf > 0) hipLaunchKernelGGL(eval_tri_count_kernel, grid1(nf, EVAL_WG / 64), dim3(EVAL_WG), 0, st, verts, nv, faces, nf, density, counts);
+  hipLaunchKernelGGL(eval_exscan_kernel, dim3(1), dim3(EVAL_SCAN_WG), 0, st, (const int*)counts, offs, nf, total);
+  return (int)hipGetLastError();
+}
+
+int neat_eval_tri_emit(const double* verts, int nv, const int* faces, int nf, double density, void* ws, double* out, int total, void* stream) {
+  if (!eval_tri_ok(verts, nv, faces, nf, density, ws) || total < 0 || (total > 0 && !out)) return -1;
+  if (nf == 0 || total == 0) return 0;
+  const int* offs = (const int*)((char*)ws + parse_al(((size_t)nf + 1) * sizeof(int)));
+  hipLaunchKernelGGL(eval_tri_emit_kernel, grid1(nf, EVAL_WG / 64), dim3(EVAL_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, density, offs, out, total);
+  return (int)hipGetLastError();
+}
+
+int neat_eval_line_cost(const double* pred, int n_pred, const double* gt, int n_gt, int ends, double* cost, void* stream) {
+  if (n_pred < 0 || n_gt < 0 || (ends != 1 && ends != 2)) return -1;
+  const long long total = (long long)n_pred * n_gt;
+  if (total == 0) return 0;
+  if (!pred || !gt || !cost || total > INT_MAX) return -1;
+  hipLaunchKernelGGL(eval_line_cost_kernel, dim3((unsigned)((total + EVAL_WG - 1) / EVAL_WG)), dim3(EVAL_WG), 0, (hipStream_t)stream, pred, n_pred, gt,
+                     n_gt, ends, cost);
   return (int)hipGetLastError();
 }
 
