@@ -497,6 +497,40 @@ int neat_eval_tri_count(const double* verts, int nv, const int* faces, int nf, d
 int neat_eval_tri_emit(const double* verts, int nv, const int* faces, int nf, double density, void* ws, double* out, int total, void* stream);
 int neat_eval_line_cost(const double* pred, int n_pred, const double* gt, int n_gt, int ends, double* cost, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, nothing existing changes, so the version number stays): pictures of a wireframe and of the
+ * surface mesh behind it, headless (code/visualization/show.py draws through an open3d window and matplotlib; code/evaluation/show-mesh.py
+ * shows the mesh alone).  F frames per call: cams [F,21] float64, per frame K [3,3] then [R|T] [3,4] (world to camera), row-major; of K
+ * only fx = K00, fy = K11, cx = K02, cy = K12 are read.  Pixel (row i, column j) has its centre at projected (x, y) = (j, i).  Every
+ * geometric decision is float64 with each product and sum rounded on its own (definitions: neat_amd/csrc/kernels_show.hpp, DESIGN 3d;
+ * tests/show_f64.py restates them).  Asynchronous on the stream, no allocation; only integer atomics (a 64-bit minimum, a 32-bit maximum),
+ * and no result depends on their order.  Bad arguments (F, H or W < 1 or H, W > 32768, null pointers, near <= 0, a negative width or
+ * radius, hidden_alpha outside [0, 1], a colour outside [0, 1], an output that is not 4-byte aligned) return -1 before any launch.
+ *
+ * neat_show_ws_bytes / neat_show_ws_layout : the workspace of (F, H, W) and the byte offsets of its four parts: offsets[0] the depth
+ *   keys, uint64 [F,H,W] = bits(float32 depth) << 32 | winning triangle (0x7f800000ffffffff where no triangle covers); [1] the line
+ *   coverage and [2] the point coverage, float32 [F,H,W]; [3] one int32 status word (1: a face index out of range), followed by the
+ *   mesh pass's own queue of large triangles.
+ * neat_show_clear   : keys to "nothing", coverages and status to 0.
+ * neat_show_mesh    : verts [nv,3] float64, faces [nf,3] int32; per pixel centre inside a triangle (edges inclusive, both windings) the
+ *   minimum key.  A triangle with a vertex nearer than `near`, of zero screen area or with a non-finite coordinate is dropped; a face
+ *   index out of range sets the status word, and neat_show_resolve then writes nothing (the caller reads the word once).
+ * neat_show_lines   : lines [n,2,3] float64; coverage clamp(width / 2 + 0.5 - distance, 0, 1) times (visible ? 1 : hidden_alpha), the
+ *   maximum over the segments; visible iff the segment's perspective-correct depth at the pixel <= the key's depth + bias.  Segments are
+ *   cut at z = near.  Call after neat_show_mesh on the same stream.
+ * neat_show_points  : points [n,3] float64 as discs of radius + 0.5 - distance, the same visibility rule.
+ * neat_show_resolve : out [F,H,W,3] bytes; colors = HOST array of twelve: background, line, point, mesh rgb in [0, 1]. */
+size_t neat_show_ws_bytes(int F, int H, int W);
+int neat_show_ws_layout(int F, int H, int W, size_t* offsets);
+int neat_show_clear(void* ws, int F, int H, int W, void* stream);
+int neat_show_mesh(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, double near, void* ws,
+                   void* stream);
+int neat_show_lines(const double* lines, int n, const double* cams, int F, int H, int W, double near, double width, double bias,
+                    double hidden_alpha, void* ws, void* stream);
+int neat_show_points(const double* points, int n, const double* cams, int F, int H, int W, double near, double radius, double bias,
+                     double hidden_alpha, void* ws, void* stream);
+int neat_show_resolve(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, const double* colors,
+                      void* ws, unsigned char* out, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

@@ -144,6 +144,15 @@ _SIGNATURES = {
     "neat_eval_tri_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, c_fp]),
     "neat_eval_tri_emit": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, ctypes.c_int, c_fp]),
     "neat_eval_line_cost": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
+    "neat_show_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "neat_show_ws_layout": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "neat_show_clear": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
+    "neat_show_mesh": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                      c_fp, c_fp]),
+    "neat_show_lines": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_fp, c_fp]),
+    "neat_show_points": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_fp, c_fp]),
+    "neat_show_resolve": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_double), c_fp, c_fp, c_fp]),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

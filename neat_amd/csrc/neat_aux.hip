@@ -1,6 +1,6 @@
 // C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
 // samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, the evaluation
-// of a reconstruction, volume weights.
+// of a reconstruction, the wireframe / mesh pictures, volume weights.
 // Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
 // boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
 #include "kernels_sampler.hpp"
@@ -8,9 +8,11 @@
 #include "kernels_parse.hpp"
 #include "kernels_mesh.hpp"
 #include "kernels_eval.hpp"
+#include "kernels_show.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <limits.h>
 #include <math.h>
 
@@ -804,6 +806,108 @@ int neat_eval_line_cost(const double* pred, int n_pred, const double* gt, int n_
   if (!pred || !gt || !cost || total > INT_MAX) return -1;
   hipLaunchKernelGGL(eval_line_cost_kernel, dim3((unsigned)((total + EVAL_WG - 1) / EVAL_WG)), dim3(EVAL_WG), 0, (hipStream_t)stream, pred, n_pred, gt,
                      n_gt, ends, cost);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: pictures of a wireframe and of the mesh behind it (kernels_show.hpp) ---------------------------------------------
+struct ShowWs { unsigned long long* key; unsigned* cov; unsigned* covp; int* status; size_t off[4], bytes; long long total; };
+static bool show_ws(int F, int H, int W, void* ws, ShowWs* s) {
+  if (F < 1 || H < 1 || W < 1 || H > 32768 || W > 32768) return false;
+  const long long total = (long long)F * H * W;
+  if (total > (1ll << 40)) return false;
+  s->total = total;
+  s->off[0] = 0;
+  s->off[1] = parse_al((size_t)total * 8);
+  s->off[2] = s->off[1] + parse_al((size_t)total * 4);
+  s->off[3] = s->off[2] + parse_al((size_t)total * 4);
+  s->bytes = s->off[3] + 256 + (size_t)SHOW_QUEUE_CAP * sizeof(long long);      // status word, queue counter (at +8), the queue of large triangles
+  char* b = (char*)ws;
+  s->key = (unsigned long long*)b; s->cov = (unsigned*)(b + s->off[1]); s->covp = (unsigned*)(b + s->off[2]); s->status = (int*)(b + s->off[3]);
+  return true;
+}
+static inline bool show_grid_ok(long long items, int per_block) { return (items + per_block - 1) / per_block <= (long long)INT_MAX; }
+static inline dim3 show_grid(long long items, int per_block) { return dim3((unsigned)((items + per_block - 1) / per_block)); }
+static inline bool show_common(const double* cams, double near, void* ws) { return cams && ws && near > 0.0 && std::isfinite(near); }
+
+size_t neat_show_ws_bytes(int F, int H, int W) {
+  ShowWs s;
+  return show_ws(F, H, W, nullptr, &s) ? s.bytes : 0;
+}
+
+int neat_show_ws_layout(int F, int H, int W, size_t* offsets) {
+  ShowWs s;
+  if (!offsets || !show_ws(F, H, W, nullptr, &s)) return -1;
+  for (int i = 0; i < 4; ++i) offsets[i] = s.off[i];
+  return 0;
+}
+
+int neat_show_clear(void* ws, int F, int H, int W, void* stream) {
+  ShowWs s;
+  if (!ws || !show_ws(F, H, W, ws, &s) || !show_grid_ok(s.total, SHOW_WG)) return -1;
+  hipLaunchKernelGGL(show_clear_kernel, show_grid(s.total, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, s.key, s.cov, s.covp, s.status, s.total);
+  return (int)hipGetLastError();
+}
+
+int neat_show_mesh(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, double near, void* ws,
+                   void* stream) {
+  ShowWs s;
+  if (!show_ws(F, H, W, ws, &s) || !show_common(cams, near, ws) || nv < 0 || nf < 0 || (nf > 0 && (!verts || !faces || nv < 1))) return -1;
+  const long long items = (long long)F * nf;
+  if (!show_grid_ok(items, SHOW_WG)) return -1;
+  if (nf == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* queued = (unsigned long long*)((char*)s.status + 8);
+  long long* queue = (long long*)((char*)s.status + 256);
+  NEAT_CHECK(hipMemsetAsync(queued, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(show_mesh_kernel, show_grid(items, SHOW_WG), dim3(SHOW_WG), 0, st, verts, nv, faces, nf, cams, F, H, W, near, s.key, s.status,
+                     queued, queue, SHOW_QUEUE_CAP);
+  hipLaunchKernelGGL(show_mesh_large_kernel, dim3(SHOW_LARGE_BLOCKS), dim3(SHOW_WG), 0, st, verts, nv, faces, nf, cams, F, H, W, near, s.key,
+                     (const unsigned long long*)queued, (const long long*)queue, SHOW_QUEUE_CAP);
+  return (int)hipGetLastError();
+}
+
+static inline bool show_cover_ok(double size, double bias, double hidden_alpha) {
+  return size >= 0.0 && std::isfinite(size) && std::isfinite(bias) && hidden_alpha >= 0.0 && hidden_alpha <= 1.0;
+}
+
+int neat_show_lines(const double* lines, int n, const double* cams, int F, int H, int W, double near, double width, double bias,
+                    double hidden_alpha, void* ws, void* stream) {
+  ShowWs s;
+  if (!show_ws(F, H, W, ws, &s) || !show_common(cams, near, ws) || n < 0 || (n > 0 && !lines) || !show_cover_ok(width, bias, hidden_alpha)) return -1;
+  const long long items = (long long)F * n;
+  if (!show_grid_ok(items, SHOW_WG / 64)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(show_lines_kernel, show_grid(items, SHOW_WG / 64), dim3(SHOW_WG), 0, (hipStream_t)stream, lines, n, cams, F, H, W, near,
+                     width / 2.0 + 0.5, bias, hidden_alpha, (const unsigned long long*)s.key, s.cov);
+  return (int)hipGetLastError();
+}
+
+int neat_show_points(const double* points, int n, const double* cams, int F, int H, int W, double near, double radius, double bias,
+                     double hidden_alpha, void* ws, void* stream) {
+  ShowWs s;
+  if (!show_ws(F, H, W, ws, &s) || !show_common(cams, near, ws) || n < 0 || (n > 0 && !points) || !show_cover_ok(radius, bias, hidden_alpha)) return -1;
+  const long long items = (long long)F * n;
+  if (!show_grid_ok(items, SHOW_WG)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(show_points_kernel, show_grid(items, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, points, n, cams, F, H, W, near,
+                     radius + 0.5, bias, hidden_alpha, (const unsigned long long*)s.key, s.covp);
+  return (int)hipGetLastError();
+}
+
+int neat_show_resolve(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, const double* colors, void* ws,
+                      unsigned char* out, void* stream) {
+  ShowWs s;
+  if (!show_ws(F, H, W, ws, &s) || !cams || !ws || !colors || !out || ((uintptr_t)out & 3) || nv < 0 || nf < 0 || (nf > 0 && (!verts || !faces || nv < 1)))
+    return -1;
+  ShowStyle st;
+  for (int c = 0; c < 3; ++c) {
+    st.bg[c] = colors[c]; st.line[c] = colors[3 + c]; st.point[c] = colors[6 + c]; st.mesh[c] = colors[9 + c];
+  }
+  for (int c = 0; c < 12; ++c) if (!(colors[c] >= 0.0 && colors[c] <= 1.0)) return -1;
+  const long long quads = (s.total + 3) / 4;
+  if (!show_grid_ok(quads, SHOW_WG)) return -1;
+  hipLaunchKernelGGL(show_resolve_kernel, show_grid(quads, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, cams, H, W, s.total, st,
+                     (const unsigned long long*)s.key, (const float*)s.cov, (const float*)s.covp, (const int*)s.status, out);
   return (int)hipGetLastError();
 }
 
