@@ -531,6 +531,34 @@ int neat_show_points(const double* points, int n, const double* cams, int F, int
 int neat_show_resolve(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, const double* colors,
                       void* ws, unsigned char* out, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): the frame side of rendering whole views of a checkpoint
+ * (code/evaluation/eval.py --eval_rendering and the trainer's do_vis pictures assemble, quantise and average on the host).  Definitions:
+ * neat_amd/csrc/kernels_frame.hpp; tests/render_f64.py restates them.  All arithmetic is IEEE float32 with one rounding per
+ * step unless said otherwise.  Asynchronous on the stream, no allocation, no float atomics: two runs give the same bytes.  Bad arguments
+ * return -1 before any launch.
+ *
+ * neat_frame_put   : the ONE launch per chunk.  rgb [n,3], normal [n,3], depth [n]: a chunk's outputs for the frame pixels p0 .. p0+n-1
+ *   of a frame of P pixels; each may be null.  Writes rgb8 [P,3] = byte(rgb) (if rgb8 is not null), normal8 [P,3] = byte((normal + 1) / 2),
+ *   depth_out [P] = depth and, with gt [P,3], err [P,3] = (rgb - gt)^2; nothing outside the chunk's pixels.
+ *   byte(x) = clamp(trunc(255 x), 0, 255), 0 for a NaN.  -1 for n < 0, p0 < 0, p0 + n > P, or an input without its output.
+ * neat_frame_sum   : out[0] = the float64 sum of x [n] float32 over a fixed 256-ary tree (independent of any launch geometry);
+ *   ws = neat_frame_sum_ws_bytes(n) bytes, 8-byte aligned (not read for n <= 256).
+ * neat_frame_range : range[0], range[1] = the minimum and maximum of the finite values of x [n], (0, 0) if there is none, left in device
+ *   memory; ws = neat_frame_range_ws_bytes() bytes.
+ * neat_frame_grey  : out [n] bytes = clamp(trunc((255 (x - lo)) / (hi - lo)), 0, 255) with (lo, hi) = range[0..1] read on the device;
+ *   0 where x is not finite or hi == lo.
+ * neat_frame_grid  : images [N,H,W,3] bytes onto the canvas of torchvision.utils.make_grid(nrow, padding = 2, pad_value = 0):
+ *   xmaps = min(nrow, N), ymaps = ceil(N / xmaps), canvas [(ymaps (H + 2) + 2), (xmaps (W + 2) + 2), 3], image k at row
+ *   (k / xmaps)(H + 2) + 2 and column (k % xmaps)(W + 2) + 2, zeros elsewhere; N = 1: the canvas is the image, unpadded. */
+int neat_frame_put(const float* rgb, const float* normal, const float* depth, const float* gt, int n, long long p0, long long P,
+                   unsigned char* rgb8, unsigned char* normal8, float* depth_out, float* err, void* stream);
+size_t neat_frame_sum_ws_bytes(long long n);
+int neat_frame_sum(const float* x, long long n, void* ws, double* out, void* stream);
+size_t neat_frame_range_ws_bytes(void);
+int neat_frame_range(const float* x, long long n, void* ws, float* range, void* stream);
+int neat_frame_grey(const float* x, long long n, const float* range, unsigned char* out, void* stream);
+int neat_frame_grid(const unsigned char* images, int N, int H, int W, int nrow, unsigned char* canvas, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

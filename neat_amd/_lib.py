@@ -153,6 +153,13 @@ _SIGNATURES = {
     "neat_show_points": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_fp, c_fp]),
     "neat_show_resolve": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_double), c_fp, c_fp, c_fp]),
+    "neat_frame_put": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_frame_sum_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "neat_frame_sum": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
+    "neat_frame_range_ws_bytes": (ctypes.c_size_t, []),
+    "neat_frame_range": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
+    "neat_frame_grey": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
+    "neat_frame_grid": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

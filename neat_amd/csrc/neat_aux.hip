@@ -1,6 +1,6 @@
 // C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
 // samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, the evaluation
-// of a reconstruction, the wireframe / mesh pictures, volume weights.
+// of a reconstruction, the wireframe / mesh pictures, the frames of rendered views, volume weights.
 // Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
 // boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
 #include "kernels_sampler.hpp"
@@ -9,6 +9,7 @@
 #include "kernels_mesh.hpp"
 #include "kernels_eval.hpp"
 #include "kernels_show.hpp"
+#include "kernels_frame.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -908,6 +909,73 @@ int neat_show_resolve(const double* verts, int nv, const int* faces, int nf, con
   if (!show_grid_ok(quads, SHOW_WG)) return -1;
   hipLaunchKernelGGL(show_resolve_kernel, show_grid(quads, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, cams, H, W, s.total, st,
                      (const unsigned long long*)s.key, (const float*)s.cov, (const float*)s.covp, (const int*)s.status, out);
+  return (int)hipGetLastError();
+}
+
+// ---- frames of rendered views (kernels_frame.hpp) ----------------------------------------------------------------------------------------
+static inline bool frame_blocks_ok(long long items) { return (items + FRAME_WG - 1) / FRAME_WG <= (long long)INT_MAX; }
+static inline dim3 frame_blocks(long long items) { return dim3((unsigned)((items + FRAME_WG - 1) / FRAME_WG)); }
+
+int neat_frame_put(const float* rgb, const float* normal, const float* depth, const float* gt, int n, long long p0, long long P,
+                   unsigned char* rgb8, unsigned char* normal8, float* depth_out, float* err, void* stream) {
+  if (n < 0 || p0 < 0 || P < 0 || p0 > P || (long long)n > P - p0) return -1;
+  if ((normal && !normal8) || (depth && !depth_out) || (gt && (!rgb || !err))) return -1;
+  if (n == 0 || (!rgb && !normal && !depth)) return 0;
+  hipLaunchKernelGGL(frame_put_kernel, frame_blocks(3ll * n), dim3(FRAME_WG), 0, (hipStream_t)stream, rgb, normal, depth, gt, n, p0, rgb8, normal8,
+                     depth_out, err);
+  return (int)hipGetLastError();
+}
+
+// the levels of the tree above the leaves: ceil(n / 256) run sums, then ceil of that / 256 ... down to the level of at most 256 values
+size_t neat_frame_sum_ws_bytes(long long n) {
+  if (n < 0) return 0;
+  size_t doubles = 0;
+  for (long long m = (n + FRAME_WG - 1) / FRAME_WG; m > 1; m = (m + FRAME_WG - 1) / FRAME_WG) doubles += (size_t)m;
+  return parse_al(doubles * sizeof(double) + sizeof(double));
+}
+
+int neat_frame_sum(const float* x, long long n, void* ws, double* out, void* stream) {
+  if (n < 0 || !out || (n > 0 && !x) || !frame_blocks_ok(n)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) return (int)hipMemsetAsync(out, 0, sizeof(double), st);
+  long long m = (n + FRAME_WG - 1) / FRAME_WG;
+  if (m > 1 && (!ws || ((uintptr_t)ws & 7))) return -1;
+  double* level = (double*)ws;
+  hipLaunchKernelGGL(frame_sum_kernel<float>, dim3((unsigned)m), dim3(FRAME_WG), 0, st, x, n, m > 1 ? level : out);
+  while (m > 1) {
+    const long long up = (m + FRAME_WG - 1) / FRAME_WG;
+    double* next = up > 1 ? level + m : out;
+    hipLaunchKernelGGL(frame_sum_kernel<double>, dim3((unsigned)up), dim3(FRAME_WG), 0, st, (const double*)level, m, next);
+    level = next;
+    m = up;
+  }
+  return (int)hipGetLastError();
+}
+
+size_t neat_frame_range_ws_bytes(void) { return (size_t)FRAME_RANGE_BLOCKS * 2 * sizeof(float); }
+
+int neat_frame_range(const float* x, long long n, void* ws, float* range, void* stream) {
+  if (n < 0 || !range || !ws || ((uintptr_t)ws & 3) || (n > 0 && !x)) return -1;
+  const int blocks = (int)std::max(1ll, std::min((long long)FRAME_RANGE_BLOCKS, (n + FRAME_WG - 1) / FRAME_WG));
+  hipLaunchKernelGGL(frame_range_partial_kernel, dim3(blocks), dim3(FRAME_WG), 0, (hipStream_t)stream, x, n, (float*)ws);
+  hipLaunchKernelGGL(frame_range_finish_kernel, dim3(1), dim3(FRAME_WG), 0, (hipStream_t)stream, (const float*)ws, blocks, range);
+  return (int)hipGetLastError();
+}
+
+int neat_frame_grey(const float* x, long long n, const float* range, unsigned char* out, void* stream) {
+  if (n < 0 || !range || (n > 0 && (!x || !out)) || !frame_blocks_ok(n)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(frame_grey_kernel, frame_blocks(n), dim3(FRAME_WG), 0, (hipStream_t)stream, x, n, range, out);
+  return (int)hipGetLastError();
+}
+
+int neat_frame_grid(const unsigned char* images, int N, int H, int W, int nrow, unsigned char* canvas, void* stream) {
+  if (!images || !canvas || N < 1 || H < 1 || W < 1 || nrow < 1 || H > 32768 || W > 32768) return -1;
+  const int xmaps = std::min(nrow, N), ymaps = (N + xmaps - 1) / xmaps, pad = N == 1 ? 0 : 2;
+  const long long ch = (long long)ymaps * (H + pad) + pad, cw3 = 3 * ((long long)xmaps * (W + pad) + pad);
+  if (cw3 > (long long)INT_MAX || ch > (long long)INT_MAX || !frame_blocks_ok(ch * cw3)) return -1;
+  hipLaunchKernelGGL(frame_grid_kernel, frame_blocks(ch * cw3), dim3(FRAME_WG), 0, (hipStream_t)stream, images, N, H, W, xmaps, pad, ch * cw3, (int)cw3,
+                     canvas);
   return (int)hipGetLastError();
 }
 

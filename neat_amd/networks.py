@@ -446,17 +446,33 @@ class VolSDFNetwork(_HipModule):
         z_vals, _ = self._z_vals(ray_dirs, cam_loc)
         return self._render(cam_loc, ray_dirs, z_vals, False)[0]
 
+    def _camera(self, input, one_launch, uv_proj=None):
+        """-> (setup, ray_dirs [R,3], cam_loc [R,3]): the rays through `uv`.  setup = ops.camera_setup's tuple if the caller allows its one
+        launch and it applies (it then carries the rays through uv_proj as well, if given), else None and the rays come from _rays."""
+        intrinsics, uv, pose = input["intrinsics"], input["uv"], input["pose"]
+        if (one_launch and uv.is_cuda and pose.shape == (1, 4, 4) and intrinsics.dtype == torch.float32 and intrinsics.stride(-1) == 1
+                and intrinsics.shape[0] == 1):
+            setup = ops.camera_setup(uv, uv_proj, pose, intrinsics)
+            return setup, setup[0], setup[1]
+        return (None,) + tuple(self._rays(input))
+
+    @torch.no_grad()
+    def render_pixels(self, uv, pose, intrinsics):
+        """uv [1,R,2], pose [1,4,4], intrinsics [1,4,4] -> (rgb [R,3], normal_map [R,3], depth [R]): the picture part of the eval
+        forward -- camera rays, the sampler and the main pass, without the junction and line block -- bit for bit what forward returns
+        as rgb_values, normal_map and depth on the same pixels (neat_amd.render walks a view with it)."""
+        assert not self.training
+        _, ray_dirs, cam_loc = self._camera({"uv": uv, "pose": pose, "intrinsics": intrinsics}, True)
+        z_vals, _ = self._z_vals(ray_dirs, cam_loc)
+        rgb, _, depth, _, _, _, _, nmap = self._render(cam_loc, ray_dirs, z_vals, True)
+        return rgb, nmap, depth
+
     def forward(self, input):
         intrinsics, uv, pose = input["intrinsics"], input["uv"], input["pose"]
         # camera-only work of the whole forward in one launch: rays through uv and through uv_proj, [R | T] of pose^-1, the contiguous
         # intrinsics (round 6; before: camera_rays twice + camera_mats)
-        setup = None
-        if (uv.is_cuda and pose.shape == (1, 4, 4) and intrinsics.dtype == torch.float32 and intrinsics.stride(-1) == 1
-                and intrinsics.shape[0] == 1 and "uv_proj" in input and input["uv_proj"].shape == uv.shape):
-            setup = ops.camera_setup(uv, input["uv_proj"], pose, intrinsics)
-            ray_dirs, cam_loc = setup[0], setup[1]
-        else:
-            ray_dirs, cam_loc = self._rays(input)
+        with_proj = "uv_proj" in input and input["uv_proj"].shape == uv.shape
+        setup, ray_dirs, cam_loc = self._camera(input, with_proj, input["uv_proj"] if with_proj else None)
         n_rays = ray_dirs.shape[0]
         z_vals, z_eik = self._z_vals(ray_dirs, cam_loc)
         grad_theta = None

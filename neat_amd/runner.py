@@ -1,8 +1,9 @@
 """Training runner in the shape of the reference's `training/exp_runner.py` + `VolSDFTrainRunner`
 (code/training/volsdf_train.py:66-410): same conf files, same loop (per-iteration re-sampling of the rays and
 ExponentialLR step), same checkpoint layout (`checkpoints/{Model,Optimizer,Scheduler}Parameters/{epoch,latest}.pth` with
-the reference's dict keys), so checkpoints move between the two code bases.  Tensorboard, git logging, the rendered-image plots and
-the open3d dumps of the reference runner are out of scope; the surface mesh of its `do_vis` branch is `--vis_mesh`.
+the reference's dict keys), so checkpoints move between the two code bases.  Tensorboard, git logging, the plotly pages and
+the open3d dumps of the reference runner are out of scope; the surface mesh of its `do_vis` branch is `--vis_mesh`, its
+rendered-image and normal pictures are `--vis_images`.
 
     python -m neat_amd.runner --conf /path/to/confs/abc-neat-a.conf --data_root /path/to/data --nepoch 2000
 
@@ -38,7 +39,7 @@ SUBDIRS = ("ModelParameters", "OptimizerParameters", "SchedulerParameters")
 
 class TrainRunner:
     def __init__(self, conf, nepochs, exps_folder="exps", expname="", scan_id=-1, data_root="../data", device="cuda:0",
-                 timestamp=None, precision=None, log_freq=50, rank=0, world=1, vis_mesh=False):
+                 timestamp=None, precision=None, log_freq=50, rank=0, world=1, vis_mesh=False, vis_images=False):
         self.conf = conf_mod.parse_file(conf) if isinstance(conf, str) else conf
         self.nepochs = nepochs
         self.device = torch.device(device)
@@ -110,6 +111,10 @@ class TrainRunner:
         # runner forces off; off by default here too)
         self.vis_mesh = vis_mesh
         self.plot_freq = self.conf.get_int("train.plot_freq", default=100)
+        # --vis_images: plots/rendering_{epoch}.png (the rendered frame over the ground truth) and plots/normal_{epoch}.png of one view
+        # every train.plot_freq epochs (the same branch; neat_amd.render).  The reference draws the view from a shuffled loader; here it
+        # is view (epoch // plot_freq) % len(dataset).
+        self.vis_images = vis_images
 
     def load_checkpoints(self, checkpoints_dir, checkpoint="latest"):
         """Continue from a run of this runner or of the reference's (volsdf_train.py:187-207)."""
@@ -144,6 +149,22 @@ class TrainRunner:
         mesh.write_ply(path, res["verts"], res["faces"], res["normals"])
         return path
 
+    def write_images(self, epoch):
+        """`<run>/plots/rendering_{epoch}.png` and `normal_{epoch}.png` from the model as it stands (neat_amd.render; rank 0, CUDA only)
+        -> the two paths or None.  The model is put in eval mode for the pictures and returned to the mode it was in."""
+        if self.rank != 0 or self.device.type != "cuda":
+            return None
+        from . import render
+        idx = (epoch // max(self.plot_freq, 1)) % len(self.train_dataset)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            return render.plot_view(self.model, self.train_dataset, idx, os.path.join(self.expdir, self.timestamp), epoch,
+                                    nrow=self.conf.get_int("plot.plot_nimgs", default=1),
+                                    chunksize=self.conf.get_int("train.split_n_pixels", default=render.DEFAULT_CHUNK))
+        finally:
+            self.model.train(was_training)
+
     def run(self):
         history = []
         epoch = self.start_epoch
@@ -152,6 +173,8 @@ class TrainRunner:
                 self.save_checkpoints(epoch)
             if self.vis_mesh and epoch % self.plot_freq == 0:
                 self.write_surface(epoch)
+            if self.vis_images and epoch % self.plot_freq == 0:
+                self.write_images(epoch)
             if self.batches is None:
                 self.train_dataset.change_sampling_idx(self.num_pixels)
             self.model.train()
@@ -194,6 +217,8 @@ def main():
     ap.add_argument("--timestamp", default=None)
     ap.add_argument("--vis_mesh", default=False, action="store_true",
                     help="write plots/surface_{epoch}.ply (neat_amd.mesh) every train.plot_freq epochs")
+    ap.add_argument("--vis_images", default=False, action="store_true",
+                    help="write plots/rendering_{epoch}.png and plots/normal_{epoch}.png (neat_amd.render) every train.plot_freq epochs")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import socket
@@ -218,7 +243,8 @@ def main():
     if torch.cuda.is_available():
         torch.cuda.set_device(local)      # the ctypes launches take torch.cuda.current_stream(): it must be this rank's device, whatever the backend
     runner = TrainRunner(args.conf, args.nepoch, args.exps_folder, args.expname, args.scan_id, args.data_root, device=f"cuda:{local}",
-                         timestamp=args.timestamp, precision=args.precision, rank=rank, world=world, vis_mesh=args.vis_mesh)
+                         timestamp=args.timestamp, precision=args.precision, rank=rank, world=world, vis_mesh=args.vis_mesh,
+                         vis_images=args.vis_images)
     if args.is_continue:
         runner.load_checkpoints(args.is_continue, args.checkpoint)
     runner.run()
