@@ -449,6 +449,44 @@ int neat_mesh_emit(const float* grid, int nx, int ny, int nz, const double* b0, 
                    int* faces, int nf, void* stream);
 int neat_unit_rows3(float* g, int n, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, nothing existing changes, so the version number stays): the evaluation mesh of a checkpoint
+ * (code/utils/plots.py: get_surface_high_res_mesh :140-218, get_surface_by_grid :221-316, get_grid :331-362; code/evaluation/eval.py
+ * :132-162; the reference samples 10 000 random surface points, aligns a grid to their principal axes, cuts with trimesh's slice_plane
+ * and moves to world coordinates on the host).  Definitions: neat_amd/csrc/kernels_evalmesh.hpp, DESIGN 3b.  No atomics, fixed-shape
+ * sums: two runs give the same bytes.  No entry point synchronises with the host.  R [3][3], c [3], origin [3], A [3][4] are HOST
+ * float64 arrays, row-major.
+ * neat_grid_points_affine : neat_grid_points in a frame: node (i, j, k) with local coordinates p (the linspace rule in float64, before
+ *   its rounding) goes to x = c + R^T p, x_a = float(c_a + ((R_0a p_0 + R_1a p_1) + R_2a p_2)) with every operation rounded to float64.
+ * neat_mesh_moments : out [10] float64 on the device = area, int (x - o) dA [3], int (x - o)(x - o)^T dA (xx, xy, xz, yy, yz, zz) of
+ *   the mesh verts [nv,3] fp32, faces [nf,3] int32, exact per triangle, summed over a fixed tree.  A triangle of zero area adds nothing;
+ *   one with a non-finite vertex or an index outside [0, nv) adds nothing and sets flag[0] (device int) to 1, else 0.
+ *   ws = neat_mesh_moments_ws_bytes(nf) bytes, 8-byte aligned (not read for nf <= 1024).
+ * neat_affine_rows3 : rows of v [n,3] fp32 become A [v; 1] in place, evaluated in float64 as ((A_r0 x + A_r1 y) + A_r2 z) + A_r3,
+ *   rounded to fp32 once.
+ * neat_affine_bounds3 : out [6] float64 on the device = min (3) and max (3) of the same mapped rows in float64; v is not written.
+ *   n >= 1; ws = neat_affine_bounds3_ws_bytes() bytes, 8-byte aligned.
+ * The cut of a mesh by the half-space sign (x[axis] - value) >= 0 (sign = +1 or -1; value must be a float32 value), in two calls with
+ *   integer sorts / scans by the caller in between:
+ * neat_mesh_cut_count : fcnt [nf] int32 = triangles each face leaves (0, 1 or 2); ekey [2 nf] int64 = keys a nv + b of its crossing
+ *   edges from inside vertex a to outside vertex b (-1: none); used [nv] int32 = 1 for a vertex some surviving face has inside, else 0.
+ * neat_mesh_cut_emit : vmap [nv] = exclusive scan of used, foff [nf] = exclusive scan of fcnt, ukey [ncut] = the unique keys >= 0
+ *   ascending, nkeep = sum of used -> out_verts [nkeep + ncut, 3] (kept vertices in their order, then one cut vertex per key at
+ *   a + t (b - a), t = d_a / (d_a - d_b) in float64, the axis coordinate exactly `value`) and out_faces [nf_out,3], nf_out = sum of fcnt
+ *   (by source face, then by emitted triangle; winding kept).  Writes beyond nv_out / nf_out are dropped.
+ * Bad arguments return -1 before any launch. */
+int neat_grid_points_affine(float* x_fm, int ldp, long long first_node, int count, const int* n, const double* b0, const double* b1,
+                            const double* R, const double* c, void* stream);
+size_t neat_mesh_moments_ws_bytes(int nf);
+int neat_mesh_moments(const float* verts, int nv, const int* faces, int nf, const double* origin, void* ws, double* out, int* flag, void* stream);
+int neat_affine_rows3(float* v, int n, const double* A, void* stream);
+size_t neat_affine_bounds3_ws_bytes(void);
+int neat_affine_bounds3(const float* v, int n, const double* A, void* ws, double* out, void* stream);
+int neat_mesh_cut_count(const float* verts, int nv, const int* faces, int nf, int axis, double value, int sign, int* fcnt, long long* ekey,
+                        int* used, void* stream);
+int neat_mesh_cut_emit(const float* verts, int nv, const int* faces, int nf, int axis, double value, int sign, const int* used, const int* vmap,
+                       const int* foff, const long long* ukey, int ncut, int nkeep, float* out_verts, int nv_out, int* out_faces, int nf_out,
+                       void* stream);
+
 /* ---- added to ABI v15 (new symbols only, nothing existing changes, so the version number stays): scoring a reconstruction against
  * ground truth on the device (code/evaluation/eval-dtu.py, eval-lsr-dtu.py, eval-wfr-dtu.py, eval-abc.py; the reference uses an sklearn
  * kd-tree on the host and a sequential thinning loop).  Points are float64 [n,3] row-major; every decision (keep / remove, inside /

@@ -133,6 +133,16 @@ _SIGNATURES = {
     "neat_mesh_emit": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_double), ctypes.c_float, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp]),
     "neat_unit_rows3": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp]),
+    "neat_grid_points_affine": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+                                + [ctypes.POINTER(ctypes.c_double)] * 4 + [c_fp]),
+    "neat_mesh_moments_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "neat_mesh_moments": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), c_fp, c_fp, c_fp, c_fp]),
+    "neat_affine_rows3": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), c_fp]),
+    "neat_affine_bounds3_ws_bytes": (ctypes.c_size_t, []),
+    "neat_affine_bounds3": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), c_fp, c_fp, c_fp]),
+    "neat_mesh_cut_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
+    "neat_mesh_cut_emit": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_fp, c_fp, c_fp, c_fp,
+                                          ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp]),
     "neat_eval_grid_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "neat_eval_grid": (ctypes.c_int, [c_fp, ctypes.POINTER(EvalGrid), c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_eval_thin_round": (ctypes.c_int, [c_fp, ctypes.POINTER(EvalGrid), ctypes.c_double, c_fp, c_fp, c_fp]),

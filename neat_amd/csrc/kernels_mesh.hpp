@@ -21,6 +21,7 @@
 #include <limits.h>
 #include <math.h>
 
+#include "device_util.hpp"       // rounded
 #include "kernels_parse.hpp"     // parse_block_exscan
 
 namespace neat {
@@ -44,7 +45,9 @@ struct MeshAxes {
 };
 
 __device__ __forceinline__ float mesh_coord(const MeshAxes& g, int a, int i) {
-  return i == g.n[a] - 1 ? (float)g.b1[a] : (float)__dadd_rn(__dmul_rn((double)i, g.step[a]), g.b0[a]);
+  // the product and the sum are rounded separately, as numpy.linspace does (__dmul_rn / __dadd_rn are plain operators and were contracted
+  // into one v_fma_f64, which parts from the rule where b0 + i step cancels to a node next to zero)
+  return i == g.n[a] - 1 ? (float)g.b1[a] : (float)rounded(rounded((double)i * g.step[a]) + g.b0[a]);
 }
 
 // ---- (a) the query points of `count` consecutive nodes from node `first` into x_fm [3][ldp]; the layout's padding columns are zeroed

@@ -1,12 +1,13 @@
 // C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
 // samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, the evaluation
-// of a reconstruction, the wireframe / mesh pictures, the frames of rendered views, volume weights.
+// mesh, the evaluation of a reconstruction, the wireframe / mesh pictures, the frames of rendered views, volume weights.
 // Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
 // boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
 #include "kernels_sampler.hpp"
 #include "kernels_junction.hpp"
 #include "kernels_parse.hpp"
 #include "kernels_mesh.hpp"
+#include "kernels_evalmesh.hpp"
 #include "kernels_eval.hpp"
 #include "kernels_show.hpp"
 #include "kernels_frame.hpp"
@@ -704,6 +705,115 @@ int neat_unit_rows3(float* g, int n, void* stream) {
   if (n < 0 || (n > 0 && !g)) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(mesh_normalize_kernel, grid1(n), dim3(256), 0, (hipStream_t)stream, g, n);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: the evaluation mesh of a checkpoint (kernels_evalmesh.hpp) ------------------------------------------------------
+static bool finite_all(const double* x, int n) {
+  if (!x) return false;
+  for (int i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false;
+  return true;
+}
+
+int neat_grid_points_affine(float* x_fm, int ldp, long long first_node, int count, const int* n, const double* b0, const double* b1,
+                            const double* R, const double* c, void* stream) {
+  MeshAxes g;
+  if (!x_fm || count < 0 || ldp < count || first_node < 0 || !mesh_axes(n, b0, b1, &g) || !finite_all(R, 9) || !finite_all(c, 3)) return -1;
+  if (first_node + count > (long long)n[0] * n[1] * n[2]) return -1;
+  if (ldp == 0) return 0;
+  Frame3 f;
+  for (int i = 0; i < 9; ++i) f.R[i] = R[i];
+  for (int i = 0; i < 3; ++i) f.c[i] = c[i];
+  hipLaunchKernelGGL(grid_points_affine_kernel, grid1(ldp, EMESH_WG), dim3(EMESH_WG), 0, (hipStream_t)stream, x_fm, ldp, first_node, count, g, f);
+  return (int)hipGetLastError();
+}
+
+// the levels of the moments' tree above the leaves, each [MOMENTS_N][m]
+size_t neat_mesh_moments_ws_bytes(int nf) {
+  if (nf < 0) return 0;
+  size_t doubles = 0;
+  for (long long m = ((long long)nf + MOMENTS_TILE - 1) / MOMENTS_TILE; m > 1; m = (m + EMESH_WG - 1) / EMESH_WG) doubles += (size_t)MOMENTS_N * (size_t)m;
+  return parse_al(doubles * sizeof(double) + sizeof(double));
+}
+
+int neat_mesh_moments(const float* verts, int nv, const int* faces, int nf, const double* origin, void* ws, double* out, int* flag, void* stream) {
+  if (nv < 0 || nf < 0 || !out || !flag || !finite_all(origin, 3) || (nf > 0 && (!faces || !verts || nv == 0))) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (nf == 0) {
+    NEAT_CHECK(hipMemsetAsync(out, 0, (MOMENTS_N - 1) * sizeof(double), st));
+    return (int)hipMemsetAsync(flag, 0, sizeof(int), st);
+  }
+  long long m = ((long long)nf + MOMENTS_TILE - 1) / MOMENTS_TILE;
+  if (m > 1 && (!ws || ((uintptr_t)ws & 7))) return -1;
+  Origin3 o;
+  for (int i = 0; i < 3; ++i) o.o[i] = origin[i];
+  double* level = (double*)ws;
+  hipLaunchKernelGGL(mesh_moments_kernel, dim3((unsigned)m), dim3(EMESH_WG), 0, st, verts, nv, faces, nf, o, level, m, m == 1, out, flag);
+  while (m > 1) {
+    const long long up = (m + EMESH_WG - 1) / EMESH_WG;
+    double* next = level + (size_t)MOMENTS_N * (size_t)m;
+    hipLaunchKernelGGL(mesh_moments_level_kernel, dim3((unsigned)up, MOMENTS_N), dim3(EMESH_WG), 0, st, (const double*)level, m, next, up, up == 1, out,
+                       flag);
+    level = next;
+    m = up;
+  }
+  return (int)hipGetLastError();
+}
+
+static bool affine_arg(const double* A, Affine34* a) {
+  if (!finite_all(A, 12)) return false;
+  for (int i = 0; i < 12; ++i) a->a[i] = A[i];
+  return true;
+}
+
+int neat_affine_rows3(float* v, int n, const double* A, void* stream) {
+  Affine34 a;
+  if (n < 0 || (n > 0 && !v) || !affine_arg(A, &a)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(affine_rows3_kernel, grid1(n, EMESH_WG), dim3(EMESH_WG), 0, (hipStream_t)stream, v, n, a);
+  return (int)hipGetLastError();
+}
+
+size_t neat_affine_bounds3_ws_bytes(void) { return (size_t)BOUNDS_BLOCKS * 6 * sizeof(double); }
+
+int neat_affine_bounds3(const float* v, int n, const double* A, void* ws, double* out, void* stream) {
+  Affine34 a;
+  if (n < 1 || !v || !out || !ws || ((uintptr_t)ws & 7) || !affine_arg(A, &a)) return -1;
+  const int blocks = std::max(1, std::min(BOUNDS_BLOCKS, (n + EMESH_WG - 1) / EMESH_WG));
+  hipLaunchKernelGGL(affine_bounds3_partial_kernel, dim3(blocks), dim3(EMESH_WG), 0, (hipStream_t)stream, v, n, a, (double*)ws);
+  hipLaunchKernelGGL(affine_bounds3_finish_kernel, dim3(1), dim3(EMESH_WG), 0, (hipStream_t)stream, (const double*)ws, blocks, out);
+  return (int)hipGetLastError();
+}
+
+static bool cut_plane(int axis, double value, int sign, CutPlane* p) {
+  if (axis < 0 || axis > 2 || (sign != 1 && sign != -1) || !std::isfinite(value) || (double)(float)value != value) return false;
+  p->axis = axis; p->value = value; p->sign = (double)sign;
+  return true;
+}
+
+int neat_mesh_cut_count(const float* verts, int nv, const int* faces, int nf, int axis, double value, int sign, int* fcnt, long long* ekey,
+                        int* used, void* stream) {
+  CutPlane p;
+  if (nv < 1 || nf < 1 || !verts || !faces || !fcnt || !ekey || !used || !cut_plane(axis, value, sign, &p)) return -1;
+  NEAT_CHECK(hipMemsetAsync(used, 0, (size_t)nv * sizeof(int), (hipStream_t)stream));
+  hipLaunchKernelGGL(cut_count_kernel, grid1(nf, EMESH_WG), dim3(EMESH_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, p, fcnt, ekey, used);
+  return (int)hipGetLastError();
+}
+
+int neat_mesh_cut_emit(const float* verts, int nv, const int* faces, int nf, int axis, double value, int sign, const int* used, const int* vmap,
+                       const int* foff, const long long* ukey, int ncut, int nkeep, float* out_verts, int nv_out, int* out_faces, int nf_out,
+                       void* stream) {
+  CutPlane p;
+  if (nv < 1 || nf < 1 || !verts || !faces || !used || !vmap || !foff || !cut_plane(axis, value, sign, &p)) return -1;
+  if (ncut < 0 || nkeep < 0 || nkeep > nv || (ncut > 0 && !ukey) || (long long)nkeep + ncut != (long long)nv_out || nf_out < 0) return -1;
+  if ((nv_out > 0 && !out_verts) || (nf_out > 0 && !out_faces)) return -1;
+  if (nv_out == 0 || nf_out == 0) return 0;
+  const long long lanes = (long long)nv + ncut;
+  if ((lanes + EMESH_WG - 1) / EMESH_WG > (long long)INT_MAX) return -1;
+  hipLaunchKernelGGL(cut_verts_kernel, dim3((unsigned)((lanes + EMESH_WG - 1) / EMESH_WG)), dim3(EMESH_WG), 0, (hipStream_t)stream, verts, nv, p, used,
+                     vmap, ukey, ncut, nkeep, out_verts, nv_out);
+  hipLaunchKernelGGL(cut_faces_kernel, grid1(nf, EMESH_WG), dim3(EMESH_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, p, foff, vmap, ukey, ncut,
+                     nkeep, out_faces, nf_out);
   return (int)hipGetLastError();
 }
 

@@ -3,6 +3,11 @@ training writes as `plots/surface_{epoch}.ply`; its evaluation scripts build the
 
     python -m neat_amd.mesh --conf <run>/runconf.conf [--checkpoint latest] [--resolution 100] [--grid-boundary -1.5 1.5] [--level 0]
                             [--largest-component] [--expdir <run>] [--gpu 0] [--precision fp32] [--overwrite]
+    python -m neat_amd.mesh --conf <run>/runconf.conf --eval [--resolution 512] [--bbox bbs.npz --scan_id N | --bbox-values x0 y0 z0 x1 y1 z1]
+                            [--cams cameras.npz] [--no-world] [--all-components] [--normals]
+
+--eval writes the mesh the reference's evaluation scores (eval_surface below; evaluation/eval.py:132-162) as `<run>/{epoch}/scan{id}.ply`,
+ready for `python -m neat_amd.evaluate dtu-mesh --data`.
 
 The grid is evaluated on the device in chunks whose query points are written straight into the SDF kernels' layout (no [N, 3] point
 tensor), and the level set is extracted on the device by marching tetrahedra (csrc/kernels_mesh.hpp) -- not the reference's
@@ -62,9 +67,11 @@ def _implicit(model):
 
 
 @torch.no_grad()
-def sdf_grid(model, resolution=DEFAULT_RESOLUTION, grid_boundary=DEFAULT_BOUNDARY, chunk=DEFAULT_CHUNK):
+def sdf_grid(model, resolution=DEFAULT_RESOLUTION, grid_boundary=DEFAULT_BOUNDARY, chunk=DEFAULT_CHUNK, frame=None):
     """get_sdf_vals on the nodes of a uniform grid -> float32 device tensor [nx, ny, nz] (x slowest), in the model's own precision.
-    `chunk` nodes per query (rounded up to the SDF kernels' point tile); the workspace is sized once, for one chunk."""
+    `chunk` nodes per query (rounded up to the SDF kernels' point tile); the workspace is sized once, for one chunk.
+    frame = (R [3,3], c [3]) float64 on the host: the grid is laid out in the local coordinates p of that frame and node p is queried at
+    c + R^T p (ops.grid_points_affine); without it the nodes are queried where they are."""
     from . import ops
     net = _implicit(model)
     shape = _shape3(resolution)
@@ -81,7 +88,10 @@ def sdf_grid(model, resolution=DEFAULT_RESOLUTION, grid_boundary=DEFAULT_BOUNDAR
     for first in range(0, total, chunk):
         count = min(chunk, total - first)
         stride = ldp if count == chunk else ops._lib.lib().neat_sdf_ldp(count, handle.precision)      # the ragged last chunk: its own stride
-        ops.grid_points(ws, stride, first, count, shape, lo, hi)
+        if frame is None:
+            ops.grid_points(ws, stride, first, count, shape, lo, hi)
+        else:
+            ops.grid_points_affine(ws, stride, first, count, shape, lo, hi, frame[0], frame[1])
         ops.sdf_values_laid_out(handle, ws, count, net.sdf_bounding_sphere, net.sphere_scale, out=flat[first:first + count])
     return grid
 
@@ -168,6 +178,187 @@ def surface(model, resolution=None, grid_boundary=None, level=0.0, largest_compo
     return {"verts": verts, "faces": faces, "normals": nrm}
 
 
+# ---- the evaluation mesh (plots.get_surface_high_res_mesh :140-218 / get_surface_by_grid(higher_res=True) :221-316, eval.py:132-162) ----
+EVAL_RESOLUTION = 512
+COARSE_RESOLUTION = 100          # the first mesh, which gives the frame (plots.py:142, :229)
+DTU_BBOX_QUIRK = np.array([[1.5], [1.0]])      # get_surface_by_grid multiplies the npz's min row by 1.5 and its max row by 1.0 (plots.py:222)
+
+
+def principal_frame(verts, faces):
+    """The principal axes of a surface -> (R [3,3], mean [3]) float64 on the host.  The moments are the exact surface integrals
+    (ops.mesh_moments; the reference estimates them from 10 000 unseeded random surface samples, plots.py:168-175) about the vertex
+    bounding-box centre o: C = M2 / A - m m^T, mean = o + m.  Rows of R = eigenvectors of C by ascending eigenvalue, each with its
+    largest-magnitude entry positive; if det R < 0 rows 1 and 2 are swapped (plots.py:176-177)."""
+    from . import ops
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        raise ValueError("principal_frame: an empty mesh has no frame")
+    box = ops.affine_bounds3(verts, np.eye(3, 4)).cpu().numpy()
+    o = 0.5 * (box[:3] + box[3:])
+    return frame_from_moments(ops.mesh_moments(verts, faces, o), o)
+
+
+def frame_from_moments(mom, o):
+    """(area, first moments [3], second moments xx xy xz yy yz zz) about o -> (R, mean); the host half of principal_frame."""
+    mom, o = np.asarray(mom, dtype=np.float64), np.asarray(o, dtype=np.float64)
+    area = mom[0]
+    if not area > 0:
+        raise ValueError("principal_frame: the mesh has no area")
+    m = mom[1:4] / area
+    xx, xy, xz, yy, yz, zz = mom[4:10] / area
+    C = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) - np.outer(m, m)
+    _, vec = np.linalg.eigh(C)                               # ascending eigenvalues, eigenvectors in columns
+    R = vec.T.copy()
+    for r in range(3):
+        if R[r, np.argmax(np.abs(R[r]))] < 0:
+            R[r] = -R[r]
+    if np.linalg.det(R) < 0:
+        R = R[[0, 2, 1]]
+    return R, o + m
+
+
+def _aligned_axes(lo, hi, resolution, eps):
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3 or any(not h > l for l, h in zip(lo, hi)):
+        raise ValueError("aligned_grid: a box with three positive extents")
+    if resolution < 2:
+        raise ValueError("aligned_grid: the shortest axis needs at least 2 nodes")
+    s = int(np.argmin([h - l for l, h in zip(lo, hi)]))
+    start_s, stop_s = lo[s] - eps, hi[s] + eps
+    h = (stop_s - start_s) / (resolution - 1)
+    shape, lo3, hi3 = [0] * 3, [0.0] * 3, [0.0] * 3
+    for a in range(3):
+        if a == s:
+            shape[a], lo3[a], hi3[a] = int(resolution), start_s, stop_s
+        else:
+            start, stop = lo[a] - eps, hi[a] + h + eps
+            shape[a] = int(np.ceil((stop - start) / h))      # numpy.arange's length rule
+            lo3[a], hi3[a] = start, start + (shape[a] - 1) * h
+    return tuple(shape), tuple(lo3), tuple(hi3)
+
+
+def aligned_grid(lo, hi, resolution, eps):
+    """get_grid (plots.py:331-362) -> (shape, lo3, hi3): the shortest axis of the box [lo, hi] gets `resolution` nodes over
+    [lo_s - eps, hi_s + eps] (numpy.linspace), spacing h; every other axis starts at lo_a - eps and has numpy.arange's
+    ceil(((hi_a + h + eps) - (lo_a - eps)) / h) nodes, the last one at lo3_a + (n_a - 1) h.  The nodes of the long axes follow the
+    linspace rule of the kernels over [lo3_a, hi3_a], not arange's start + i h: equal within one float32 ulp.
+    A grid of 2^31 nodes or more raises, naming the largest resolution that fits."""
+    shape, lo3, hi3 = _aligned_axes(lo, hi, int(resolution), float(eps))
+    nodes = lambda r: int(np.prod([int(n) for n in _aligned_axes(lo, hi, r, float(eps))[0]], dtype=object))
+    if nodes(int(resolution)) >= 2 ** 31:
+        fit, top = 2, int(resolution)
+        while top - fit > 1:                                 # nodes(r) grows with r
+            mid = (fit + top) // 2
+            fit, top = (mid, top) if nodes(mid) < 2 ** 31 else (fit, mid)
+        raise ValueError("aligned_grid: resolution {} gives a grid of {} x {} x {} nodes, 2^31 or more; the largest resolution that fits "
+                         "this box is {}".format(resolution, shape[0], shape[1], shape[2], fit))
+    return shape, lo3, hi3
+
+
+def clip_box(verts, faces, lo, hi):
+    """The part of a mesh inside the axis-aligned box [lo, hi] (float32 values), uncapped (trimesh's slice_plane(cap=False),
+    plots.py:307-314): six half-spaces one after the other, x >= lo, x <= hi, y >= lo, y <= hi, z >= lo, z <= hi (ops.mesh_cut).
+    -> (verts, faces); an empty result is ([0,3], [0,3])."""
+    from . import ops
+    lo, hi = _bounds3((lo, hi))
+    for axis in range(3):
+        for value, sign in ((lo[axis], 1), (hi[axis], -1)):
+            verts, faces = ops.mesh_cut(verts, faces, axis, value, sign)
+    return verts, faces
+
+
+def _affine34(M3, t):
+    A = np.zeros((3, 4), dtype=np.float64)
+    A[:, :3], A[:, 3] = M3, t
+    return A
+
+
+def eval_surface(model, resolution=EVAL_RESOLUTION, grid_boundary=None, level=0.0, bbox=None, take_components=True, scale_mat=None,
+                 normals=False, plot_conf=None, timings=None, chunk=DEFAULT_CHUNK):
+    """The mesh the reference's evaluation scores (eval.py:132-162) -> dict(verts, faces, normals or None, frame) on the device, or None
+    if a grid does not cross the level.  frame = dict(R, mean, shape, lo3, hi3): the principal frame of the coarse mesh and the fine grid
+    aligned to it.
+    Without bbox (get_surface_high_res_mesh): coarse cubic 100-node grid over grid_boundary -> its mesh -> the largest component (if
+    take_components) -> frame -> aligned grid, eps 0.1 -> mesh -> model frame.  With bbox [2,3] (get_surface_by_grid(higher_res=True)): the
+    coarse grid is aligned_grid(bbox, 100, eps 0), the largest component is always taken, eps is 0.01, and the mesh is cut by the box.
+    Then scale_mat [4,4] (model -> world) if given, and the largest component by area.  Normals (at the model-frame vertices) need
+    scale_mat's 3x3 part to be a positive multiple of the identity."""
+    from . import ops
+    plot_conf = plot_conf or {}
+    if grid_boundary is None:
+        grid_boundary = tuple(plot_conf.get("grid_boundary", DEFAULT_BOUNDARY))
+    S = None
+    if scale_mat is not None:
+        S = np.asarray(torch.as_tensor(scale_mat).detach().cpu().numpy(), dtype=np.float64)
+        if S.shape != (4, 4) or not np.isfinite(S).all():
+            raise ValueError("eval_surface: scale_mat [4, 4]")
+        if normals and not (S[0, 0] > 0 and np.array_equal(S[:3, :3], S[0, 0] * np.eye(3))):
+            raise ValueError("eval_surface: normals need scale_mat's 3x3 part to be a positive multiple of the identity")
+    dev = next(_implicit(model).parameters()).device
+    t = [time.perf_counter()]
+
+    def lap(name):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            t.append(time.perf_counter())
+            timings[name] = timings.get(name, 0.0) + t[-1] - t[-2]
+
+    if timings is not None:
+        torch.cuda.synchronize(dev)
+        t[0] = time.perf_counter()
+    if bbox is None:
+        cshape, clo, chi = _shape3(COARSE_RESOLUTION), *_bounds3(grid_boundary)
+        eps = 0.1
+    else:
+        bbox = np.asarray(torch.as_tensor(bbox).detach().cpu().numpy(), dtype=np.float32).astype(np.float64)      # the box as float32 values
+        if bbox.shape != (2, 3):
+            raise ValueError("eval_surface: bbox [2, 3] = (min, max)")
+        cshape, clo, chi = aligned_grid(bbox[0], bbox[1], COARSE_RESOLUTION, 0.0)
+        eps = 0.01
+    grid = sdf_grid(model, cshape, (clo, chi), chunk=chunk)
+    verts, faces = extract(grid, clo, chi, level)
+    del grid
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        return None
+    if take_components or bbox is not None:
+        verts, faces, _ = keep_largest_component(verts, faces)
+    lap("coarse_s")
+    R, mean = principal_frame(verts, faces)
+    box = ops.affine_bounds3(verts, _affine34(R, -R @ mean)).cpu().numpy()
+    shape, lo3, hi3 = aligned_grid(box[:3], box[3:], resolution, eps)
+    del verts, faces
+    lap("frame_s")
+    grid = sdf_grid(model, shape, (lo3, hi3), chunk=chunk, frame=(R, mean))
+    gmin, gmax = torch.aminmax(grid)
+    crosses = not (float(gmin) > level or float(gmax) < level)      # plots.py:199
+    lap("grid_s")
+    frame = {"R": R, "mean": mean, "shape": shape, "lo3": lo3, "hi3": hi3}
+    if not crosses:
+        return None
+    verts, faces = extract(grid, lo3, hi3, level)
+    del grid
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        return None
+    ops.affine_rows3_(verts, _affine34(R.T, mean))          # local -> model frame
+    lap("extract_s")
+    if bbox is not None:
+        verts, faces = clip_box(verts, faces, bbox[0], bbox[1])
+        lap("cut_s")
+        if faces.shape[0] == 0:
+            return None
+    world = verts
+    if S is not None:
+        world = ops.affine_rows3_(verts.clone(), S[:3])
+    world, faces, kept = keep_largest_component(world, faces)
+    lap("components_s")
+    nrm = vertex_normals(model, verts[kept].contiguous()) if normals else None
+    return {"verts": world, "faces": faces, "normals": nrm, "frame": frame}
+
+
+def eval_out_path(run_dir, epoch, scan_id=None):
+    """`<run>/{epoch}/scan{scan_id}.ply` (eval.py:160-162 under the run directory); `scan.ply` without an id."""
+    return os.path.join(run_dir, str(epoch), "scan{}.ply".format("" if scan_id is None else scan_id))
+
+
 def write_ply(path, verts, faces, normals=None):
     """Binary little-endian PLY: float32 x y z [nx ny nz] per vertex, `uchar 3 + 3 x int32` per face."""
     v = np.ascontiguousarray(torch.as_tensor(verts).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
@@ -211,6 +402,17 @@ def build_parser():
     ap.add_argument("--gpu", type=int, default=0, help="device index")
     ap.add_argument("--precision", choices=["fp32", "bf16", "bf16x3", "fp16", "fp16x3"], default=None)
     ap.add_argument("--overwrite", default=False, action="store_true", help="write even if the .ply exists")
+    ev = ap.add_argument_group("evaluation mesh (eval_surface)")
+    ev.add_argument("--eval", default=False, action="store_true", help="the mesh the evaluation scores: aligned fine grid, box cut, world frame "
+                    "(--resolution then defaults to %d and no normals are written unless --normals)" % EVAL_RESOLUTION)
+    ev.add_argument("--bbox", default=None, type=str, metavar="FILE.npz", help="bounding boxes by scan id (DTU's bbs.npz); needs --scan_id; "
+                    "its min row is multiplied by 1.5 as the reference does")
+    ev.add_argument("--bbox-values", default=None, type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="the box, taken as given")
+    ev.add_argument("--scan_id", default=None, type=int)
+    ev.add_argument("--cams", default=None, type=str, metavar="cameras.npz", help="its scale_mat_0 moves the mesh to world coordinates")
+    ev.add_argument("--no-world", default=False, action="store_true", help="stay in the model's frame even with --cams")
+    ev.add_argument("--all-components", default=False, action="store_true", help="no component selection on the coarse mesh (no-bbox route)")
+    ev.add_argument("--normals", default=False, action="store_true", help="write vertex normals")
     return ap
 
 
@@ -238,11 +440,53 @@ def load(conf_path, checkpoint, device, expdir=None, precision=None):
     return model, state["epoch"], root, plot_block(conf)
 
 
+def eval_bbox(opt):
+    """--bbox FILE.npz --scan_id N: npz[str(N)] * [[1.5], [1.0]], the reference's own scaling of the DTU boxes (plots.py:222), which
+    applies to this route only; --bbox-values: the six numbers as given.  -> float64 [2,3] or None."""
+    if opt.bbox is not None and opt.bbox_values is not None:
+        raise SystemExit("--bbox and --bbox-values exclude each other")
+    if opt.bbox is not None:
+        if opt.scan_id is None:
+            raise SystemExit("--bbox needs --scan_id")
+        with np.load(opt.bbox) as npz:
+            return np.asarray(npz[str(opt.scan_id)], dtype=np.float64).reshape(2, 3) * DTU_BBOX_QUIRK
+    if opt.bbox_values is not None:
+        return np.asarray(opt.bbox_values, dtype=np.float64).reshape(2, 3)
+    return None
+
+
+def main_eval(opt, model, epoch, root, plot):
+    path = eval_out_path(root, epoch, opt.scan_id)
+    if os.path.exists(path) and not opt.overwrite:
+        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+        return 0
+    scale_mat = None
+    if opt.cams is not None and not opt.no_world:
+        with np.load(opt.cams) as npz:
+            scale_mat = np.asarray(npz["scale_mat_0"], dtype=np.float64)
+    timings = {}
+    res = eval_surface(model, opt.resolution or EVAL_RESOLUTION, tuple(opt.grid_boundary) if opt.grid_boundary else None, level=opt.level,
+                       bbox=eval_bbox(opt), take_components=not opt.all_components, scale_mat=scale_mat, normals=opt.normals, plot_conf=plot,
+                       timings=timings)
+    print(", ".join("{} {:.3f} s".format(name, timings[key]) for name, key in (("coarse", "coarse_s"), ("frame", "frame_s"), ("fine grid", "grid_s"),
+          ("extraction", "extract_s"), ("cut", "cut_s"), ("components", "components_s")) if key in timings), flush=True)
+    if res is None:
+        print("a grid does not cross level {} (or the box cuts everything away): no surface, nothing written".format(opt.level), flush=True)
+        return 0
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    write_ply(path, res["verts"], res["faces"], res["normals"])
+    print("{}: {} vertices, {} faces, aligned grid {} x {} x {}".format(path, res["verts"].shape[0], res["faces"].shape[0], *res["frame"]["shape"]),
+          flush=True)
+    return 0
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
     model, epoch, root, plot = load(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
+    if opt.eval:
+        return main_eval(opt, model, epoch, root, plot)
     path = out_path(root, epoch)
     if os.path.exists(path) and not opt.overwrite:
         print("exists: {} (--overwrite to replace it)".format(path), flush=True)

@@ -1212,3 +1212,94 @@ def unit_rows3_(g):
         raise RuntimeError("unit_rows3_: contiguous CUDA float32 [n, 3]")
     _lib.check(_lib.lib().neat_unit_rows3(_p(g), g.shape[0], _stream()), "neat_unit_rows3")
     return g
+
+
+# ---- evaluation mesh (neat_amd/mesh.py eval_surface; csrc/kernels_evalmesh.hpp): no gradient -----------------------------------------
+def _f64s(values, n, what):
+    flat = [float(v) for row in values for v in (row if hasattr(row, "__len__") else (row,))]
+    if len(flat) != n:
+        raise ValueError("%s: %d numbers, got %d" % (what, n, len(flat)))
+    return (ctypes.c_double * n)(*flat)
+
+
+def _mesh_pair(verts, faces):
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("a mesh: verts [nv, 3] float32 and faces [nf, 3] int32")
+    return _f32c(verts.detach()), _i32(faces)
+
+
+def grid_points_affine(x_fm, ldp, first_node, count, n, b0, b1, R, c):
+    """grid_points in a frame: node with local coordinates p (the linspace rule, float64) -> c + R^T p, R [3,3] and c [3] on the host."""
+    cn, c0, c1, _ = _axes3(n, b0, b1)
+    _lib.check(_lib.lib().neat_grid_points_affine(_p(x_fm), int(ldp), int(first_node), int(count), cn, c0, c1, _f64s(R, 9, "R"), _f64s(c, 3, "c"),
+                                                  _stream()), "neat_grid_points_affine")
+
+
+def mesh_moments(verts, faces, origin):
+    """-> float64 [10] on the HOST: area, first moments (3), second moments (xx, xy, xz, yy, yz, zz) of the surface about `origin`
+    (one read-back of 10 numbers and the flag).  A non-finite vertex or an index outside the vertices raises."""
+    verts, faces = _mesh_pair(verts, faces)
+    lib, dev = _lib.lib(), verts.device
+    nf = faces.shape[0]
+    ws = _ws(lib.neat_mesh_moments_ws_bytes(nf), dev)
+    out = torch.empty(10, device=dev, dtype=torch.float64)
+    flag = torch.empty(1, device=dev, dtype=torch.int32)
+    _lib.check(lib.neat_mesh_moments(_p(verts) if verts.shape[0] else None, verts.shape[0], _p(faces) if nf else None, nf,
+                                     _f64s(origin, 3, "origin"), _p(ws), _p(out), _p(flag), _stream()), "neat_mesh_moments")
+    if int(flag.item()) != 0:
+        raise RuntimeError("mesh_moments: a triangle has a non-finite vertex or an index outside the vertices")
+    return out.cpu().numpy()
+
+
+def affine_rows3_(verts, A):
+    """Rows of verts [n,3] (contiguous float32, device) become A [v; 1] in place, A [3,4] float64 on the host."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32 or not verts.is_cuda or not verts.is_contiguous():
+        raise RuntimeError("affine_rows3_: contiguous CUDA float32 [n, 3]")
+    _lib.check(_lib.lib().neat_affine_rows3(_p(verts), verts.shape[0], _f64s(A, 12, "A"), _stream()), "neat_affine_rows3")
+    return verts
+
+
+def affine_bounds3(verts, A):
+    """-> float64 [6] on the device: min (3) and max (3) of A [v; 1] over the rows of verts [n >= 1, 3]; verts is not written."""
+    verts = _f32c(verts.detach())
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError("affine_bounds3: verts [n >= 1, 3]")
+    lib = _lib.lib()
+    ws = torch.empty(lib.neat_affine_bounds3_ws_bytes() // 8, device=verts.device, dtype=torch.float64)
+    out = torch.empty(6, device=verts.device, dtype=torch.float64)
+    _lib.check(lib.neat_affine_bounds3(_p(verts), verts.shape[0], _f64s(A, 12, "A"), _p(ws), _p(out), _stream()), "neat_affine_bounds3")
+    return out
+
+
+def mesh_cut(verts, faces, axis, value, sign):
+    """The part of a mesh in the half-space sign (x[axis] - value) >= 0, value a float32 -> (verts, faces); cut vertices are shared by
+    the faces on both sides of a crossing edge.  The kernels classify, place the cut vertices and emit; the unique ascending edge keys
+    and the two exclusive scans between them are torch integer ops.  One read-back of the three counts."""
+    verts, faces = _mesh_pair(verts, faces)
+    nv, nf, dev = verts.shape[0], faces.shape[0], verts.device
+    if nv == 0 or nf == 0:
+        return verts.new_zeros(0, 3), faces.new_zeros(0, 3)
+    lib = _lib.lib()
+    fcnt = torch.empty(nf, device=dev, dtype=torch.int32)
+    ekey = torch.empty(2 * nf, device=dev, dtype=torch.int64)
+    used = torch.empty(nv, device=dev, dtype=torch.int32)
+    value = ctypes.c_float(value).value                      # the plane, rounded to float32
+    _lib.check(lib.neat_mesh_cut_count(_p(verts), nv, _p(faces), nf, int(axis), value, int(sign), _p(fcnt), _p(ekey), _p(used), _stream()),
+               "neat_mesh_cut_count")
+    ukey = torch.unique(ekey[ekey >= 0])                      # sorted ascending
+    vinc = torch.cumsum(used, 0)
+    finc = torch.cumsum(fcnt, 0)
+    nkeep, nf_out = int(vinc[-1]), int(finc[-1])
+    ncut = int(ukey.shape[0])
+    if nkeep + ncut >= 2 ** 31 or nf_out >= 2 ** 31:
+        raise RuntimeError("mesh_cut: more vertices or faces than int32 indexes")
+    if nf_out == 0:
+        return verts.new_zeros(0, 3), faces.new_zeros(0, 3)
+    vmap = (vinc - used).to(torch.int32)
+    foff = (finc - fcnt).to(torch.int32)
+    out_v = torch.empty(nkeep + ncut, 3, device=dev)
+    out_f = torch.empty(nf_out, 3, device=dev, dtype=torch.int32)
+    _lib.check(lib.neat_mesh_cut_emit(_p(verts), nv, _p(faces), nf, int(axis), value, int(sign), _p(used), _p(vmap), _p(foff),
+                                      _p(ukey) if ncut else None, ncut, nkeep, _p(out_v), nkeep + ncut, _p(out_f), nf_out, _stream()),
+               "neat_mesh_cut_emit")
+    return out_v, out_f
