@@ -6,7 +6,6 @@ Float64 removes the oracle's own rounding from the comparison, so every number m
 bars are the existing ones for the same quantity (TOL for the fp32-grade builds, the 2e-3 / F16X3_GAIN_BAR gradient bars,
 HALF_BOUNDS / BF16_GRAD_REL_L2 for the 16-bit builds) or tighter where the float64 measurement showed the build far inside them.
 NEAT_F64_TABLE=<path> writes every measured error as JSON lines (build, entry point, size, error)."""
-import json
 import os
 
 import pytest
@@ -14,6 +13,7 @@ import torch
 
 from neat_amd import synth
 from tests import f64_reference as ref
+from tests.f64_table import check, record, rel_err, write_table  # noqa: F401  (write_table: the NEAT_F64_TABLE writer, autouse)
 from tests.test_gpu_parity import BF16_GRAD_REL_L2, F16X3_GAIN_BAR, HALF_BOUNDS, TOL, build_model, close_sampler
 
 pytestmark = pytest.mark.gpu
@@ -41,23 +41,6 @@ GRAD_MAX_BAR = {"fp32": 1e-3, "fp16x3": 2e-3, "bf16x3": 2e-2}
 SDF_GRAD_MAX_BAR_FP32 = 5e-5
 GRAD_REL_L2 = {"fp16": HALF_BOUNDS["fp16"][4], "bf16": BF16_GRAD_REL_L2}
 
-_TABLE = []
-
-
-def record(build, entry, P, err):
-    _TABLE.append({"build": build, "entry": entry, "P": P, "err": float(err)})
-    return err
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_table():
-    yield
-    path = os.environ.get("NEAT_F64_TABLE")
-    if path and _TABLE:
-        with open(path, "a") as f:
-            for row in _TABLE:
-                f.write(json.dumps(row) + "\n")
-
 
 @pytest.fixture(scope="module")
 def dev():
@@ -75,21 +58,6 @@ def model(dev, build):
     if m is None:
         m = _MODELS[build] = build_model(dev, VARIANT, seed=SEED, precision=build)
     return m
-
-
-def rel_err(a, b):
-    """max |a - b| relative to max(1, max |b|) (test_gpu_parity.close's measure); a may live on the GPU, b is float64."""
-    a = a.detach().cpu().to(torch.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    assert torch.isfinite(a).all(), "non-finite values"
-    if a.numel() == 0:
-        return 0.0
-    return float((a - b).abs().max()) / max(1.0, float(b.abs().max()))
-
-
-def check(build, entry, P, a, b, bar):
-    err = record(build, entry, P, rel_err(a, b))
-    assert err <= bar, f"{build} {entry} P={P}: err {err:.3e} > {bar:.1e}"
 
 
 def points(n, seed=0):
