@@ -597,6 +597,39 @@ int neat_frame_range(const float* x, long long n, void* ws, float* range, void* 
 int neat_frame_grey(const float* x, long long n, const float* range, unsigned char* out, void* stream);
 int neat_frame_grid(const unsigned char* images, int N, int H, int W, int nrow, unsigned char* canvas, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): sphere tracing of an SDF along rays (neat_amd/trace.py).  The
+ * SDF is queried by the caller between these launches (the raw network: neat_sdf_forward with radius 0, or any field); these are the
+ * per-ray state machine and the ordered compaction of the rays that still need a query.  Definitions: neat_amd/csrc/kernels_trace.hpp,
+ * DESIGN 3f; tests/trace_f64.py restates them in float64.  Asynchronous on the stream, no allocation, no atomics: two runs give the same
+ * lists and the same bytes.  Bad arguments return -1 before any launch.  States: 0 MISS, 1 HIT, 2 INSIDE, 3 UNCONVERGED.
+ *
+ * ws = neat_trace_ws_bytes(R) bytes (0 for R < 1 or R > 2^24: the scan of the per-workgroup counts is one workgroup walking
+ * ceil(R / 256) entries, 64 rounds at the cap; trace more rays in chunks, as neat_amd.trace.rays does), 256-byte aligned, kept from init to finish.  ctl: two int64 in device memory, ctl[0] = the
+ * length of the current active list, ctl[1] = the evaluations asked for so far (the sum of those lengths).  The caller reads ctl[0]
+ * after init and after every step, queries the SDF at points [ctl[0], 3] (row-major; `points` needs room for R rows) and hands the
+ * values to the next step, with parity 0 for the first step and alternating from there; it stops at ctl[0] = 0.
+ * neat_trace_list_offset : the byte offset in ws of active list `parity` (int32 ray ids; the list the step with that parity reads);
+ *   0 for bad arguments (no list starts at 0).
+ * neat_trace_init   : origins, dirs [R,3] (|dir| = 1), t_end [R] or null; the sphere chord and its clip to [near, t_end] in float64,
+ *   the first state, the first active list (ray order) and its query points.
+ * neat_trace_step   : values [n] of the current list's points, n <= R (entries past the device's own count are ignored); advances
+ *   each ray, writes the next list (ray order kept), its points and ctl.
+ * neat_trace_finish : depth [R] (NaN unless HIT or INSIDE), state [R] bytes, steps [R] (queries made per ray), hit_points [R,3] (NaN rows
+ *   likewise); each may be null.  A ray still active reads UNCONVERGED.
+ * neat_trace_target_rays : the rays from F centres [F,3] towards N x S targets: target (n, j) = a + j / (S - 1) (b - a) of row n =
+ *   [a | b] (`stride` >= 6 floats per row; S = 1: the point a, stride >= 3), float64 arithmetic.  Ray (f N + n) S + j: origin the
+ *   centre, unit direction, t_end = |p - c| - bias, ok = 1 iff |p| <= radius and |p - c| >= near + bias. */
+size_t neat_trace_ws_bytes(int R);
+size_t neat_trace_list_offset(int R, int parity);
+int neat_trace_init(const float* origins, const float* dirs, const float* t_end, int R, double radius, double near, void* ws, float* points,
+                    long long* ctl, void* stream);
+int neat_trace_step(const float* origins, const float* dirs, const float* values, int n, int R, int parity, float eps, float relax,
+                    int max_steps, int refine_steps, void* ws, float* points, long long* ctl, void* stream);
+int neat_trace_finish(const float* origins, const float* dirs, int R, void* ws, float* depth, unsigned char* state, int* steps,
+                      float* hit_points, void* stream);
+int neat_trace_target_rays(const float* centres, int F, const float* rows, int stride, int N, int S, double radius, double near, double bias,
+                           float* origins, float* dirs, float* t_end, unsigned char* ok, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

@@ -170,6 +170,14 @@ _SIGNATURES = {
     "neat_frame_range": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
     "neat_frame_grey": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
     "neat_frame_grid": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
+    "neat_trace_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "neat_trace_list_offset": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "neat_trace_init": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_fp, c_fp, c_fp, c_fp]),
+    "neat_trace_step": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                       ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
+    "neat_trace_finish": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_trace_target_rays": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

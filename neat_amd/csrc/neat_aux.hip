@@ -11,6 +11,7 @@
 #include "kernels_eval.hpp"
 #include "kernels_show.hpp"
 #include "kernels_frame.hpp"
+#include "kernels_trace.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -1086,6 +1087,88 @@ int neat_frame_grid(const unsigned char* images, int N, int H, int W, int nrow, 
   if (cw3 > (long long)INT_MAX || ch > (long long)INT_MAX || !frame_blocks_ok(ch * cw3)) return -1;
   hipLaunchKernelGGL(frame_grid_kernel, frame_blocks(ch * cw3), dim3(FRAME_WG), 0, (hipStream_t)stream, images, N, H, W, xmaps, pad, ch * cw3, (int)cw3,
                      canvas);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: sphere tracing of an SDF along rays (kernels_trace.hpp) ------------------------------------------------------------
+static inline int trace_tiles(int R) { return (R + TRACE_WG - 1) / TRACE_WG; }
+
+static TraceWs trace_ws(void* ws, int R) {
+  TraceWs w{};
+  char* p = (char*)ws;
+  const size_t fl = parse_al((size_t)R * sizeof(float)), by = parse_al((size_t)R);
+  float** fp[6] = {&w.t, &w.ta, &w.fa, &w.tb, &w.fb, &w.t1};
+  for (auto f : fp) { *f = (float*)p; p += fl; }
+  int** ip[5] = {&w.steps, &w.march, &w.refine, &w.ids[0], &w.ids[1]};
+  for (auto i : ip) { *i = (int*)p; p += fl; }
+  w.phase = (unsigned char*)p; p += by;
+  w.side = (unsigned char*)p; p += by;
+  w.flag = (unsigned char*)p; p += by;
+  w.tile = (int*)p;
+  return w;
+}
+
+constexpr int TRACE_MAX_RAYS = 1 << 24;      // trace_scan_kernel is one workgroup of 1024 over ceil(R / 256) counts: 64 rounds at most
+
+size_t neat_trace_ws_bytes(int R) {
+  if (R < 1 || R > TRACE_MAX_RAYS) return 0;
+  return 11 * parse_al((size_t)R * sizeof(float)) + 3 * parse_al((size_t)R) + parse_al((size_t)trace_tiles(R) * sizeof(int));
+}
+
+size_t neat_trace_list_offset(int R, int parity) {
+  if (R < 1 || R > TRACE_MAX_RAYS || (parity != 0 && parity != 1)) return 0;
+  char base[1];
+  const TraceWs w = trace_ws(base, R);
+  return (size_t)((char*)w.ids[parity] - base);
+}
+
+static inline bool trace_common(const float* origins, const float* dirs, int R, void* ws) {
+  return origins && dirs && R >= 1 && R <= TRACE_MAX_RAYS && ws && !((uintptr_t)ws & 255);
+}
+
+int neat_trace_init(const float* origins, const float* dirs, const float* t_end, int R, double radius, double near, void* ws, float* points,
+                    long long* ctl, void* stream) {
+  if (!trace_common(origins, dirs, R, ws) || !points || !ctl || !(radius > 0.0) || !std::isfinite(radius) || !std::isfinite(near)) return -1;
+  const TraceWs w = trace_ws(ws, R);
+  const int tiles = trace_tiles(R);
+  hipLaunchKernelGGL(trace_init_kernel, dim3(tiles), dim3(TRACE_WG), 0, (hipStream_t)stream, w, origins, dirs, t_end, R, radius, near);
+  hipLaunchKernelGGL(trace_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w.tile, tiles, ctl, 1);
+  hipLaunchKernelGGL(trace_emit_kernel, dim3(tiles), dim3(TRACE_WG), 0, (hipStream_t)stream, w, (const int*)nullptr, w.ids[0], R, R, origins, dirs,
+                     points);
+  return (int)hipGetLastError();
+}
+
+int neat_trace_step(const float* origins, const float* dirs, const float* values, int n, int R, int parity, float eps, float relax,
+                    int max_steps, int refine_steps, void* ws, float* points, long long* ctl, void* stream) {
+  if (!trace_common(origins, dirs, R, ws) || !points || !ctl || n < 0 || n > R || (n > 0 && !values) || (parity != 0 && parity != 1)) return -1;
+  if (!(eps > 0.f) || !(relax > 0.f) || !std::isfinite(eps) || !std::isfinite(relax) || max_steps < 0 || refine_steps < 0 || refine_steps > 64) return -1;
+  const TraceWs w = trace_ws(ws, R);
+  const int tiles = std::max(trace_tiles(n), 1);
+  hipLaunchKernelGGL(trace_advance_kernel, dim3(tiles), dim3(TRACE_WG), 0, (hipStream_t)stream, w, (const int*)w.ids[parity], values, n, R,
+                     (const long long*)ctl, eps, relax, max_steps, refine_steps);
+  hipLaunchKernelGGL(trace_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w.tile, tiles, ctl, 0);
+  hipLaunchKernelGGL(trace_emit_kernel, dim3(tiles), dim3(TRACE_WG), 0, (hipStream_t)stream, w, (const int*)w.ids[parity], w.ids[parity ^ 1], n, R,
+                     origins, dirs, points);
+  return (int)hipGetLastError();
+}
+
+int neat_trace_finish(const float* origins, const float* dirs, int R, void* ws, float* depth, unsigned char* state, int* steps,
+                      float* hit_points, void* stream) {
+  if (!trace_common(origins, dirs, R, ws)) return -1;
+  hipLaunchKernelGGL(trace_finish_kernel, dim3(trace_tiles(R)), dim3(TRACE_WG), 0, (hipStream_t)stream, trace_ws(ws, R), origins, dirs, R, depth,
+                     state, steps, hit_points);
+  return (int)hipGetLastError();
+}
+
+int neat_trace_target_rays(const float* centres, int F, const float* rows, int stride, int N, int S, double radius, double near, double bias,
+                           float* origins, float* dirs, float* t_end, unsigned char* ok, void* stream) {
+  if (F < 0 || N < 0 || S < 1 || stride < (S > 1 ? 6 : 3) || !std::isfinite(radius) || !std::isfinite(near) || !std::isfinite(bias)) return -1;
+  const long long total = (long long)F * N * S;
+  if (total > (long long)INT_MAX) return -1;
+  if (total == 0) return 0;
+  if (!centres || !rows || !origins || !dirs || !t_end || !ok) return -1;
+  hipLaunchKernelGGL(trace_target_rays_kernel, dim3((unsigned)((total + TRACE_WG - 1) / TRACE_WG)), dim3(TRACE_WG), 0, (hipStream_t)stream, centres, F,
+                     rows, stride, N, S, radius, near, bias, origins, dirs, t_end, ok);
   return (int)hipGetLastError();
 }
 

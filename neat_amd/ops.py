@@ -1303,3 +1303,70 @@ def mesh_cut(verts, faces, axis, value, sign):
                                       _p(ukey) if ncut else None, ncut, nkeep, _p(out_v), nkeep + ncut, _p(out_f), nf_out, _stream()),
                "neat_mesh_cut_emit")
     return out_v, out_f
+
+
+# ---- sphere tracing (neat_amd/trace.py; csrc/kernels_trace.hpp): no gradient; the caller reads the active count once per iteration -------
+TRACE_MISS, TRACE_HIT, TRACE_INSIDE, TRACE_UNCONVERGED = 0, 1, 2, 3
+TRACE_MAX_RAYS = 1 << 24           # per batch (neat_trace_ws_bytes); trace.rays chunks
+
+
+class TraceRun:
+    """The device state of one batch of R >= 1 rays between neat_trace_init and neat_trace_finish: the workspace, the query points
+    [R, 3] (the first `count` rows are the pending query), ctl = (active count, evaluations so far) as two int64 on the device."""
+
+    def __init__(self, origins, dirs, t_end, radius, near):
+        lib = _lib.lib()
+        self.origins, self.dirs = _f32c(origins.detach()), _f32c(dirs.detach())
+        self.R = R = int(self.origins.shape[0])
+        if self.origins.shape != (R, 3) or self.dirs.shape != (R, 3) or not 1 <= R <= TRACE_MAX_RAYS:
+            raise ValueError("trace: origins and dirs [R, 3], 1 <= R <= 2^24 per batch")
+        self.t_end = None if t_end is None else _f32c(t_end.detach()).reshape(-1)
+        if self.t_end is not None and self.t_end.shape[0] != R:
+            raise ValueError("trace: t_end [R]")
+        dev = self.origins.device
+        self.ws = _ws(lib.neat_trace_ws_bytes(R), dev)
+        self.points = torch.empty(R, 3, device=dev)
+        self.ctl = torch.empty(2, device=dev, dtype=torch.int64)
+        self.parity = 0
+        _lib.check(lib.neat_trace_init(_p(self.origins), _p(self.dirs), _p(self.t_end), R, float(radius), float(near), _p(self.ws), _p(self.points),
+                                       _p(self.ctl), _stream()), "neat_trace_init")
+
+    def count(self):
+        """The length of the current active list (the one read-back of an iteration)."""
+        return int(self.ctl[0].item())
+
+    def active(self, n):
+        """The current active list: n ray ids, int32 on the device (a view of the workspace)."""
+        first = int(_lib.lib().neat_trace_list_offset(self.R, self.parity))
+        return self.ws[first:first + 4 * n].view(torch.int32)
+
+    def step(self, values, n, eps, relax, max_steps, refine_steps):
+        values = _f32c(values.detach()).reshape(-1)
+        if values.shape[0] != n:
+            raise ValueError("trace: the field returned %d values for %d points" % (values.shape[0], n))
+        _lib.check(_lib.lib().neat_trace_step(_p(self.origins), _p(self.dirs), _p(values), int(n), self.R, self.parity, float(eps), float(relax),
+                                              int(max_steps), int(refine_steps), _p(self.ws), _p(self.points), _p(self.ctl), _stream()),
+                   "neat_trace_step")
+        self.parity ^= 1
+
+    def finish(self, depth, state, steps, hit_points):
+        """Into contiguous [R] float32 / uint8 / int32 and [R, 3] float32 views."""
+        _lib.check(_lib.lib().neat_trace_finish(_p(self.origins), _p(self.dirs), self.R, _p(self.ws), _p(depth), _p(state), _p(steps),
+                                                _p(hit_points), _stream()), "neat_trace_finish")
+
+    def evals(self):
+        return int(self.ctl[1].item())
+
+
+def trace_target_rays(centres, rows, samples, radius, near, bias):
+    """centres [F,3], rows [N,3] (samples = 1) or [N,6] segments -> (origins [F N S,3], dirs, t_end [F N S], ok uint8 [F N S])."""
+    centres, rows = _f32c(centres.detach()), _f32c(rows.detach())
+    F, N, S = int(centres.shape[0]), int(rows.shape[0]), int(samples)
+    if centres.shape != (F, 3) or rows.dim() != 2 or rows.shape[1] != (3 if S == 1 else 6) or S < 1:
+        raise ValueError("trace_target_rays: centres [F,3] and rows [N,3] (one sample) or [N,6] (segments)")
+    dev, T = rows.device, F * N * S
+    o, d = torch.empty(T, 3, device=dev), torch.empty(T, 3, device=dev)
+    t_end, ok = torch.empty(T, device=dev), torch.empty(T, device=dev, dtype=torch.uint8)
+    _lib.check(_lib.lib().neat_trace_target_rays(_p(centres), F, _p(rows), int(rows.shape[1]), N, S, float(radius), float(near), float(bias),
+                                                 _p(o), _p(d), _p(t_end), _p(ok), _stream()), "neat_trace_target_rays")
+    return o, d, t_end, ok

@@ -3,7 +3,7 @@ PSNR per view (the reference's code/evaluation/eval.py --eval_rendering, which w
 psnr_{epoch}.csv, and the pictures of the trainer's do_vis branch, code/training/volsdf_train.py:300-332 with utils/plots.py:362-396):
 
     python -m neat_amd.render --conf <run>/runconf.conf [--checkpoint latest] [--views all|0,5,10] [--chunksize N]
-        [--maps rgb,normal,depth] [--depth-range LO HI] [--save-depth] [--cam-json cam.json --width W --height H --fov 60]
+        [--maps rgb,normal,depth] [--surface] [--depth-range LO HI] [--save-depth] [--cam-json cam.json --width W --height H --fov 60]
         [--expdir <run>] [--data_root ../data] [--scan_id -1] [--gpu 0] [--precision P] [--json] [--overwrite]
 
 A view is walked in chunks of `chunksize` pixels: VolSDFNetwork.render_pixels (camera rays, sampler, main pass: the eval forward without
@@ -14,6 +14,9 @@ the byte rules are DESIGN 3e, restated in numpy by tests/render_f64.py.  The hos
 
 Files: <run>/rendering_{epoch}/eval_{idx:03d}.png (the reference's name), normal_{idx:03d}.png, depth_{idx:03d}.png, depth_{idx:03d}.npy
 under --save-depth, and <run>/psnr_{epoch}.csv; epoch is read from the checkpoint.  Existing files are kept unless --overwrite.
+--surface (or `surface` among --maps) adds surface_depth_{idx:03d}.png and surface_normal_{idx:03d}.png (surface_depth_{idx:03d}.npy under
+--save-depth): depth and unit normal of the first hit of each pixel's ray with the raw SDF's zero level (neat_amd.trace.view),
+NaN / zero where the ray hits nothing; --maps surface alone runs no volumetric forward.
 --cam-json takes the list of 4 x 4 world-to-camera matrices that neat_amd.show writes as cam.json, with --width --height --fov
 (show.intrinsics); pose = inverse(w2c); no PSNR on this route.
 
@@ -34,6 +37,7 @@ import torch
 from . import _lib
 
 MAPS = ("rgb", "normal", "depth")
+SURFACE = "surface"            # --maps surface / --surface: the sphere-traced first hit (neat_amd.trace.view), not a map of the volumetric forward
 DEFAULT_CHUNK = 10000          # eval.py:80
 
 
@@ -266,6 +270,29 @@ def out_paths(run_dir, epoch, idx, maps=MAPS, save_depth=False):
     return paths
 
 
+def surface_paths(run_dir, epoch, idx, save_depth=False):
+    """-> {"surface_depth": .../surface_depth_{idx:03d}.png, "surface_normal": ..., "surface_depth_npy": ... under save_depth}."""
+    d = out_dir(run_dir, epoch)
+    paths = {"surface_depth": os.path.join(d, "surface_depth_%03d.png" % idx), "surface_normal": os.path.join(d, "surface_normal_%03d.png" % idx)}
+    if save_depth:
+        paths["surface_depth_npy"] = os.path.join(d, "surface_depth_%03d.npy" % idx)
+    return paths
+
+
+def surface_view(model, pose, intrinsics, H, W, depth_range=None, timings=None):
+    """The first hit of every pixel's ray (trace.view) as frames -> dict: "depth" float32 [H,W] (NaN off the surface), "depth8" uint8 [H,W]
+    (grey over depth_range, default the finite range of the plane: depth_*.png's rule), "normal" uint8 [H,W,3] (byte((n + 1) / 2), a zero
+    normal off the surface), "state" uint8 [H,W]."""
+    from . import trace
+    depth, normal, state = trace.view(model, pose, intrinsics, H, W, timings=timings)
+    dev = depth.device
+    with torch.cuda.device(dev):
+        rng = torch.tensor([float(depth_range[0]), float(depth_range[1])], dtype=torch.float32).to(dev) if depth_range is not None else frame_range(depth)
+        normal8 = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+        frame_put(None, normal.reshape(-1, 3), None, None, 0, H * W, normal8=normal8)
+        return {"depth": depth, "depth8": frame_grey(depth, rng), "normal": normal8, "state": state}
+
+
 def csv_path(run_dir, epoch):
     return os.path.join(run_dir, "psnr_{}.csv".format(epoch))
 
@@ -296,7 +323,8 @@ def build_parser():
     ap.add_argument("--checkpoint", default="latest", type=str, help="the trained model checkpoint to render")
     ap.add_argument("--views", default="all", type=str, help="`all` or comma-separated view indices of the dataset")
     ap.add_argument("--chunksize", default=None, type=int, help="pixels per chunk (default: the conf's train.split_n_pixels, else 10000)")
-    ap.add_argument("--maps", default=",".join(MAPS), type=str, help="comma-separated subset of rgb,normal,depth")
+    ap.add_argument("--maps", default=",".join(MAPS), type=str, help="comma-separated subset of rgb,normal,depth (and surface: see --surface)")
+    ap.add_argument("--surface", default=False, action="store_true", help="also write the sphere-traced surface depth and normal frames")
     ap.add_argument("--depth-range", default=None, type=float, nargs=2, metavar=("LO", "HI"), help="grey scale of the depth picture (default: its finite range)")
     ap.add_argument("--save-depth", default=False, action="store_true", help="write the float32 depth plane as depth_{idx:03d}.npy too")
     ap.add_argument("--cam-json", default=None, type=str, help="a JSON list of 4x4 world-to-camera matrices (neat_amd.show's cam.json), one frame each")
@@ -318,8 +346,10 @@ def parse_args(argv=None):
     ap = build_parser()
     opt = ap.parse_args(argv)
     opt.maps = tuple(m for m in opt.maps.split(",") if m)
-    if not opt.maps or set(opt.maps) - set(MAPS):
-        ap.error("--maps: a comma-separated subset of " + ",".join(MAPS))
+    if not opt.maps or set(opt.maps) - set(MAPS) - {SURFACE}:
+        ap.error("--maps: a comma-separated subset of " + ",".join(MAPS + (SURFACE,)))
+    opt.surface = opt.surface or SURFACE in opt.maps
+    opt.maps = tuple(m for m in opt.maps if m != SURFACE)
     if opt.cam_json is not None and (opt.width is None or opt.height is None):
         ap.error("--cam-json needs --width and --height")
     if opt.chunksize is not None and opt.chunksize < 1:
@@ -369,7 +399,9 @@ def main(argv=None):
             raise SystemExit("--views: %s out of range (the dataset has %d views)" % (bad, len(dataset)))
     scan_id = opt.scan_id if opt.scan_id != -1 else conf.get_int("dataset.scan_id", default=-1)
     targets = [out_paths(root, epoch, idx, opt.maps, opt.save_depth) for idx in views]
-    every = [p for t in targets for p in t.values()] + ([csv_path(root, epoch)] if dataset is not None else [])
+    surf = [surface_paths(root, epoch, idx, opt.save_depth) if opt.surface else {} for idx in views]
+    with_csv = dataset is not None and bool(opt.maps)             # --maps surface alone: no forward, hence no PSNR
+    every = [p for t in targets + surf for p in t.values()] + ([csv_path(root, epoch)] if with_csv else [])
     if not opt.overwrite and all(os.path.exists(p) for p in every):
         print("exists: all {} files under {} (--overwrite to replace them)".format(len(every), out_dir(root, epoch)), flush=True)
         if opt.json:
@@ -377,14 +409,15 @@ def main(argv=None):
         return 0
     os.makedirs(out_dir(root, epoch), exist_ok=True)
     psnrs, render_s, encode_s, written = [], 0.0, 0.0, 0
-    for idx, paths in zip(views, targets):
+    trace_s, trace_evals = 0.0, 0
+    for idx, paths, spaths in zip(views, targets, surf):
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
         if dataset is not None:
             uv, pose, K, gt, H, W = dataset_view(dataset, idx, device)
         else:
             (uv, pose, K), gt, H, W = camera_view(cams[idx], opt.width, opt.height, opt.fov, device), None, opt.height, opt.width
-        res = view(model, uv, pose, K, H, W, gt=gt, chunksize=chunksize, maps=opt.maps, depth_range=opt.depth_range)
+        res = view(model, uv, pose, K, H, W, gt=gt, chunksize=chunksize, maps=opt.maps, depth_range=opt.depth_range) if opt.maps else {"psnr": None}
         torch.cuda.synchronize(device)
         t1 = time.perf_counter()
         for m, key in (("rgb", "rgb"), ("normal", "normal"), ("depth", "depth8")):
@@ -394,6 +427,16 @@ def main(argv=None):
             np.save(paths["depth_npy"], res["depth"].cpu().numpy())
             written += 1
         render_s, encode_s = render_s + (t1 - t0), encode_s + (time.perf_counter() - t1)
+        if opt.surface:
+            tm = {}
+            sres = surface_view(model, pose, K, H, W, depth_range=opt.depth_range, timings=tm)
+            trace_s, trace_evals = trace_s + tm["trace_s"], trace_evals + tm["evals"]
+            t2 = time.perf_counter()
+            written += write_png(spaths["surface_depth"], sres["depth8"], opt.overwrite) + write_png(spaths["surface_normal"], sres["normal"], opt.overwrite)
+            if "surface_depth_npy" in spaths and (opt.overwrite or not os.path.exists(spaths["surface_depth_npy"])):
+                np.save(spaths["surface_depth_npy"], sres["depth"].cpu().numpy())
+                written += 1
+            encode_s += time.perf_counter() - t2
         if res["psnr"] is not None:
             psnrs.append(res["psnr"])
     report = {"epoch": int(epoch), "views": views, "chunksize": int(chunksize), "render_s": render_s, "encode_s": encode_s, "written": written,
@@ -406,6 +449,9 @@ def main(argv=None):
         report.update(psnr=[float(v) for v in psnrs], mean=float(rows[-2]), std=float(rows[-1]))
     print("{} views of the checkpoint of epoch {} -> {}: rendering {:.3f} s, encoding {:.3f} s".format(len(views), epoch, out_dir(root, epoch),
                                                                                                       render_s, encode_s), flush=True)
+    if opt.surface:
+        report.update(trace_s=trace_s, trace_evals=int(trace_evals))
+        print("surface frames: tracing {:.3f} s, {} SDF evaluations".format(trace_s, trace_evals), flush=True)
     if opt.json:
         print(json.dumps(report), flush=True)
     return 0
