@@ -630,6 +630,47 @@ int neat_trace_finish(const float* origins, const float* dirs, int R, void* ws, 
 int neat_trace_target_rays(const float* centres, int F, const float* rows, int stride, int N, int S, double radius, double near, double bias,
                            float* origins, float* dirs, float* t_end, unsigned char* ok, void* stream);
 
+/* ---- added to ABI v15 (new symbols only): fuse, refine and snap of a parsed line soup against the views' 2-D detections
+ * (code/evaluation/fusion.py :79-141, refinement.py :95-198, nms.py :156-204; neat_amd/post.py).  fp32, no atomics, fixed-shape
+ * reductions: two runs give the same bytes.  No entry point synchronises with the host; counts that depend on the data are device memory.
+ *
+ * Shared inputs: lines [n,2,3]; det = the views' detections packed, row stride det_stride floats (x1, y1, x2, y2, score, ...), view v's at
+ * rows [det_off[v], det_off[v+1]) (det_off [V+1] int32 on the device, mtot rows in all); K3 [V,3,3], w2c [V,3,4] (neat_camera_mats).
+ * A line's cost in a view = min over the detections and both orientations of the squared 4-vector distance of its projection
+ * (lowest detection on ties; a row with a NaN distance never matches; a view without detections sees nothing).
+ *
+ * neat_post_fuse, all views in one launch: a line is available in a view if its cost < dis_threshold.  It then receives the score
+ *   (det column 4) of detection number r of that view, r = the RANK of its detection among the detections matched in that view
+ *   (by_label = 0, the reference's enumerate) or r = its detection (by_label = 1), summed in view order; count [n] int32 = views that saw
+ *   it, score [n] = sum / max(count, 1), keep [n] bytes = score > keep_threshold, kept [n,2,3] = those lines in order, *n_kept of them.
+ *   ws: neat_post_fuse_ws_bytes(n, V, mtot).
+ * neat_post_select: out [n,2,3] = the lines with keep[i] != 0, in order, *n_out of them (refine's pre-filter).  ws: n ints.
+ * neat_post_refine_view, one view of the sequential walk: cur [ncap,2,3] holds *n_cur lines.  A line is possible if its projection lies
+ *   in [0,width] x [0,height] (inclusive) and its cost < dis_threshold; it is reversed if the reversed orientation is strictly the closer at
+ *   its detection.  next [ncap,2,3] = the lines that are not possible, in order, then the mean of the (reversed) members of every matched
+ *   detection in ascending detection order (neat_parse_group's grouping and means); *n_next <= *n_cur.  m = the view's detections
+ *   (<= mmax, the bound ws was sized with).  ws: neat_post_refine_ws_bytes(ncap, mmax).
+ * neat_post_snap: end points -> cells of a G^3 grid over their bounding box (2 <= G <= 1024, anything else is refused before any
+ *   launch): delta = (max - min) / (G - 1), cell = rint((p - min) / delta) (IEEE division, half to even; a zero-extent axis has cell 0).
+ *   A cell is a peak if it holds at least as many end points as every cell of its 3x3x3 neighbourhood inside the grid; junctions [2n,3]
+ *   (capacity) = the peaks in row-major (ix, iy, iz) order at the nodes of torch.linspace(min, max, G) (lo + step i below the middle,
+ *   hi - step (G - 1 - i) from it on, fused multiply-adds), pcount [2n] their end points.  Every end point snaps to the nearest peak (squared
+ *   distance, lowest index on ties).  edges [n,2] int32 / lines_out [n,2,3] = junctions[edges]: the lines whose two end points moved less
+ *   than max_snap (max_snap < 0: all), in line order; with unique = 1 the distinct pairs (min, max) with min != max, ascending.
+ *   counts [2] = (peaks, edges).  ws: neat_post_snap_ws_bytes(n, G) (0 for a refused G). */
+size_t neat_post_fuse_ws_bytes(int n, int V, int mtot);
+int neat_post_fuse(const float* lines, int n, const float* det, int det_stride, const int* det_off, int mtot, const float* K3, const float* w2c,
+                   int V, float dis_threshold, float keep_threshold, int by_label, float* score, int* count, unsigned char* keep, float* kept,
+                   int* n_kept, void* ws, void* stream);
+int neat_post_select(const float* lines, int n, const unsigned char* keep, float* out, int* n_out, void* ws, void* stream);
+size_t neat_post_refine_ws_bytes(int ncap, int mmax);
+int neat_post_refine_view(const float* cur, const int* n_cur, int ncap, const float* det, int det_stride, const int* det_off, int m, int mmax,
+                          const float* K3, const float* w2c, int view, float dis_threshold, float width, float height, float* next, int* n_next,
+                          void* ws, void* stream);
+size_t neat_post_snap_ws_bytes(int n, int G);
+int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique, float* junctions, int* pcount, int* edges, float* lines_out,
+                   int* counts, void* ws, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

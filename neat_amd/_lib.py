@@ -178,6 +178,15 @@ _SIGNATURES = {
     "neat_trace_finish": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_trace_target_rays": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                               ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_post_fuse_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "neat_post_fuse": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float,
+                                      ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_post_select": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_post_refine_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "neat_post_refine_view": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp,
+                                             ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, c_fp]),
+    "neat_post_snap_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "neat_post_snap": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

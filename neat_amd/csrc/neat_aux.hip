@@ -1,6 +1,7 @@
 // C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
 // samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, the evaluation
-// mesh, the evaluation of a reconstruction, the wireframe / mesh pictures, the frames of rendered views, volume weights.
+// mesh, the evaluation of a reconstruction, the wireframe / mesh pictures, the frames of rendered views, the sphere tracer,
+// the fuse / refine / snap post-processing, volume weights.
 // Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
 // boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
 #include "kernels_sampler.hpp"
@@ -12,12 +13,14 @@
 #include "kernels_show.hpp"
 #include "kernels_frame.hpp"
 #include "kernels_trace.hpp"
+#include "kernels_post.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits.h>
 #include <math.h>
+#include <rocprim/device/device_radix_sort.hpp>
 
 using namespace neat;
 
@@ -1169,6 +1172,128 @@ int neat_trace_target_rays(const float* centres, int F, const float* rows, int s
   if (!centres || !rows || !origins || !dirs || !t_end || !ok) return -1;
   hipLaunchKernelGGL(trace_target_rays_kernel, dim3((unsigned)((total + TRACE_WG - 1) / TRACE_WG)), dim3(TRACE_WG), 0, (hipStream_t)stream, centres, F,
                      rows, stride, N, S, radius, near, bias, origins, dirs, t_end, ok);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: fuse, refine and snap of a parsed line soup (kernels_post.hpp) ----------------------------------------------------------
+size_t neat_post_fuse_ws_bytes(int n, int V, int mtot) {
+  PostFuseWs w;
+  return post_fuse_layout(n, V, mtot, &w) ? w.total : 0;
+}
+
+int neat_post_fuse(const float* lines, int n, const float* det, int det_stride, const int* det_off, int mtot, const float* K3, const float* w2c,
+                   int V, float dis_threshold, float keep_threshold, int by_label, float* score, int* count, unsigned char* keep, float* kept,
+                   int* n_kept, void* ws, void* stream) {
+  PostFuseWs w;
+  if (!post_fuse_layout(n, V, mtot, &w) || !n_kept || (by_label != 0 && by_label != 1)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) return (int)hipMemsetAsync(n_kept, 0, sizeof(int), st);
+  if (!lines || !score || !count || !keep || !kept || !ws || (V > 0 && (!det_off || !K3 || !w2c)) || (mtot > 0 && (!det || det_stride < 5))) return -1;
+  int* label = (int*)((char*)ws + w.label);
+  unsigned char* present = (unsigned char*)ws + w.present;
+  int* rank = (int*)((char*)ws + w.rank);
+  if (V > 0) {
+    if (mtot > 0) NEAT_CHECK(hipMemsetAsync(present, 0, (size_t)mtot, st));
+    hipLaunchKernelGGL(post_match_kernel, dim3((n + PARSE_WG - 1) / PARSE_WG, V), dim3(PARSE_WG), 0, st, lines, (const int*)nullptr, n, det,
+                       det_stride, det_off, K3, w2c, 0, dis_threshold, 0, 0.f, 0.f, label, present);
+    hipLaunchKernelGGL(post_rank_kernel, dim3(V), dim3(1024), 0, st, present, det_off, rank);
+  }
+  hipLaunchKernelGGL(post_fuse_score_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, st, label, n, V, det, det_stride, det_off, rank, by_label,
+                     keep_threshold, score, count, keep);
+  hipLaunchKernelGGL(post_keep_kernel, dim3(1), dim3(1024), 0, st, lines, n, keep, (int*)((char*)ws + w.idx), kept, n_kept);
+  return (int)hipGetLastError();
+}
+
+int neat_post_select(const float* lines, int n, const unsigned char* keep, float* out, int* n_out, void* ws, void* stream) {
+  if (n < 0 || n > INT_MAX / 6 || !n_out) return -1;
+  if (n == 0) return (int)hipMemsetAsync(n_out, 0, sizeof(int), (hipStream_t)stream);
+  if (!lines || !keep || !out || !ws) return -1;
+  hipLaunchKernelGGL(post_keep_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, lines, n, keep, (int*)ws, out, n_out);
+  return (int)hipGetLastError();
+}
+
+size_t neat_post_refine_ws_bytes(int ncap, int mmax) {
+  PostRefineWs w;
+  if (ncap < 0 || mmax < 0) return 0;
+  return post_refine_layout(ncap, mmax, neat_parse_group_ws_bytes(ncap, mmax), &w) ? w.total : 0;
+}
+
+int neat_post_refine_view(const float* cur, const int* n_cur, int ncap, const float* det, int det_stride, const int* det_off, int m, int mmax,
+                          const float* K3, const float* w2c, int view, float dis_threshold, float width, float height, float* next, int* n_next,
+                          void* ws, void* stream) {
+  PostRefineWs w;
+  if (ncap < 0 || mmax < 0 || m < 0 || m > mmax || view < 0 || !post_refine_layout(ncap, mmax, neat_parse_group_ws_bytes(ncap, mmax), &w)) return -1;
+  if (ncap == 0) return 0;
+  if (!cur || !n_cur || !next || !n_next || !ws || !det_off || !K3 || !w2c || (m > 0 && (!det || det_stride < 4))) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  char* p = (char*)ws;
+  int* label = (int*)(p + w.label);
+  float* glines = (float*)(p + w.glines);
+  int* gcount = (int*)(p + w.gcount);
+  hipLaunchKernelGGL(post_match_kernel, dim3((ncap + PARSE_WG - 1) / PARSE_WG, 1), dim3(PARSE_WG), 0, st, cur, n_cur, ncap, det, det_stride, det_off,
+                     K3, w2c, view, dis_threshold, 1, width, height, label, (unsigned char*)nullptr);
+  NEAT_CHECK(hipGetLastError());
+  // the stable grouping by label and the means of the groups after reversal: parse_group's (its score output is not used; l3d = the lines)
+  const int e = neat_parse_group(label, cur, cur, ncap, m, glines, (float*)(p + w.gscores), gcount, p + w.group, stream);
+  if (e != 0) return e;
+  hipLaunchKernelGGL(post_refine_assemble_kernel, dim3(1), dim3(1024), 0, st, cur, n_cur, ncap, label, glines, gcount, (int*)(p + w.idx), next,
+                     n_next);
+  return (int)hipGetLastError();
+}
+
+static size_t post_sort_bytes(int n) {
+  size_t a = 0, b = 0;
+  if (n <= 0) return 0;
+  if (rocprim::radix_sort_keys(nullptr, a, (int*)nullptr, (int*)nullptr, 2 * (size_t)n) != hipSuccess) return 0;
+  if (rocprim::radix_sort_keys(nullptr, b, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)n) != hipSuccess) return 0;
+  return std::max(a, b);
+}
+
+size_t neat_post_snap_ws_bytes(int n, int G) {
+  PostSnapWs w;
+  if (n < 0) return 0;
+  return post_snap_layout(n, G, post_sort_bytes(n), &w) ? w.total : 0;
+}
+
+int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique, float* junctions, int* pcount, int* edges, float* lines_out,
+                   int* counts, void* ws, void* stream) {
+  PostSnapWs w;
+  if (n < 0 || !post_grid_ok(G) || !counts || (unique != 0 && unique != 1) || max_snap != max_snap) return -1;   // G > 1024: refused before any launch
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) return (int)hipMemsetAsync(counts, 0, 2 * sizeof(int), st);
+  const size_t sort_bytes = post_sort_bytes(n);
+  if (!post_snap_layout(n, G, sort_bytes, &w) || !lines || !junctions || !pcount || !edges || !lines_out || !ws) return -1;
+  const int M = 2 * n;
+  char* p = (char*)ws;
+  float* box = (float*)(p + w.box);
+  int* wcnt = (int*)(p + w.counts);
+  int *key = (int*)(p + w.key), *skey = (int*)(p + w.skey), *head = (int*)(p + w.head), *flag = (int*)(p + w.flag), *cnt = (int*)(p + w.cnt);
+  int *pidx = (int*)(p + w.pidx), *near = (int*)(p + w.near), *idx = (int*)(p + w.idx);
+  float* dist2 = (float*)(p + w.dist2);
+  hipLaunchKernelGGL(post_snap_bbox_kernel, dim3(1), dim3(1024), 0, st, lines, M, G, box);
+  hipLaunchKernelGGL(post_snap_key_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, lines, M, G, (const float*)box, key);
+  NEAT_CHECK(hipGetLastError());
+  size_t tb = sort_bytes;
+  NEAT_CHECK(rocprim::radix_sort_keys((void*)(p + w.sort), tb, key, skey, (size_t)M, 0u, 32u, st));
+  hipLaunchKernelGGL(post_snap_cells_kernel, dim3(1), dim3(1024), 0, st, (const int*)skey, M, head, wcnt);
+  hipLaunchKernelGGL(post_snap_peak_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)skey, (const int*)head, (const int*)wcnt, M, G,
+                     flag, cnt);
+  hipLaunchKernelGGL(post_snap_select_kernel, dim3(1), dim3(1024), 0, st, (const int*)skey, (const int*)head, (const int*)wcnt, M, G,
+                     (const float*)box, (const int*)flag, (const int*)cnt, pidx, junctions, pcount, counts);
+  hipLaunchKernelGGL(post_snap_nearest_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, lines, M, (const float*)junctions, (const int*)counts,
+                     near, dist2);
+  if (!unique) {
+    hipLaunchKernelGGL(post_snap_edges_kernel, dim3(1), dim3(1024), 0, st, (const int*)near, (const float*)dist2, n, max_snap,
+                       (const float*)junctions, idx, edges, lines_out, counts + 1);
+    return (int)hipGetLastError();
+  }
+  unsigned long long *pkey = (unsigned long long*)(p + w.pkey), *spkey = (unsigned long long*)(p + w.spkey);
+  hipLaunchKernelGGL(post_snap_pairkey_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)near, (const float*)dist2, n, max_snap, pkey);
+  NEAT_CHECK(hipGetLastError());
+  tb = sort_bytes;
+  NEAT_CHECK(rocprim::radix_sort_keys((void*)(p + w.sort), tb, pkey, spkey, (size_t)n, 0u, 64u, st));
+  hipLaunchKernelGGL(post_snap_unique_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long*)spkey, n, (const float*)junctions, idx, edges,
+                     lines_out, counts + 1);
   return (int)hipGetLastError();
 }
 

@@ -1166,6 +1166,85 @@ def parse_visibility(lines, n_lines, gt_packed, gt_off, K3, w2c, ckdist, ckview)
     return vis_count[:ecap], checked[:ecap], n_checked
 
 
+# ---- fuse / refine / snap of a parsed line soup (neat_amd/post.py): no gradient, nothing synchronises ---------------------------------
+def _det_rows(det, cols):
+    det = _f32c(det.detach())
+    if det.dim() != 2 or (det.shape[0] > 0 and det.shape[1] < cols):
+        raise RuntimeError(f"post ops: packed detections [sum m_v, >= {cols}]")
+    return det, max(int(det.shape[1]), cols)
+
+
+def post_fuse(lines, det, det_off, K3, w2c, dis_threshold, keep_threshold, by_label):
+    """fusion.py :79-141, all views in one launch.  lines [n,2,3]; det [sum m_v, >= 5] (x1 y1 x2 y2 score) with view v at rows
+    det_off[v]:det_off[v+1] (int32 [V+1] on the device); K3 [V,3,3], w2c [V,3,4].
+    -> score [n], count [n] int32, keep [n] bool, kept [n,2,3] (the first n_kept rows), n_kept int32 [1] (device)."""
+    lines = _f32c(lines.detach().reshape(-1, 6))
+    n, dev, V = lines.shape[0], lines.device, int(det_off.shape[0]) - 1
+    det, stride = _det_rows(det, 5)
+    K3, w2c = _f32c(K3.detach()), _f32c(w2c.detach())
+    score, count = torch.empty(n, device=dev), torch.empty(n, device=dev, dtype=torch.int32)
+    keep, kept = torch.empty(n, device=dev, dtype=torch.uint8), torch.empty(n, 2, 3, device=dev)
+    n_kept = torch.empty(1, device=dev, dtype=torch.int32)
+    lib = _lib.lib()
+    nbytes = lib.neat_post_fuse_ws_bytes(n, V, det.shape[0])
+    if nbytes == 0 and n > 0:
+        raise RuntimeError(f"post_fuse: {n} lines x {V} views x {det.shape[0]} detections is beyond what one launch indexes")
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.neat_post_fuse(_p(lines), n, _p(det) if det.shape[0] > 0 else None, stride, _p(_i32(det_off)), det.shape[0], _p(K3), _p(w2c), V,
+                                  float(dis_threshold), float(keep_threshold), 1 if by_label else 0, _p(score), _p(count), _p(keep), _p(kept),
+                                  _p(n_kept), _p(ws), _stream()), "neat_post_fuse")
+    return score, count, keep.view(torch.bool), kept, n_kept
+
+
+def post_select(lines, keep, out, n_out):
+    """out [n,2,3] <- the lines with keep != 0 (uint8 [n], device), in order; n_out int32 [1] (device) <- their number."""
+    lines = _f32c(lines.detach().reshape(-1, 6))
+    n = lines.shape[0]
+    ws = _ws(4 * n, lines.device)
+    _lib.check(_lib.lib().neat_post_select(_p(lines), n, _p(_as_u8(keep)), _p(out), _p(n_out), _p(ws), _stream()), "neat_post_select")
+
+
+def post_refine_workspace(ncap, mmax, device):
+    nbytes = _lib.lib().neat_post_refine_ws_bytes(ncap, mmax)
+    if nbytes == 0 and ncap > 0:
+        raise RuntimeError(f"post_refine: {ncap} lines / {mmax} detections per view is beyond what one launch indexes")
+    return _ws(nbytes, device)
+
+
+def post_refine_view(cur, n_cur, det, det_off, m, mmax, K3, w2c, view, dis_threshold, width, height, nxt, n_next, ws):
+    """refinement.py :128-181 for view `view` of the sequential walk: cur [ncap,2,3] holding n_cur (int32 [1], device) lines -> nxt, n_next
+    (written in place).  m = the view's detection count (host), mmax = the bound `ws` (post_refine_workspace) was sized with."""
+    ncap = cur.shape[0]
+    det, stride = _det_rows(det, 4)
+    _lib.check(_lib.lib().neat_post_refine_view(_p(cur), _p(n_cur), ncap, _p(det) if det.shape[0] > 0 else None, stride, _p(det_off), int(m),
+                                                int(mmax), _p(K3), _p(w2c), int(view), float(dis_threshold), float(width), float(height),
+                                                _p(nxt), _p(n_next), _p(ws), _stream()), "neat_post_refine_view")
+
+
+POST_MAX_GRID = 1024
+
+
+def post_snap(lines, grid, max_snap, unique):
+    """nms.py :156-204.  lines [n,2,3] -> junctions [2n,3], pcount [2n] int32, edges [n,2] int32, lines_out [n,2,3] (padded) and
+    counts int32 [2] = (peaks, edges) on the device.  A grid outside 2..1024 is refused here, before any launch."""
+    grid = int(grid)
+    if grid < 2 or grid > POST_MAX_GRID:
+        raise ValueError(f"snap: --grid {grid} is refused (2 <= G <= {POST_MAX_GRID}: cell keys (ix G + iy) G + iz are 32-bit)")
+    lines = _f32c(lines.detach().reshape(-1, 6))
+    n, dev = lines.shape[0], lines.device
+    junc, pcount = torch.empty(max(2 * n, 1), 3, device=dev), torch.empty(max(2 * n, 1), device=dev, dtype=torch.int32)
+    edges, out = torch.empty(max(n, 1), 2, device=dev, dtype=torch.int32), torch.empty(max(n, 1), 2, 3, device=dev)
+    counts = torch.empty(2, device=dev, dtype=torch.int32)
+    lib = _lib.lib()
+    nbytes = lib.neat_post_snap_ws_bytes(n, grid)
+    if nbytes == 0:
+        raise RuntimeError(f"post_snap: {n} lines are beyond what one launch indexes")
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.neat_post_snap(_p(lines), n, grid, -1.0 if max_snap is None else float(max_snap), 1 if unique else 0, _p(junc), _p(pcount),
+                                  _p(edges), _p(out), _p(counts), _p(ws), _stream()), "neat_post_snap")
+    return junc, pcount, edges, out, counts
+
+
 # ---- surface mesh (neat_amd/mesh.py): no gradient; extract() reads its two counts once ------------------------------------
 def _axes3(n, b0, b1):
     n3 = [int(v) for v in n]
