@@ -5,6 +5,8 @@ There is NO fallback: if the shared library is missing or a call fails, a Runtim
 import ctypes
 import os
 
+import torch
+
 NUM_LAYERS = 19
 ABI_VERSION = 15
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2, "fp16": 3, "fp16x3": 4}
@@ -235,3 +237,13 @@ def lib():
 def check(code, what):
     if code != 0:
         raise RuntimeError(f"libneat_hip: {what} failed with code {code}")
+
+
+def stream():
+    """The current stream of the current device, as the library's hipStream_t argument."""
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t):
+    """A tensor's device address; NULL for None and for an empty tensor."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None

@@ -23,106 +23,15 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ply, run_io
+from ._lib import ptr as _p, stream as _stream
 
 DENSE_MAX_FACTOR = 4          # a dense box is used while it has at most this many cells per point (and at least 4096 are always allowed)
 MAX_DIM = 1 << 20             # cells per axis the kernels index
 THIN_BATCH = 8                # thinning rounds between two reads of the undecided counters
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
-              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
 # ------------------------------------------------------------------ files
-def read_ply(path):
-    """-> dict(points float64 [n,3], faces int32 [m,3] or None, normals / colors or None).  ascii and binary little-endian; vertex
-    properties beyond x y z are read by name (nx ny nz, red green blue); faces are a list property of 3 indices each."""
-    with open(path, "rb") as fh:
-        if fh.readline().strip() != b"ply":
-            raise ValueError("%s: not a PLY file" % path)
-        fmt, elements = None, []
-        while True:
-            line = fh.readline()
-            if not line:
-                raise ValueError("%s: no end_header" % path)
-            tok = line.decode("ascii", "replace").split()
-            if not tok or tok[0] in ("comment", "obj_info"):
-                continue
-            if tok[0] == "format":
-                fmt = tok[1]
-            elif tok[0] == "element":
-                elements.append({"name": tok[1], "count": int(tok[2]), "props": []})
-            elif tok[0] == "property":
-                if tok[1] == "list":
-                    elements[-1]["props"].append(("list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]], tok[4]))
-                else:
-                    elements[-1]["props"].append(("scalar", _PLY_TYPES[tok[1]], None, tok[2]))
-            elif tok[0] == "end_header":
-                break
-        if fmt not in ("ascii", "binary_little_endian"):
-            raise ValueError("%s: format %s is not read (ascii, binary_little_endian)" % (path, fmt))
-        out = {"points": None, "faces": None, "normals": None, "colors": None}
-        ascii_rows = fh.read().decode("ascii").split("\n") if fmt == "ascii" else None
-        row = 0
-        for el in elements:
-            n, props = el["count"], el["props"]
-            has_list = any(p[0] == "list" for p in props)
-            if not has_list:
-                dt = np.dtype([(p[3], "<" + p[1]) for p in props])
-                if fmt == "ascii":
-                    tab = np.array([r.split() for r in ascii_rows[row:row + n]], dtype=np.float64).reshape(n, len(props))
-                    row += n
-                    col = {p[3]: tab[:, k] for k, p in enumerate(props)}
-                else:
-                    rec = np.frombuffer(fh.read(dt.itemsize * n), dtype=dt, count=n)
-                    col = {p[3]: rec[p[3]] for p in props}
-                if el["name"] == "vertex":
-                    out["points"] = np.stack([col["x"], col["y"], col["z"]], 1).astype(np.float64)
-                    if all(k in col for k in ("nx", "ny", "nz")):
-                        out["normals"] = np.stack([col["nx"], col["ny"], col["nz"]], 1).astype(np.float64)
-                    if all(k in col for k in ("red", "green", "blue")):
-                        out["colors"] = np.stack([col["red"], col["green"], col["blue"]], 1)
-            else:
-                if len(props) != 1:
-                    raise ValueError("%s: element %s mixes a list with other properties" % (path, el["name"]))
-                _, ct, it, _ = props[0]
-                if fmt == "ascii":
-                    rows = [r.split() for r in ascii_rows[row:row + n]]
-                    row += n
-                    if any(int(r[0]) != 3 for r in rows):
-                        raise ValueError("%s: only triangles are read" % path)
-                    lists = np.array([r[1:4] for r in rows], dtype=np.int64).reshape(n, 3)
-                else:
-                    dt = np.dtype([("n", "<" + ct), ("i", "<" + it, (3,))])
-                    rec = np.frombuffer(fh.read(dt.itemsize * n), dtype=dt, count=n)
-                    if n and not (rec["n"] == 3).all():
-                        raise ValueError("%s: only triangles are read" % path)
-                    lists = rec["i"]
-                if el["name"] == "face":
-                    out["faces"] = lists.astype(np.int32).reshape(n, 3)
-        if out["points"] is None:
-            raise ValueError("%s: no vertex element" % path)
-        return out
-
-
-def write_ply_cloud(path, points, colors=None):
-    """Binary little-endian PLY of a cloud: double x y z and, given colours in [0, 1], uchar red green blue (what open3d writes)."""
-    p = np.ascontiguousarray(np.asarray(points, dtype=np.float64)).reshape(-1, 3)
-    fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
-    header = ["ply", "format binary_little_endian 1.0", "comment neat_amd.evaluate", "element vertex %d" % p.shape[0],
-              "property double x", "property double y", "property double z"]
-    if colors is not None:
-        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
-        header += ["property uchar red", "property uchar green", "property uchar blue"]
-    rec = np.empty(p.shape[0], dtype=fields)
-    rec["x"], rec["y"], rec["z"] = p[:, 0], p[:, 1], p[:, 2]
-    if colors is not None:
-        c = np.floor(np.clip(np.asarray(colors, dtype=np.float64).reshape(-1, 3), 0, 1) * 255.0 + 0.5).astype(np.uint8)      # rounded, as open3d does
-        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
-    with open(path, "wb") as fh:
-        fh.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
-        fh.write(rec.tobytes())
-
-
 def load_obs(dataset_dir=None, scan=None, npz=None):
     """-> dict(ObsMask [a,b,c], BB [2,3], Res, P [4]) from <dataset_dir>/ObsMask/ObsMask{scan}_10.mat and Plane{scan}.mat (scipy.io.loadmat),
     or from one .npz with the same four arrays."""
@@ -144,14 +53,6 @@ def load_obs(dataset_dir=None, scan=None, npz=None):
 
 
 # ------------------------------------------------------------------ device pieces
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _dev_points(x, device=None):
     """arrays and tensors -> contiguous float64 [n,3] on the device (no host fallback: a CPU tensor without a device to go to raises)."""
     t = torch.as_tensor(np.asarray(x)) if not torch.is_tensor(x) else x
@@ -503,7 +404,7 @@ def build_parser():
 def _dtu_inputs(opt):
     obs = load_obs(opt.dataset_dir, opt.scan, opt.obs)
     stl_path = opt.stl or os.path.join(opt.dataset_dir, "Points", "stl", "stl%03d_total.ply" % opt.scan)
-    return obs, read_ply(stl_path)["points"]
+    return obs, ply.read_ply(stl_path)["points"]
 
 
 def _scale_mat(opt):
@@ -528,7 +429,7 @@ def _emit(opt, result, timings, lines):
 
 def run_dtu_mesh(opt, dev):
     timings = {"sample_s": 0.0}
-    data = read_ply(opt.data)
+    data = ply.read_ply(opt.data)
     obs, stl = _dtu_inputs(opt)
     if opt.mode == "mesh":
         if data["faces"] is None:
@@ -574,23 +475,11 @@ def write_vis(opt, details, stl):
     colors = vis_colors(details, stl.shape[0], opt.visualize_threshold, opt.max_dist)
     os.makedirs(opt.vis_out_dir, exist_ok=True)
     for name, pts, color in (("d2s", details["data_down"].cpu().numpy(), colors[0]), ("s2d", stl, colors[1])):
-        write_ply_cloud(os.path.join(opt.vis_out_dir, "vis_%03d_%s.ply" % (opt.scan, name)), pts, color)
-
-
-def _load_lines(path):
-    """-> (lines3d, scores or None): `lines3d_wfi_checked` of a -neat.pth, or `lines3d` (and `scores`) of an .npz."""
-    if path.endswith(".pth"):
-        return torch.load(path, map_location="cpu")["lines3d_wfi_checked"], None
-    data = np.load(path, allow_pickle=True)
-    lines3d = data["lines3d"]
-    if lines3d.dtype == object:
-        lines3d = np.concatenate(lines3d, axis=0)
-    return lines3d, (data["scores"] if "scores" in data.files else None)
+        ply.write_ply_cloud(os.path.join(opt.vis_out_dir, "vis_%03d_%s.ply" % (opt.scan, name)), pts, color)
 
 
 def run_dtu_lines(opt, dev):
-    lines3d, scores = _load_lines(opt.data)
-    lines3d = np.asarray(lines3d)
+    lines3d, scores = run_io.load_lines(opt.data)          # float64: line_cloud computes in float64 whatever the file holds
     if opt.score is not None:
         if scores is None:
             raise SystemExit("--score needs the key `scores` in %s" % opt.data)
@@ -608,7 +497,7 @@ def run_dtu_lines(opt, dev):
 
 
 def run_dtu_junctions(opt, dev):
-    lines3d = _load_lines(opt.data)[0]
+    lines3d = run_io.load_lines(opt.data)[0]
     obs, stl = _dtu_inputs(opt)
     cloud, n = junction_cloud(lines3d, _scale_mat(opt))
     timings, details = {"sample_s": 0.0}, {}

@@ -27,6 +27,10 @@ import time
 import numpy as np
 import torch
 
+from . import ply
+from ._lib import PRECISIONS
+from .run_io import implicit_network_of, load_model
+
 DEFAULT_RESOLUTION = 100
 DEFAULT_BOUNDARY = (-1.5, 1.5)
 DEFAULT_CHUNK = 262144          # grid nodes per SDF query
@@ -62,10 +66,6 @@ def _bounds3(grid_boundary):
     return lo, hi
 
 
-def _implicit(model):
-    return getattr(model, "implicit_network", model)
-
-
 @torch.no_grad()
 def sdf_grid(model, resolution=DEFAULT_RESOLUTION, grid_boundary=DEFAULT_BOUNDARY, chunk=DEFAULT_CHUNK, frame=None):
     """get_sdf_vals on the nodes of a uniform grid -> float32 device tensor [nx, ny, nz] (x slowest), in the model's own precision.
@@ -73,7 +73,7 @@ def sdf_grid(model, resolution=DEFAULT_RESOLUTION, grid_boundary=DEFAULT_BOUNDAR
     frame = (R [3,3], c [3]) float64 on the host: the grid is laid out in the local coordinates p of that frame and node p is queried at
     c + R^T p (ops.grid_points_affine); without it the nodes are queried where they are."""
     from . import ops
-    net = _implicit(model)
+    net = implicit_network_of(model)
     shape = _shape3(resolution)
     lo, hi = _bounds3(grid_boundary)
     if min(shape) < 2:
@@ -140,7 +140,7 @@ def keep_largest_component(verts, faces):
 def vertex_normals(model, verts, chunk=65536):
     """Unit normals = the SDF network's gradient at the vertices (ops.sdf_point_normals), normalised on the device."""
     from . import ops
-    net = _implicit(model)
+    net = implicit_network_of(model)
     out = torch.empty_like(verts)
     with torch.no_grad():
         for i0 in range(0, verts.shape[0], chunk):
@@ -159,7 +159,7 @@ def surface(model, resolution=None, grid_boundary=None, level=0.0, largest_compo
     if grid_boundary is None:
         grid_boundary = tuple(plot_conf.get("grid_boundary", DEFAULT_BOUNDARY))
     lo, hi = _bounds3(grid_boundary)
-    dev = next(_implicit(model).parameters()).device
+    dev = next(implicit_network_of(model).parameters()).device
     sync = (lambda: torch.cuda.synchronize(dev)) if timings is not None else (lambda: None)
     sync()
     t0 = time.perf_counter()
@@ -293,7 +293,7 @@ def eval_surface(model, resolution=EVAL_RESOLUTION, grid_boundary=None, level=0.
             raise ValueError("eval_surface: scale_mat [4, 4]")
         if normals and not (S[0, 0] > 0 and np.array_equal(S[:3, :3], S[0, 0] * np.eye(3))):
             raise ValueError("eval_surface: normals need scale_mat's 3x3 part to be a positive multiple of the identity")
-    dev = next(_implicit(model).parameters()).device
+    dev = next(implicit_network_of(model).parameters()).device
     t = [time.perf_counter()]
 
     def lap(name):
@@ -359,31 +359,6 @@ def eval_out_path(run_dir, epoch, scan_id=None):
     return os.path.join(run_dir, str(epoch), "scan{}.ply".format("" if scan_id is None else scan_id))
 
 
-def write_ply(path, verts, faces, normals=None):
-    """Binary little-endian PLY: float32 x y z [nx ny nz] per vertex, `uchar 3 + 3 x int32` per face."""
-    v = np.ascontiguousarray(torch.as_tensor(verts).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
-    f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), dtype="<i4").reshape(-1, 3)
-    cols = [v]
-    header = ["ply", "format binary_little_endian 1.0", "comment neat_amd.mesh: SDF level surface, marching tetrahedra",
-              "element vertex %d" % v.shape[0], "property float x", "property float y", "property float z"]
-    if normals is not None:
-        n = np.ascontiguousarray(torch.as_tensor(normals).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
-        if n.shape != v.shape:
-            raise ValueError("write_ply: one normal per vertex")
-        cols.append(n)
-        header += ["property float nx", "property float ny", "property float nz"]
-    header += ["element face %d" % f.shape[0], "property list uchar int vertex_indices", "end_header"]
-    rec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
-    rec["n"] = 3
-    rec["i"] = f
-    tmp = path + ".tmp"
-    with open(tmp, "wb") as fh:
-        fh.write(("\n".join(header) + "\n").encode("ascii"))
-        fh.write(np.concatenate(cols, axis=1).astype("<f4").tobytes())
-        fh.write(rec.tobytes())
-    os.replace(tmp, path)
-
-
 def out_path(run_dir, epoch):
     """`<run>/plots/surface_{epoch}.ply`: the reference's name (plots.py:37-38, :131-134)."""
     return os.path.join(run_dir, "plots", "surface_{}.ply".format(epoch))
@@ -400,7 +375,7 @@ def build_parser():
     ap.add_argument("--no-normals", default=False, action="store_true", help="write no vertex normals")
     ap.add_argument("--expdir", default=None, help="run directory holding checkpoints/ (default: the conf's directory)")
     ap.add_argument("--gpu", type=int, default=0, help="device index")
-    ap.add_argument("--precision", choices=["fp32", "bf16", "bf16x3", "fp16", "fp16x3"], default=None)
+    ap.add_argument("--precision", choices=list(PRECISIONS), default=None)
     ap.add_argument("--overwrite", default=False, action="store_true", help="write even if the .ply exists")
     ev = ap.add_argument_group("evaluation mesh (eval_surface)")
     ev.add_argument("--eval", default=False, action="store_true", help="the mesh the evaluation scores: aligned fine grid, box cut, world frame "
@@ -419,25 +394,6 @@ def build_parser():
 def plot_block(conf):
     """The conf's `plot` block as a plain dict (empty if absent)."""
     return dict(conf.get("plot", None) or {})
-
-
-def load(conf_path, checkpoint, device, expdir=None, precision=None):
-    """-> (model with the checkpoint loaded strictly, its epoch, run directory, the conf's plot block)."""
-    from . import conf as conf_mod
-    from .general import get_class
-    from .runner import CLASS_MAP
-    conf = conf_mod.parse_file(conf_path)
-    root = expdir or os.path.dirname(os.path.abspath(conf_path))
-    name = conf.get_string("train.model_class")
-    model = get_class(CLASS_MAP.get(name, name))(conf=conf.get_config("model")).to(device)
-    if precision is not None:
-        model.set_precision(precision)
-    path = os.path.join(root, "checkpoints", "ModelParameters", str(checkpoint) + ".pth")
-    print("Checkpoint: {}".format(path), flush=True)
-    state = torch.load(path, map_location=device)
-    model.load_state_dict(state["model_state_dict"], strict=True)
-    model.eval()
-    return model, state["epoch"], root, plot_block(conf)
 
 
 def eval_bbox(opt):
@@ -474,7 +430,7 @@ def main_eval(opt, model, epoch, root, plot):
         print("a grid does not cross level {} (or the box cuts everything away): no surface, nothing written".format(opt.level), flush=True)
         return 0
     os.makedirs(os.path.dirname(path), exist_ok=True)
-    write_ply(path, res["verts"], res["faces"], res["normals"])
+    ply.write_ply(path, res["verts"], res["faces"], res["normals"])
     print("{}: {} vertices, {} faces, aligned grid {} x {} x {}".format(path, res["verts"].shape[0], res["faces"].shape[0], *res["frame"]["shape"]),
           flush=True)
     return 0
@@ -484,7 +440,8 @@ def main(argv=None):
     opt = build_parser().parse_args(argv)
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
-    model, epoch, root, plot = load(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
+    model, epoch, root, conf = load_model(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
+    plot = plot_block(conf)
     if opt.eval:
         return main_eval(opt, model, epoch, root, plot)
     path = out_path(root, epoch)
@@ -500,7 +457,7 @@ def main(argv=None):
         print("the grid does not cross level {}: no surface, nothing written".format(opt.level), flush=True)
         return 0
     os.makedirs(os.path.dirname(path), exist_ok=True)
-    write_ply(path, res["verts"], res["faces"], res["normals"])
+    ply.write_ply(path, res["verts"], res["faces"], res["normals"])
     print("{}: {} vertices, {} faces".format(path, res["verts"].shape[0], res["faces"].shape[0]), flush=True)
     return 0
 

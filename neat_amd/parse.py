@@ -3,7 +3,7 @@
     python -m neat_amd.parse --conf <run>/runconf.conf [--checkpoint latest] [--gpu 0] [--data_root ../data]
 
 The checkpoint is read from `<dir of conf>/checkpoints/ModelParameters/<checkpoint>.pth` (or `<expdir>/checkpoints/...` with --expdir)
-and loaded strictly; class paths of the conf that name the reference's classes are mapped through runner.CLASS_MAP.  Files written under
+and loaded strictly; class paths of the conf that name the reference's classes are mapped through run_io.CLASS_MAP.  Files written under
 `<run>/wireframes/` (run = the conf's directory, or --expdir):
     {checkpoint}-{h}-all.npz, -wfi.npz, -wfi_checked.npz   key `lines3d`
     {checkpoint}-{h}-neat.pth                              the result dict and `kwargs`
@@ -54,29 +54,6 @@ def out_basename(conf, checkpoint, distance, sdf_junction_refine):
     return "{}-{}".format(checkpoint, digest[:8].replace("/", "n"))
 
 
-def load(conf_path, checkpoint, device, expdir=None, data_root="../data"):
-    """-> (model with the checkpoint loaded strictly, eval dataset built with distance_threshold = 1, run directory)."""
-    from . import conf as conf_mod
-    from .general import get_class
-    from .runner import CLASS_MAP
-    conf = conf_mod.parse_file(conf_path)
-    cls = lambda key: get_class(CLASS_MAP.get(conf.get_string(key), conf.get_string(key)))
-    root = expdir or os.path.dirname(os.path.abspath(conf_path))
-    dataset_conf = dict(conf.get_config("dataset").items())
-    dataset_conf["distance_threshold"] = 1.0
-    ds_cls = cls("train.dataset_class")
-    if ds_cls.__module__.startswith("neat_amd"):
-        dataset_conf["data_root"] = data_root
-    dataset = ds_cls(**dataset_conf)
-    model = cls("train.model_class")(conf=conf.get_config("model")).to(device)
-    path = os.path.join(root, "checkpoints", "ModelParameters", str(checkpoint) + ".pth")
-    print("Checkpoint: {}".format(path), flush=True)
-    state = torch.load(path, map_location=device)
-    model.load_state_dict(state["model_state_dict"], strict=True)
-    model.eval()
-    return model, dataset, root
-
-
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     kwargs = dict(conf=opt.conf, checkpoint=opt.checkpoint, chunksize=opt.chunksize, distance=opt.reproj_dis, overwrite=opt.overwrite,
@@ -84,8 +61,9 @@ def main(argv=None):
                   junc_match_threshold=opt.junc_match_threshold)
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
-    from . import parsing
-    model, dataset, root = load(opt.conf, opt.checkpoint, device, opt.expdir, opt.data_root)
+    from . import parsing, run_io
+    model, _, root, conf = run_io.load_model(opt.conf, opt.checkpoint, device, opt.expdir)
+    dataset = run_io.build_dataset(conf, opt.data_root, distance_threshold=1.0)          # the eval dataset
     wireframe_dir = os.path.join(root, "wireframes")
     os.makedirs(wireframe_dir, exist_ok=True)
     base = out_basename(opt.conf, opt.checkpoint, opt.reproj_dis, kwargs["sdf_junction_refine"])
@@ -94,12 +72,7 @@ def main(argv=None):
         print("reusing {}".format(pth_path), flush=True)
         results = torch.load(pth_path, map_location="cpu")
         # a reused result gets its visibility check again, with this call's --ckdist / --ckview (as the reference does)
-        gts, Ks, poses = [], [], []
-        for i in range(len(dataset)):
-            _, sample, _ = dataset[i]
-            gts.append(sample["wireframe"].line_segments(0.05))
-            Ks.append(sample["intrinsics"][:3, :3])
-            poses.append(sample["pose"])
+        gts, Ks, poses = run_io.dataset_views(dataset)
         wfi = results["lines3d_wfi"].to(device).float().contiguous()
         _, checked, n_checked = parsing.visibility(wfi, gts, Ks, poses, opt.ckdist, opt.ckview)
         results["lines3d_wfi_checked"] = checked[:int(n_checked.item())].cpu()

@@ -26,7 +26,7 @@ import time
 import numpy as np
 import torch
 
-from . import ops
+from . import conf as conf_mod, ops, run_io
 from .parsing import _cameras, _dev
 
 
@@ -44,20 +44,13 @@ def pack_views(dets, Ks, poses, img_res, device):
 
 def views_of(dataset, device):
     """The per-view inputs of a dataset: detections wireframe.line_segments(0.05), intrinsics, pose, img_res = (height, width)."""
-    dets, Ks, poses = [], [], []
-    for i in range(len(dataset)):
-        _, sample, _ = dataset[i]
-        dets.append(sample["wireframe"].line_segments(0.05))
-        Ks.append(sample["intrinsics"][:3, :3])
-        poses.append(sample["pose"])
-    return pack_views(dets, Ks, poses, dataset.img_res, device)
+    return pack_views(*run_io.dataset_views(dataset), dataset.img_res, device)
 
 
 def as_lines(lines3d, device):
     """lines3d [N,2,3], or an object array of per-view arrays (concatenated) -> float32 device tensor [N,2,3]."""
     if isinstance(lines3d, np.ndarray) and lines3d.dtype == object:
-        parts = [np.asarray(p, np.float32).reshape(-1, 2, 3) for p in lines3d]
-        lines3d = np.concatenate(parts) if parts else np.zeros((0, 2, 3), np.float32)
+        lines3d = run_io.stack_lines(lines3d, np.float32)
     return _dev(lines3d, device).reshape(-1, 2, 3).contiguous()
 
 
@@ -163,23 +156,8 @@ def out_path(opt):
     suffix = {"fuse": "fused", "refine": "ref", "snap": "snap"}[opt.cmd]
     if opt.cmd == "snap" and not opt.expdir:
         return os.path.join(os.path.dirname(os.path.abspath(opt.data)), f"{base}-snap.npz")
-    root = opt.expdir or os.path.dirname(os.path.abspath(opt.conf))
+    root = run_io.run_dir(opt.conf, opt.expdir)
     return os.path.join(root, "wireframes", f"{base}-{suffix}.npz")
-
-
-def load_dataset(conf_path, data_root):
-    """The eval dataset of a conf (built as neat_amd.parse builds it) and the parsed conf."""
-    from . import conf as conf_mod
-    from .general import get_class
-    from .runner import CLASS_MAP
-    conf = conf_mod.parse_file(conf_path)
-    name = conf.get_string("train.dataset_class")
-    ds_cls = get_class(CLASS_MAP.get(name, name))
-    dataset_conf = dict(conf.get_config("dataset").items())
-    dataset_conf["distance_threshold"] = 1.0
-    if ds_cls.__module__.startswith("neat_amd"):
-        dataset_conf["data_root"] = data_root
-    return ds_cls(**dataset_conf)
 
 
 def main(argv=None):
@@ -208,7 +186,7 @@ def main(argv=None):
         print(f"load {t1 - t0:.3f} s, snap {t2 - t1:.3f} s: {lines.shape[0]} lines -> {res['junctions'].shape[0]} junctions, "
               f"{res['edges'].shape[0]} edges", flush=True)
     else:
-        views = views_of(load_dataset(opt.conf, opt.data_root), device)
+        views = views_of(run_io.build_dataset(conf_mod.parse_file(opt.conf), opt.data_root, distance_threshold=1.0), device)      # the eval dataset, as neat_amd.parse builds it
         sync()
         t1 = time.perf_counter()
         if opt.cmd == "fuse":
@@ -220,12 +198,11 @@ def main(argv=None):
                   f"{res['lines3d'].shape[0]}", flush=True)
         else:
             model, scores = None, None
-            ckpt = os.path.join(opt.expdir or os.path.dirname(os.path.abspath(opt.conf)), "checkpoints", "ModelParameters", opt.checkpoint + ".pth")
+            ckpt = run_io.checkpoint_path(run_io.run_dir(opt.conf, opt.expdir), opt.checkpoint)
             if opt.no_filter or not os.path.exists(ckpt):
                 print("SDF pre-filter skipped" + ("" if opt.no_filter else f": no checkpoint at {ckpt}"), flush=True)
             else:
-                from .parse import load
-                model = load(opt.conf, opt.checkpoint, device, opt.expdir, opt.data_root)[0]
+                model = run_io.load_model(opt.conf, opt.checkpoint, device, opt.expdir)[0]
                 scores = np.asarray(data["scores"], np.float32) if "scores" in data.files else None
             sync()
             t1 = time.perf_counter()

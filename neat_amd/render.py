@@ -24,7 +24,6 @@ Divergences: bytes are clamped where numpy's cast wraps or is u
 squares (the reference: a float32 mean in an unspecified order); output goes under the run directory, not ../evals/.
 """
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -34,7 +33,8 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, run_io
+from ._lib import ptr as _p, stream as _stream
 
 MAPS = ("rgb", "normal", "depth")
 SURFACE = "surface"            # --maps surface / --surface: the sphere-traced first hit (neat_amd.trace.view), not a map of the volumetric forward
@@ -42,14 +42,6 @@ DEFAULT_CHUNK = 10000          # eval.py:80
 
 
 # ------------------------------------------------------------------ device
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _f32(t, what):
     if t is None:
         return None
@@ -335,7 +327,7 @@ def build_parser():
     ap.add_argument("--data_root", default="../data", help="root of the dataset's data_dir")
     ap.add_argument("--scan_id", default=-1, type=int)
     ap.add_argument("--gpu", default=0, type=int, help="device index")
-    ap.add_argument("--precision", choices=["fp32", "bf16", "bf16x3", "fp16", "fp16x3"], default=None)
+    ap.add_argument("--precision", choices=list(_lib.PRECISIONS), default=None)
     ap.add_argument("--json", default=False, action="store_true", help="print one JSON object with the PSNRs and the timings")
     ap.add_argument("--overwrite", default=False, action="store_true", help="rewrite files that are already on disk")
     return ap
@@ -364,35 +356,18 @@ def parse_args(argv=None):
     return opt
 
 
-def load_dataset(conf, data_root, scan_id=-1):
-    """The conf's dataset, as the runner builds it (class paths of the reference mapped through runner.CLASS_MAP)."""
-    from .general import get_class
-    from .runner import CLASS_MAP
-    name = conf.get_string("train.dataset_class")
-    ds_cls = get_class(CLASS_MAP.get(name, name))
-    dataset_conf = dict(conf.get_config("dataset").items())
-    if scan_id != -1:
-        dataset_conf["scan_id"] = scan_id
-    if ds_cls.__module__.startswith("neat_amd"):
-        dataset_conf["data_root"] = data_root
-    return ds_cls(**dataset_conf)
-
-
 def main(argv=None):
     opt = parse_args(argv)
     _lib.lib()                      # a missing library is an error before any file is read
-    from . import conf as conf_mod, mesh
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
-    conf = conf_mod.parse_file(opt.conf)
+    model, epoch, root, conf = run_io.load_model(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
     chunksize = opt.chunksize if opt.chunksize is not None else conf.get_int("train.split_n_pixels", default=DEFAULT_CHUNK)
-    model, epoch, root, _ = mesh.load(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
     if opt.cam_json is not None:
-        with open(opt.cam_json) as fh:
-            cams = np.asarray(json.load(fh), dtype=np.float64).reshape(-1, 4, 4)
+        cams = run_io.load_cam_json(opt.cam_json)
         dataset, views = None, list(range(len(cams)))
     else:
-        dataset = load_dataset(conf, opt.data_root, opt.scan_id)
+        dataset = run_io.build_dataset(conf, opt.data_root, opt.scan_id)
         views = list(range(len(dataset))) if opt.views is None else opt.views
         bad = [v for v in views if not 0 <= v < len(dataset)]
         if bad:

@@ -26,14 +26,9 @@ import torch
 
 from . import conf as conf_mod
 from . import dp, rend_util
-from .general import get_class
+from ._lib import PRECISIONS
+from .run_io import CLASS_MAP, build_dataset, conf_class      # (CLASS_MAP: the reference's class paths -> neat_amd's)
 
-CLASS_MAP = {
-    "datasets.blender_hawp_dataset.BlenderDataset": "neat_amd.datasets.BlenderDataset",
-    "datasets.scene_hawp_dataset.SceneDataset": "neat_amd.datasets.SceneDataset",
-    "model.networks.neat_wfr_rend_a.VolSDFNetwork": "neat_amd.networks.VolSDFNetwork",
-    "model.networks.loss_wfr.VolSDFLoss": "neat_amd.loss.VolSDFLoss",
-}
 SUBDIRS = ("ModelParameters", "OptimizerParameters", "SchedulerParameters")
 
 
@@ -53,14 +48,8 @@ class TrainRunner:
         if self.rank == 0:
             for sub in SUBDIRS:
                 os.makedirs(os.path.join(self.checkpoints_path, sub), exist_ok=True)
-        cls = lambda key: get_class(CLASS_MAP.get(self.conf.get_string(key), self.conf.get_string(key)))
-        dataset_conf = dict(self.conf.get_config("dataset").items())
-        if scan_id != -1:
-            dataset_conf["scan_id"] = scan_id
-        ds_cls = cls("train.dataset_class")
-        if ds_cls.__module__.startswith("neat_amd"):
-            dataset_conf["data_root"] = data_root
-        self.train_dataset = ds_cls(**dataset_conf)
+        cls = lambda key: conf_class(self.conf, key)
+        self.train_dataset = build_dataset(self.conf, data_root, scan_id)
         gen = torch.Generator()
         gen.manual_seed(dp.rank_seed(42, self.rank))      # each rank walks the views in its own order (one view per rank and step)
         self.train_dataloader = torch.utils.data.DataLoader(self.train_dataset, batch_size=1, shuffle=True, generator=gen,
@@ -139,14 +128,14 @@ class TrainRunner:
         """`<run>/plots/surface_{epoch}.ply` from the model as it stands (neat_amd.mesh; rank 0, CUDA only) -> the path or None."""
         if self.rank != 0 or self.device.type != "cuda":
             return None
-        from . import mesh
+        from . import mesh, ply
         res = mesh.surface(self.model, plot_conf=mesh.plot_block(self.conf))
         if res is None:
             print(f"{self.expname}/{self.timestamp} [{epoch}]: the SDF grid does not cross zero, no surface written", flush=True)
             return None
         path = mesh.out_path(os.path.join(self.expdir, self.timestamp), epoch)
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        mesh.write_ply(path, res["verts"], res["faces"], res["normals"])
+        ply.write_ply(path, res["verts"], res["faces"], res["normals"])
         return path
 
     def write_images(self, epoch):
@@ -210,7 +199,7 @@ def main():
     ap.add_argument("--exps_folder", default="exps")
     ap.add_argument("--scan_id", type=int, default=-1)
     ap.add_argument("--data_root", default="../data")
-    ap.add_argument("--precision", choices=["fp32", "bf16", "bf16x3", "fp16", "fp16x3"], default=None)
+    ap.add_argument("--precision", choices=list(PRECISIONS), default=None)
     ap.add_argument("--is_continue", default=None, help="checkpoints directory of the run to continue")
     ap.add_argument("--checkpoint", default="latest")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks (one per GPU); > 1 re-executes under torch.distributed.run")

@@ -24,7 +24,8 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ply, run_io
+from ._lib import ptr as _p, stream as _stream
 
 POSES = {"dtu": (-155.0, 0.0, -25.0, 3.0), "scan": (0.0, 170.0, -45.0, 3.0), None: (0.0, 0.0, 0.0, 3.0)}      # show.py:459-471
 STYLE = dict(line_width=1.5, point_radius=2.5, near=0.05, depth_bias=0.01, hidden_alpha=0.0, bg=(1.0, 1.0, 1.0), line_color=(0.0, 0.0, 0.0),
@@ -99,14 +100,6 @@ def dataset_cameras(path, views):
 
 
 # ------------------------------------------------------------------ device
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _dev(x, dtype, cols, device):
     t = x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(np.asarray(x)))
     t = t.detach().to(device=device, dtype=dtype).reshape(-1, cols).contiguous()
@@ -207,19 +200,6 @@ def render(lines3d, cameras, K, width, height, mesh=None, points=None, return_bu
 
 
 # ------------------------------------------------------------------ files
-def load_lines(path):
-    """`lines3d` of a -wfi_checked.npz / -wfi.npz / -all.npz (an object array of per-view blocks is concatenated, show.py:478-479), or
-    `lines3d_wfi_checked` of the -neat.pth that neat_amd.parse writes -> float64 [n,2,3]."""
-    if path.endswith(".pth"):
-        lines3d = torch.load(path, map_location="cpu")["lines3d_wfi_checked"]
-        lines3d = lines3d.numpy() if torch.is_tensor(lines3d) else np.asarray(lines3d)
-    else:
-        lines3d = np.load(path, allow_pickle=True)["lines3d"]
-        if lines3d.ndim == 1:
-            lines3d = np.concatenate(list(lines3d), axis=0) if len(lines3d) else np.zeros((0, 2, 3))
-    return np.asarray(lines3d, dtype=np.float64).reshape(-1, 2, 3)
-
-
 def write_frames(directory, frames, gif=None, overwrite=False, first=0):
     """frames uint8 [F,H,W,3] (tensor or array) -> directory/{k:04d}.png, kept if present unless `overwrite`; gif = a path writes the
     frames as they are on disk after this call (30 per second, as show.py).  -> the PNG paths."""
@@ -287,8 +267,7 @@ def cameras_of(opt):
     """-> (w2c [F,4,4], K [3,3] or [F,3,3]) from --cam-json, --cams / --views or the orbit."""
     K = intrinsics(opt.width, opt.height, opt.fov)
     if opt.cam_json is not None:
-        with open(opt.cam_json) as fh:
-            return np.asarray(json.load(fh), dtype=np.float64).reshape(-1, 4, 4), K
+        return run_io.load_cam_json(opt.cam_json), K
     if opt.cams is not None:
         if not opt.views:
             raise SystemExit("--cams needs --views")
@@ -305,11 +284,10 @@ def style_of(opt):
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     _lib.lib()                      # a missing library is an error before any file is read
-    lines3d = load_lines(opt.data)
+    lines3d = run_io.load_lines(opt.data)[0]          # an object array of per-view blocks is concatenated (show.py:478-479)
     mesh = None
     if opt.mesh is not None:
-        from .evaluate import read_ply
-        m = read_ply(opt.mesh)
+        m = ply.read_ply(opt.mesh)
         if m["faces"] is None:
             raise SystemExit("%s has no faces" % opt.mesh)
         mesh = (m["points"], m["faces"])

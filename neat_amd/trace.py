@@ -30,19 +30,22 @@ import time
 import numpy as np
 import torch
 
+from . import _lib, run_io
+
 MISS, HIT, INSIDE, UNCONVERGED = 0, 1, 2, 3
 DEFAULTS = dict(eps=1e-4, relax=1.0, max_steps=64, refine_steps=8, near=0.0)
 DEFAULT_CHUNK = 1 << 20
 
 
-def _implicit(sdf):
-    net = getattr(sdf, "implicit_network", sdf)
+def _sdf_network(sdf):
+    """The SDF network of a model, or None for anything else (a bare callable field)."""
+    net = run_io.implicit_network_of(sdf)
     return net if hasattr(net, "handle") and hasattr(net, "sphere_scale") else None
 
 
 def field_of(sdf):
     """A model (its implicit_network, unclamped, at the model's build) or any callable points [n,3] -> values [n] on the device."""
-    net = _implicit(sdf)
+    net = _sdf_network(sdf)
     if net is None:
         if not callable(sdf):
             raise TypeError("trace: sdf is a model or a callable points [n,3] -> values [n]")
@@ -89,7 +92,7 @@ def rays(sdf, origins, dirs, *, radius, t_end=None, eps=DEFAULTS["eps"], relax=D
 def _radius_of(model, radius):
     if radius is not None:
         return float(radius)
-    r = float(getattr(_implicit(model), "sdf_bounding_sphere", 0.0) or 0.0)
+    r = float(getattr(_sdf_network(model), "sdf_bounding_sphere", 0.0) or 0.0)
     if not r > 0:
         raise ValueError("trace: the model has no bounding sphere; give radius=")
     return r
@@ -104,7 +107,7 @@ def view(model, pose, intrinsics, H, W, *, radius=None, timings=None, **march):
     timings = a dict receives trace_s (device-synchronised wall time), evals and rays."""
     from . import ops
     from .render import pixel_grid
-    net = _implicit(model)
+    net = _sdf_network(model)
     if net is None:
         raise TypeError("trace.view: a model")
     dev = next(net.parameters()).device
@@ -138,7 +141,7 @@ def camera_centres(cams):
 
 def _visible(model, rows, cams, samples, bias, radius, march):
     from . import ops
-    net = _implicit(model)
+    net = _sdf_network(model)
     dev = next(net.parameters()).device if net is not None else rows.device
     radius = _radius_of(model, radius)
     near = march.get("near", DEFAULTS["near"])
@@ -183,15 +186,6 @@ def out_path(data):
     return os.path.splitext(data)[0] + "_occl.npz"
 
 
-def load_lines(path):
-    """`lines3d` of an .npz (as neat_amd.show reads it) or `lines3d_wfi` of the -neat.pth neat_amd.parse writes -> float64 [n,2,3]."""
-    if path.endswith(".pth"):
-        lines3d = torch.load(path, map_location="cpu")["lines3d_wfi"]
-        return np.asarray(lines3d.numpy() if torch.is_tensor(lines3d) else lines3d, dtype=np.float64).reshape(-1, 2, 3)
-    from .show import load_lines as npz_lines
-    return npz_lines(path)
-
-
 def write_occl(path, lines3d, views, kept):
     lines3d = np.asarray(lines3d).reshape(-1, 2, 3)
     kept = np.asarray(kept, dtype=bool)
@@ -214,7 +208,7 @@ def build_parser():
     ck.add_argument("--expdir", default=None, help="run directory holding checkpoints/ (default: the conf's directory)")
     ck.add_argument("--data_root", default="../data", help="root of the dataset's data_dir")
     ck.add_argument("--gpu", default=0, type=int, help="device index")
-    ck.add_argument("--precision", choices=["fp32", "bf16", "bf16x3", "fp16", "fp16x3"], default=None)
+    ck.add_argument("--precision", choices=list(_lib.PRECISIONS), default=None)
     ck.add_argument("--json", default=False, action="store_true", help="print one JSON object with the counts and the seconds")
     ck.add_argument("--overwrite", default=False, action="store_true", help="rewrite an _occl.npz that is already on disk")
     return ap
@@ -229,8 +223,6 @@ def parse_args(argv=None):
 
 
 def main_check(opt):
-    from . import _lib, conf as conf_mod, mesh
-    from .render import load_dataset
     _lib.lib()
     path = out_path(opt.data)
     if os.path.exists(path) and not opt.overwrite:
@@ -238,11 +230,11 @@ def main_check(opt):
         return 0
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
-    model, epoch, _, _ = mesh.load(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
-    dataset = load_dataset(conf_mod.parse_file(opt.conf), opt.data_root)
+    model, epoch, _, conf = run_io.load_model(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
+    dataset = run_io.build_dataset(conf, opt.data_root)
     poses = np.stack([np.asarray(torch.as_tensor(dataset.pose_all[i]).numpy(), dtype=np.float64) for i in range(len(dataset))])
     cams = np.linalg.inv(poses)                      # the datasets hold camera-to-world
-    lines3d = load_lines(opt.data)
+    lines3d = run_io.load_lines(opt.data, pth_key="lines3d_wfi")[0]          # of a -neat.pth: the lines before the 2-D visibility check
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
     frac = visible_lines(model, torch.from_numpy(lines3d), cams, samples=opt.samples, bias=opt.bias).cpu().numpy()

@@ -192,7 +192,7 @@ def face_normals(verts, faces):
 
 
 def read_ply(path):
-    """Minimal reader of the binary little-endian PLY that neat_amd.mesh.write_ply writes -> (verts, normals or None, faces)."""
+    """Minimal reader of the binary little-endian PLY that neat_amd.ply.write_ply writes -> (verts, normals or None, faces)."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")

@@ -22,16 +22,16 @@ def run_cli(args, env=None):
 @pytest.fixture(scope="module")
 def files(golden, tmp_path_factory):
     from scipy.io import savemat
-    from neat_amd import evaluate as E
+    from neat_amd import ply
     g = golden("g20_evaluation")
     d = tmp_path_factory.mktemp("dtu")
     os.makedirs(d / "ObsMask")
     os.makedirs(d / "Points" / "stl")
     savemat(str(d / "ObsMask" / "ObsMask7_10.mat"), {"ObsMask": g["obs"], "BB": g["bb"], "Res": np.array([[float(g["res"])]])})
     savemat(str(d / "ObsMask" / "Plane7.mat"), {"P": g["plane"]})
-    E.write_ply_cloud(str(d / "Points" / "stl" / "stl007_total.ply"), g["stl"].astype(np.float64))
+    ply.write_ply_cloud(str(d / "Points" / "stl" / "stl007_total.ply"), g["stl"].astype(np.float64))
     write_mesh_f64(str(d / "surface_100.ply"), g["verts"], g["faces"])
-    E.write_ply_cloud(str(d / "cloud.ply"), g["pcd_cloud"])
+    ply.write_ply_cloud(str(d / "cloud.ply"), g["pcd_cloud"])
     np.savez(str(d / "cameras.npz"), scale_mat_0=g["scale_mat"])
     np.savez(str(d / "x-wfi_checked.npz"), lines3d=g["lines"], scores=g["scores"])
     torch.save({"lines3d_wfi_checked": torch.tensor(g["lines"]), "junctions3d_initial": torch.tensor(g["abc_junctions_pred"])}, str(d / "x-neat.pth"))
@@ -69,13 +69,13 @@ def common(d, g):
 
 @pytest.mark.gpu
 def test_dtu_mesh_and_pcd_end_to_end(files):
-    from neat_amd import evaluate as E
+    from neat_amd import ply
     g, d = files
     r = run_cli(["dtu-mesh", "--data", d / "surface_100.ply", "--vis_out_dir", d / "vis", "--seed", 11] + common(d, g))
     assert r.returncode == 0, r.stderr
-    vis = E.read_ply(str(d / "vis" / "vis_007_s2d.ply"))
+    vis = ply.read_ply(str(d / "vis" / "vis_007_s2d.ply"))
     assert vis["points"].shape == (len(g["stl"]), 3) and vis["colors"].shape == (len(g["stl"]), 3)
-    down = E.read_ply(str(d / "vis" / "vis_007_d2s.ply"))
+    down = ply.read_ply(str(d / "vis" / "vis_007_d2s.ply"))
     assert np.array_equal(down["points"], g["mesh_data_down"]) and down["colors"].shape == down["points"].shape
     # the averaged distances are counted from the colours: white to red is a distance below max_dist, green one beyond, blue not scored
     na = int((down["colors"][:, 0] == 255).sum())

@@ -115,31 +115,31 @@ def test_round_rule_equals_the_sequential_loop(case):
 
 def test_ply_reader_ascii_binary_and_our_own_meshes(tmp_path):
     import torch
-    from neat_amd import evaluate as E, mesh
+    from neat_amd import ply
     v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0.5, 0.25, 2]], dtype=np.float64)
     f = np.array([[0, 1, 2], [1, 2, 3]], dtype=np.int32)
     p = tmp_path / "a.ply"
     p.write_text("ply\nformat ascii 1.0\ncomment made by hand\nelement vertex 4\nproperty float x\nproperty float y\nproperty float z\n"
                  "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face 2\nproperty list uchar int vertex_indices\n"
                  "end_header\n" + "".join("%r %r %r 255 0 7\n" % tuple(float(x) for x in r) for r in v) + "3 0 1 2\n3 1 2 3\n")
-    r = E.read_ply(str(p))
+    r = ply.read_ply(str(p))
     assert np.array_equal(r["points"], v) and np.array_equal(r["faces"], f) and r["colors"].shape == (4, 3) and r["normals"] is None
     nrm = np.tile([[0.0, 0.0, 1.0]], (4, 1))
-    mesh.write_ply(str(tmp_path / "b.ply"), torch.tensor(v, dtype=torch.float32), torch.tensor(f), torch.tensor(nrm, dtype=torch.float32))
-    r = E.read_ply(str(tmp_path / "b.ply"))
+    ply.write_ply(str(tmp_path / "b.ply"), torch.tensor(v, dtype=torch.float32), torch.tensor(f), torch.tensor(nrm, dtype=torch.float32))
+    r = ply.read_ply(str(tmp_path / "b.ply"))
     assert np.array_equal(r["points"], v.astype(np.float32).astype(np.float64)) and np.array_equal(r["faces"], f)
     assert np.array_equal(r["normals"], nrm)
-    mesh.write_ply(str(tmp_path / "c.ply"), torch.tensor(v, dtype=torch.float32), torch.tensor(f))
-    assert E.read_ply(str(tmp_path / "c.ply"))["normals"] is None
-    E.write_ply_cloud(str(tmp_path / "d.ply"), v * 1.1, np.array([[1, 0, 0.5]] * 4))          # a double cloud, as the stl clouds are
-    r = E.read_ply(str(tmp_path / "d.ply"))
+    ply.write_ply(str(tmp_path / "c.ply"), torch.tensor(v, dtype=torch.float32), torch.tensor(f))
+    assert ply.read_ply(str(tmp_path / "c.ply"))["normals"] is None
+    ply.write_ply_cloud(str(tmp_path / "d.ply"), v * 1.1, np.array([[1, 0, 0.5]] * 4))          # a double cloud, as the stl clouds are
+    r = ply.read_ply(str(tmp_path / "d.ply"))
     assert np.array_equal(r["points"], v * 1.1) and r["faces"] is None and r["colors"][0].tolist() == [255, 0, 128]
     (tmp_path / "e.ply").write_bytes(b"ply\nformat binary_big_endian 1.0\nelement vertex 0\nproperty float x\nend_header\n")
     with pytest.raises(ValueError):
-        E.read_ply(str(tmp_path / "e.ply"))
+        ply.read_ply(str(tmp_path / "e.ply"))
     (tmp_path / "f.ply").write_bytes(b"plx\n")
     with pytest.raises(ValueError):
-        E.read_ply(str(tmp_path / "f.ply"))
+        ply.read_ply(str(tmp_path / "f.ply"))
 
 
 def test_mat_and_npz_loaders(tmp_path, g20):

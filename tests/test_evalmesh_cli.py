@@ -4,7 +4,6 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 from tests import evalmesh_f64 as E
 from tests import mesh_f64 as M
@@ -16,15 +15,8 @@ BOX = np.array([[-0.5, -1.0, -1.0], [0.3, 1.0, 1.0]])      # what the pipeline u
 
 @pytest.fixture(scope="module")
 def run_dir(tmp_path_factory):
-    from neat_amd import networks, synth
-    run = tmp_path_factory.mktemp("exps") / "toy" / "2024_01_01_00_00_00"
-    (run / "checkpoints" / "ModelParameters").mkdir(parents=True)
-    conf = {"train": {"expname": "toy", "model_class": "model.networks.neat_wfr_rend_a.VolSDFNetwork"},
-            "plot": {"plot_nimgs": 1, "resolution": 100, "grid_boundary": [-1.5, 1.5]}, "model": synth.ABC_NEAT_A_MODEL_CONF}
-    (run / "runconf.conf").write_text(synth.hocon_text(conf))
-    model = networks.VolSDFNetwork(synth.ABC_NEAT_A_MODEL_CONF)
-    model.load_state_dict({k: torch.tensor(v) for k, v in synth.synth_state_dict(7, "init").items()})
-    torch.save({"model_state_dict": model.state_dict(), "epoch": EPOCH}, str(run / "checkpoints" / "ModelParameters" / "latest.pth"))
+    from tests.util_run import write_synth_run
+    run = write_synth_run(tmp_path_factory.mktemp("evalmesh_cli"), epoch=EPOCH, plot={"plot_nimgs": 1, "resolution": 100, "grid_boundary": [-1.5, 1.5]})["dir"]
     np.savez(run / "bbs.npz", **{"65": BOX / [[1.5], [1.0]]})
     S = np.eye(4)
     S[:3, :3] *= 300.0
@@ -39,7 +31,7 @@ def cli(run, *args):
 
 
 def test_eval_file_name_world_frame_and_kept_file(run_dir, capsys):
-    from neat_amd import evaluate, mesh
+    from neat_amd import mesh, ply
     out = run_dir / str(EPOCH) / "scan.ply"
     cli(run_dir, "--no-world", "--cams", run_dir / "cameras.npz", "--normals")
     text = capsys.readouterr().out
@@ -57,7 +49,7 @@ def test_eval_file_name_world_frame_and_kept_file(run_dir, capsys):
     S = np.load(run_dir / "cameras.npz")["scale_mat_0"]
     assert wn is None and np.array_equal(wf, f) and np.array_equal(w, E.affine_rows(v, S[:3]))      # scale_mat_0 of --cams
     # the reader of the evaluation takes the file as it is
-    back = evaluate.read_ply(str(out))
+    back = ply.read_ply(str(out))
     assert np.array_equal(back["points"], w.astype(np.float64)) and np.array_equal(back["faces"], wf)
 
 

@@ -33,11 +33,10 @@ def test_flags_and_defaults():
 def test_file_naming_and_plot_block_on_a_fake_run_directory(tmp_path):
     from neat_amd import conf as conf_mod, mesh
     from neat_amd.synth import hocon_text
-    run = tmp_path / "exps" / "toy" / "2024_01_01_00_00_00"
-    (run / "checkpoints" / "ModelParameters").mkdir(parents=True)
+    from tests.util_run import write_synth_run
+    run = write_synth_run(tmp_path, plot={"plot_nimgs": 1, "resolution": 100, "grid_boundary": [-1.5, 1.5]})["dir"]
     assert mesh.out_path(str(run), 1000) == str(run / "plots" / "surface_1000.ply")          # the reference's name (plots.py)
     conf_path = run / "runconf.conf"
-    conf_path.write_text(hocon_text({"train": {"expname": "toy"}, "plot": {"plot_nimgs": 1, "resolution": 100, "grid_boundary": [-1.5, 1.5]}}))
     block = mesh.plot_block(conf_mod.parse_file(str(conf_path)))
     assert int(block["resolution"]) == 100 and [float(v) for v in block["grid_boundary"]] == [-1.5, 1.5]
     conf_path.write_text(hocon_text({"train": {"expname": "toy"}}))
@@ -55,7 +54,7 @@ def test_runner_takes_vis_mesh():
 
 @pytest.mark.gpu
 def test_cli_end_to_end_on_a_runner_checkpoint(tmp_path):
-    from neat_amd import mesh, synth
+    from neat_amd import mesh, run_io, synth
     from neat_amd.runner import TrainRunner
     from tests.test_runner import _toy_scene, _hocon
     _toy_scene(tmp_path / "data" / "abc" / "toy", n_views=3)
@@ -90,7 +89,8 @@ def test_cli_end_to_end_on_a_runner_checkpoint(tmp_path):
     out = mesh.out_path(run_dir, 1)                               # `latest` is the checkpoint of epoch 1
     assert os.path.exists(out), os.listdir(os.path.dirname(out))
     v, n, f = M.read_ply(out)
-    model, epoch, root, plot = mesh.load(conf_path, "latest", torch.device("cuda:0"))
+    model, epoch, root, conf_read = run_io.load_model(conf_path, "latest", torch.device("cuda:0"))
+    plot = mesh.plot_block(conf_read)
     assert epoch == 1 and root == run_dir and int(plot["resolution"]) == 40
     res = mesh.surface(model, plot_conf=plot)
     assert np.array_equal(v, res["verts"].cpu().numpy()) and np.array_equal(f, res["faces"].cpu().numpy())

@@ -186,20 +186,20 @@ def test_linspace_rule_is_numpy_linspace():
 
 
 def test_ply_round_trip(tmp_path):
-    from neat_amd import mesh
+    from neat_amd import ply
     rng = np.random.default_rng(0)
     v = rng.normal(size=(11, 3)).astype(np.float32)
     n = rng.normal(size=(11, 3)).astype(np.float32)
     f = rng.integers(0, 11, size=(7, 3)).astype(np.int32)
     for normals in (n, None):
         path = str(tmp_path / "m.ply")
-        mesh.write_ply(path, v, f, normals)
+        ply.write_ply(path, v, f, normals)
         v2, n2, f2 = M.read_ply(path)
         assert np.array_equal(v2, v) and np.array_equal(f2, f)
         assert (n2 is None) if normals is None else np.array_equal(n2, n)
         assert not os.path.exists(path + ".tmp")
     with pytest.raises(ValueError):
-        mesh.write_ply(str(tmp_path / "bad.ply"), v, f, n[:3])
+        ply.write_ply(str(tmp_path / "bad.ply"), v, f, n[:3])
 
 
 def test_entry_points_check_their_arguments_before_any_launch():

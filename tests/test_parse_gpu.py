@@ -242,8 +242,8 @@ def _f64_restatement(junc, views, thr):
 
 @pytest.mark.gpu
 def test_cli_end_to_end_on_a_runner_checkpoint(tmp_path):
-    from neat_amd import parsing, synth
-    from neat_amd.parse import load, out_basename
+    from neat_amd import parsing, run_io, synth
+    from neat_amd.parse import out_basename
     from neat_amd.runner import TrainRunner
     from tests.test_runner import _toy_scene, _hocon
     _toy_scene(tmp_path / "data" / "abc" / "toy", n_views=6)
@@ -280,7 +280,8 @@ def test_cli_end_to_end_on_a_runner_checkpoint(tmp_path):
     assert saved["kwargs"]["distance"] == 50 and saved["kwargs"]["sdf_junction_refine"] is True
     # the same model outputs through the test-side float64 restatement
     dev = torch.device("cuda:0")
-    model, dataset, _ = load(conf_path, "latest", dev, data_root=str(tmp_path / "data"))
+    model, _, _, conf_read = run_io.load_model(conf_path, "latest", dev)
+    dataset = run_io.build_dataset(conf_read, str(tmp_path / "data"), distance_threshold=1.0)
     thr = dict(line_dis_threshold=50, line_score_threshold=0.01, junc_match_threshold=0.2, ckdist=100.0, ckview=1)
     res, info = parsing.wireframe_recon(model, dataset, device=dev, **{k: v for k, v in thr.items() if k != "line_score_threshold"})
     junc = parsing.refined_junctions(model)

@@ -1,5 +1,5 @@
 """CPU checks of `python -m neat_amd.post`: argument parsing, output file names, --overwrite, and that the files it writes are files the
-loaders of neat_amd.evaluate and neat_amd.show accept.  No device is touched."""
+loader of neat_amd.evaluate and neat_amd.show (run_io.load_lines) accepts.  No device is touched."""
 import os
 
 import numpy as np
@@ -61,7 +61,7 @@ def test_snap_help_needs_no_device(capsys):
 
 
 def test_written_files_are_read_by_evaluate_and_show(tmp_path):
-    from neat_amd import evaluate, show
+    from neat_amd import run_io
     lines = np.arange(24, dtype=np.float32).reshape(4, 2, 3)
     fused = tmp_path / "x-fused.npz"
     np.savez(fused, lines3d=lines[:3], score=np.ones(4, np.float32), count=np.ones(4, np.int32), keep=np.array([1, 1, 1, 0], bool))
@@ -72,6 +72,6 @@ def test_written_files_are_read_by_evaluate_and_show(tmp_path):
     edges = np.array([[0, 1], [1, 2]], np.int32)
     np.savez(snap, junctions=junc, edges=edges, lines3d=junc[edges], count=np.ones(3, np.int32))
     for path, n in ((fused, 3), (ref, 2), (snap, 2)):
-        got, scores = evaluate._load_lines(str(path))
+        got, scores = run_io.load_lines(str(path))
         assert scores is None and np.asarray(got).shape == (n, 2, 3)          # `score` is not `scores`: dtu-lines does not filter by it
-        assert show.load_lines(str(path)).shape == (n, 2, 3)
+        assert run_io.load_lines(str(path), pth_key="lines3d_wfi")[0].shape == (n, 2, 3)

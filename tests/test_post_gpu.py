@@ -319,21 +319,10 @@ def test_snap_cases():
 # ---- command line ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_cli_runs_each_subcommand_on_a_toy_run_directory(tmp_path, capsys):
-    from neat_amd import networks, post, synth
-    from tests.test_runner import _hocon, _toy_scene
-    _toy_scene(tmp_path / "data" / "abc" / "toy", n_views=3)
-    conf = {"train": {"expname": "toy_post", "dataset_class": "datasets.blender_hawp_dataset.BlenderDataset",
-                      "model_class": "model.networks.neat_wfr_rend_a.VolSDFNetwork", "loss_class": "model.networks.loss_wfr.VolSDFLoss"},
-            "loss": dict(synth.ABC_NEAT_A_LOSS_CONF),
-            "dataset": {"data_dir": "abc/toy", "img_res": [64, 64], "reverse_coordinate": True},
-            "model": synth.ABC_NEAT_A_MODEL_CONF}
-    run = tmp_path / "run"
-    (run / "checkpoints" / "ModelParameters").mkdir(parents=True)
-    conf_path = run / "runconf.conf"
-    conf_path.write_text(_hocon(conf))
-    torch.manual_seed(0)
-    model = networks.VolSDFNetwork(synth.ABC_NEAT_A_MODEL_CONF)
-    torch.save({"model_state_dict": model.state_dict(), "epoch": 0}, run / "checkpoints" / "ModelParameters" / "latest.pth")
+    from neat_amd import conf as conf_mod, post, run_io
+    from tests.util_run import synth_init_model, write_synth_run
+    paths = write_synth_run(tmp_path, n_views=3)
+    run, conf_path, model = paths["dir"], paths["conf"], synth_init_model()
     rng = np.random.default_rng(0)
     blocks = np.empty(2, dtype=object)                                   # per-view blocks, as -all.npz holds lines3d_all
     blocks[0], blocks[1] = (rng.uniform(-0.4, 0.4, (k, 2, 3)).astype(np.float32) for k in (30, 50))
@@ -341,7 +330,7 @@ def test_cli_runs_each_subcommand_on_a_toy_run_directory(tmp_path, capsys):
     np.savez(data, lines3d=blocks, scores=np.full(80, 0.001, np.float32))
     lines = torch.tensor(np.concatenate(list(blocks))).to(dev())
     common = ["--conf", str(conf_path), "--data", str(data), "--data_root", str(tmp_path / "data")]
-    views = post.views_of(post.load_dataset(str(conf_path), str(tmp_path / "data")), dev())
+    views = post.views_of(run_io.build_dataset(conf_mod.parse_file(conf_path), paths["data_root"], distance_threshold=1.0), dev())
     assert len(views["m"]) == 3 and min(views["m"]) > 0 and (views["height"], views["width"]) == (64.0, 64.0)
 
     assert post.main(["fuse"] + common + ["--dis", "400"]) == 0

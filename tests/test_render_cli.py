@@ -31,8 +31,8 @@ def test_bad_combinations_exit(bad):
 
 
 def test_file_names_on_a_fake_run_directory(tmp_path):
-    run = tmp_path / "exps" / "toy" / "2024_01_01_00_00_00"
-    (run / "checkpoints" / "ModelParameters").mkdir(parents=True)
+    from tests.util_run import write_synth_run
+    run = write_synth_run(tmp_path)["dir"]
     d = run / "rendering_1000"
     assert render.out_dir(str(run), 1000) == str(d)
     assert render.out_paths(str(run), 1000, 7) == {"rgb": str(d / "eval_007.png"), "normal": str(d / "normal_007.png"),

@@ -156,7 +156,7 @@ CONF_TRAIN = {"expname": "toy_render", "dataset_class": "datasets.blender_hawp_d
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Two epochs of the runner on the toy scene (64 x 64, 3 views) with vis_images=True, then the checkpoint loaded once."""
-    from neat_amd import mesh, synth
+    from neat_amd import run_io, synth
     from neat_amd.runner import TrainRunner
     from tests.test_runner import _toy_scene, _hocon
     tmp = tmp_path_factory.mktemp("render")
@@ -177,9 +177,8 @@ def run(tmp_path_factory):
     conf_path = os.path.join(run_dir, "runconf.conf")
     with open(conf_path, "w") as fh:
         fh.write(_hocon(conf))
-    from neat_amd import conf as conf_mod
-    model, epoch, root, _ = mesh.load(conf_path, "latest", torch.device(DEV))
-    dataset = render.load_dataset(conf_mod.parse_file(conf_path), str(tmp / "data"))
+    model, epoch, root, conf_read = run_io.load_model(conf_path, "latest", torch.device(DEV))
+    dataset = run_io.build_dataset(conf_read, str(tmp / "data"))
     assert epoch == 2 and root == run_dir and len(dataset) == 3
     return {"dir": run_dir, "conf": conf_path, "data": str(tmp / "data"), "model": model, "dataset": dataset, "stats": stats, "tmp": tmp}
 

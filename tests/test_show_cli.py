@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from neat_amd import show
+from neat_amd import run_io, show
 
 
 def _opt(*argv):
@@ -63,15 +63,15 @@ def test_lines3d_object_array_is_concatenated(tmp_path):
         obj[i] = b
     path = str(tmp_path / "a-all.npz")
     np.savez(path, lines3d=obj)
-    got = show.load_lines(path)
+    got = run_io.load_lines(path)[0]
     assert got.shape == (8, 2, 3) and got.dtype == np.float64 and np.array_equal(got, np.concatenate(blocks).astype(np.float64))
     flat = str(tmp_path / "a-wfi_checked.npz")
     np.savez(flat, lines3d=blocks[2], scores=np.ones(5))
-    assert np.array_equal(show.load_lines(flat), blocks[2].astype(np.float64))
+    assert np.array_equal(run_io.load_lines(flat)[0], blocks[2].astype(np.float64))
     import torch
     pth = str(tmp_path / "a-neat.pth")
     torch.save({"lines3d_wfi_checked": torch.tensor(blocks[0])}, pth)
-    assert np.array_equal(show.load_lines(pth), blocks[0].astype(np.float64))
+    assert np.array_equal(run_io.load_lines(pth)[0], blocks[0].astype(np.float64))
     assert len(show.endpoints(np.stack([blocks[0][0], blocks[0][0][::-1]]))) == 2          # distinct endpoints
 
 

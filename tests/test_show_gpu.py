@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from neat_amd import _lib, show
+from neat_amd import _lib, run_io, show
 from tests import show_f64 as S
 from tests import show_scenes as Z
 
@@ -373,7 +373,7 @@ def test_face_index_out_of_range():
 # ------------------------------------------------------------------ the command line
 def test_cli_end_to_end(tmp_path, capsys):
     from PIL import Image
-    from neat_amd.mesh import write_ply
+    from neat_amd.ply import write_ply
     verts, faces, edges = Z.cube()
     run = tmp_path / "run" / "wireframes"
     run.mkdir(parents=True)
@@ -386,7 +386,7 @@ def test_cli_end_to_end(tmp_path, capsys):
     assert "device rendering" in text and "encoding" in text and "12 segments, 12 triangles, 4 frames" in text
     out = os.path.join(str(run), "..", "video")
     w2c = show.orbit(*show.POSES["dtu"], frames=4, step=90.0)
-    lines = show.load_lines(data)
+    lines = run_io.load_lines(data)[0]
     want = show.render(lines, w2c, show.intrinsics(128, 96, 60.0), 128, 96, mesh=(verts.astype(np.float32), faces),
                        points=show.endpoints(lines)).cpu().numpy()
     assert want.shape == (4, 96, 128, 3) and len(np.unique(want.reshape(-1, 3), axis=0)) > 10

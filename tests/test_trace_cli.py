@@ -15,19 +15,9 @@ EPOCH = 7
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
-    from neat_amd import networks, synth
-    from tests.test_runner import _toy_scene
-    tmp = tmp_path_factory.mktemp("trace_cli")
-    _toy_scene(tmp / "data" / "abc" / "toy", n_views=3)
-    run_dir = tmp / "exps" / "toy" / "2024_01_01_00_00_00"
-    (run_dir / "checkpoints" / "ModelParameters").mkdir(parents=True)
-    conf = {"train": {"expname": "toy", "dataset_class": "datasets.blender_hawp_dataset.BlenderDataset",
-                      "model_class": "model.networks.neat_wfr_rend_a.VolSDFNetwork", "split_n_pixels": 1024},
-            "dataset": {"data_dir": "abc/toy", "img_res": [64, 64], "reverse_coordinate": True}, "model": synth.ABC_NEAT_A_MODEL_CONF}
-    (run_dir / "runconf.conf").write_text(synth.hocon_text(conf))
-    model = networks.VolSDFNetwork(synth.ABC_NEAT_A_MODEL_CONF)
-    model.load_state_dict({k: torch.tensor(v) for k, v in synth.synth_state_dict(7, "init").items()})
-    torch.save({"model_state_dict": model.state_dict(), "epoch": EPOCH}, str(run_dir / "checkpoints" / "ModelParameters" / "latest.pth"))
+    from tests.util_run import write_synth_run
+    run = write_synth_run(tmp_path_factory.mktemp("trace_cli"), epoch=EPOCH, n_views=3, train_extra={"split_n_pixels": 1024})
+    run_dir = run["dir"]
     # a wireframe: short segments well outside the initial surface (a sphere of about 0.6) and segments inside it
     rng = np.random.default_rng(1)
     u = rng.standard_normal((12, 3))
@@ -36,11 +26,11 @@ def run(tmp_path_factory):
     (run_dir / "wireframes").mkdir()
     data = run_dir / "wireframes" / "latest-abcdefgh-wfi.npz"
     np.savez(data, lines3d=lines)
-    return {"dir": run_dir, "conf": str(run_dir / "runconf.conf"), "data_root": str(tmp / "data"), "lines": lines, "data": str(data)}
+    return {**run, "lines": lines, "data": str(data)}
 
 
 def test_check_writes_the_occlusion_file_and_keeps_it(run, capsys):
-    from neat_amd import show, trace
+    from neat_amd import run_io, trace
     args = ["check", "--conf", run["conf"], "--data", run["data"], "--data_root", run["data_root"], "--min-views", "1", "--precision", "fp32", "--json"]
     assert trace.main(args) == 0
     out = capsys.readouterr().out
@@ -56,11 +46,10 @@ def test_check_writes_the_occlusion_file_and_keeps_it(run, capsys):
     assert np.array_equal(kept, views >= 1) and np.array_equal(lines, run["lines"][kept]) and int(kept.sum()) == report["kept"]
     # segments inside the surface are seen by no camera; a segment outside it by at least one of three cameras around the object
     assert not kept[6:].any() and (views[6:] == 0).all() and kept[:6].any() and views.max() <= 3
-    assert np.array_equal(show.load_lines(path), lines)
+    assert np.array_equal(run_io.load_lines(path)[0], lines)
     # the library gives what the file holds
-    from neat_amd import conf as conf_mod, mesh, render
-    model, _, _, _ = mesh.load(run["conf"], "latest", torch.device("cuda:0"), precision="fp32")
-    ds = render.load_dataset(conf_mod.parse_file(run["conf"]), run["data_root"])
+    model, _, _, conf = run_io.load_model(run["conf"], "latest", torch.device("cuda:0"), precision="fp32")
+    ds = run_io.build_dataset(conf, run["data_root"])
     cams = np.linalg.inv(np.stack([ds.pose_all[i].numpy().astype(np.float64) for i in range(3)]))
     frac = trace.visible_lines(model, torch.from_numpy(run["lines"]), cams).cpu().numpy()
     assert np.array_equal(trace.keep_rule(frac, 1, 0.5)[0], views)

@@ -183,10 +183,9 @@ def test_target_rays_and_visibility_with_an_analytic_field():
 @pytest.fixture(scope="module", params=["fp32", None])
 def net_view(request):
     """The synthetic-conf model at its geometric initialisation (a sphere-like surface), a 48 x 64 view from outside."""
-    from neat_amd import networks, synth
-    model = networks.VolSDFNetwork(synth.ABC_NEAT_A_MODEL_CONF)
-    model.load_state_dict({k: torch.tensor(v) for k, v in synth.synth_state_dict(7, "init").items()})
-    model.to(DEV).eval()
+    from neat_amd import synth
+    from tests.util_run import synth_init_model
+    model = synth_init_model().to(DEV).eval()
     if request.param is not None:
         model.set_precision(request.param)
     H, W = 48, 64

@@ -174,11 +174,11 @@ def test_keep_rule_on_a_hand_made_table():
 
 
 def test_occl_file_layout_and_readers(tmp_path):
-    from neat_amd import show, trace
+    from neat_amd import run_io, trace
     rng = np.random.default_rng(0)
     lines = rng.uniform(-1, 1, (6, 2, 3))
     np.savez(tmp_path / "latest-h-wfi.npz", lines3d=lines)
-    assert np.array_equal(trace.load_lines(str(tmp_path / "latest-h-wfi.npz")), lines)
+    assert np.array_equal(run_io.load_lines(str(tmp_path / "latest-h-wfi.npz"), pth_key="lines3d_wfi")[0], lines)
     views = np.array([5, 0, 7, 1, 9, 3])
     kept = views >= 5
     path = trace.out_path(str(tmp_path / "latest-h-wfi.npz"))
@@ -188,8 +188,8 @@ def test_occl_file_layout_and_readers(tmp_path):
         assert z["views"].dtype == np.int32 and z["views"].tolist() == views.tolist()
         assert z["kept"].dtype == bool and z["kept"].tolist() == kept.tolist()
         assert z["lines3d"].shape == (3, 2, 3) and np.array_equal(z["lines3d"], lines[kept])
-    assert np.array_equal(show.load_lines(path), lines[kept])            # neat_amd.show reads the file as it is
+    assert np.array_equal(run_io.load_lines(path)[0], lines[kept])            # neat_amd.show reads the file as it is
     assert os.listdir(tmp_path).count(os.path.basename(path)) == 1 and not [f for f in os.listdir(tmp_path) if "tmp" in f]
     import torch
     torch.save({"lines3d_wfi": torch.from_numpy(lines).float(), "lines3d_wfi_checked": torch.zeros(0, 2, 3)}, str(tmp_path / "latest-h-neat.pth"))
-    assert np.array_equal(trace.load_lines(str(tmp_path / "latest-h-neat.pth")), lines.astype(np.float32).astype(np.float64))
+    assert np.array_equal(run_io.load_lines(str(tmp_path / "latest-h-neat.pth"), pth_key="lines3d_wfi")[0], lines.astype(np.float32).astype(np.float64))
