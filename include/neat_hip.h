@@ -671,6 +671,29 @@ size_t neat_post_snap_ws_bytes(int n, int G);
 int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique, float* junctions, int* pcount, int* edges, float* lines_out,
                    int* counts, void* ws, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): ray casting against an indexed triangle mesh
+ * (neat_amd/raycast.py; what open3d's RaycastingScene.cast_rays answers in code/evaluation/abc-analysis.py :44-56).  The rule of
+ * intersection (Woop, Benthin, Wald 2013, decided in float64, both windings, edges inclusive, ties in t to the lowest face index), the
+ * tree and the walk: neat_amd/csrc/kernels_raycast.hpp; tests/raycast_f64.py restates them in float64.  The result is the
+ * brute-force minimum over all triangles under that rule.  Asynchronous on the stream, no allocation, no atomics: two runs give the
+ * same bytes.  Bad arguments return -1 before any launch.
+ *
+ * neat_raycast_bvh_bytes / neat_raycast_ws_bytes : the sizes of the tree and of the build's workspace for nf faces, both 256-byte
+ *   aligned caller-owned device memory; 0 for nf < 0 or nf > 2^24 (bvh_bytes(0) > 0: the empty tree).  ws is free after the build.
+ * neat_raycast_build : verts [nv,3] float64, faces [nf,3] int32 (as neat_show_mesh takes them).  Triangles are sorted by the Morton key of
+ *   their centroid (rocprim radix sort) into the implicit complete binary tree over a power of two of leaves, float32 boxes rounded
+ *   outwards; a triangle with a non-finite vertex or zero area is never hit.  A face index outside [0, nv) is found before any vertex
+ *   is read: the first int32 of bvh (the status word, 0 otherwise) becomes 1 and the tree is empty, so every cast misses.
+ * neat_raycast_cast : origins, dirs [R,3] float32 (any length of dir; t is in units of it), t_min, t_max [R] or null (0 and +inf); a hit
+ *   has t_min <= t < t_max.  any_hit = 0: the closest hit; 1: the first accepted hit the walk meets (visibility).  t [R] (+inf on a
+ *   miss), tri [R] the original face index (-1 on a miss), uv [R,2] barycentrics (hit = (1 - u - v) v0 + u v1 + v v2; 0 on a miss),
+ *   counts [R,2] uint32 (node boxes tested, triangles tested) or null.  nf = the build's. */
+size_t neat_raycast_bvh_bytes(int nf);
+size_t neat_raycast_ws_bytes(int nf);
+int neat_raycast_build(const double* verts, int nv, const int* faces, int nf, void* bvh, void* ws, void* stream);
+int neat_raycast_cast(const void* bvh, int nf, const float* origins, const float* dirs, const float* t_min, const float* t_max, int R, int any_hit,
+                      float* t, int* tri, float* uv, unsigned* counts, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

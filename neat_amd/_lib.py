@@ -180,6 +180,10 @@ _SIGNATURES = {
     "neat_trace_finish": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_trace_target_rays": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                               ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_raycast_bvh_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "neat_raycast_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "neat_raycast_build": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
+    "neat_raycast_cast": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "neat_post_fuse_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "neat_post_fuse": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),

@@ -1,7 +1,7 @@
 // C entry points of libneat_hip.so that have no 16-bit storage type (see include/neat_hip.h): camera, eikonal points, the depth
 // samplers, batch gather / copy, Adam, the junction MLP, the losses, LSAP, DBSCAN, the wireframe parsing stages, the surface mesh, the evaluation
 // mesh, the evaluation of a reconstruction, the wireframe / mesh pictures, the frames of rendered views, the sphere tracer,
-// the fuse / refine / snap post-processing, volume weights.
+// the fuse / refine / snap post-processing, ray casting against a triangle mesh, volume weights.
 // Compiled once (build.sh), without NEAT_HALF; the network orchestration and its f16 twin are neat_net.hip.  What crosses the
 // boundary: the point stride of an SDF workspace, which the callers of the samplers pass in (neat_sdf_ldp), and the two tuning keys below.
 #include "kernels_sampler.hpp"
@@ -14,6 +14,7 @@
 #include "kernels_frame.hpp"
 #include "kernels_trace.hpp"
 #include "kernels_post.hpp"
+#include "kernels_raycast.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -1294,6 +1295,95 @@ int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique,
   NEAT_CHECK(rocprim::radix_sort_keys((void*)(p + w.sort), tb, pkey, spkey, (size_t)n, 0u, 64u, st));
   hipLaunchKernelGGL(post_snap_unique_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long*)spkey, n, (const float*)junctions, idx, edges,
                      lines_out, counts + 1);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: ray casting against a triangle mesh (kernels_raycast.hpp) ---------------------------------------------------------------
+struct RaycastLayout { int L, per; size_t nodes, tris, bvh_total; size_t key, skey, val, sval, partial, box, sort, sort_bytes, ws_total; };
+
+static bool raycast_layout(int nf, RaycastLayout* w) {
+  if (nf < 0 || nf > RC_MAX_FACES) return false;
+  int L = 1;
+  while (L < nf) L <<= 1;
+  w->L = L;
+  w->per = std::min(L, RC_WG);
+  size_t o = 256;                                          // the status word
+  w->nodes = o; o += parse_al((size_t)2 * L * 6 * sizeof(float));
+  w->tris = o; o += parse_al((size_t)nf * RC_TRI_STRIDE * sizeof(double));
+  w->bvh_total = o;
+  // room for the radix sort, fixed by nf alone so that the size does not depend on a device being present: rocprim's temporary keys
+  // and values (12 bytes a triangle), its histograms and per-block look-back states; the build asks rocprim and refuses if it wants more
+  const size_t sb = nf > 0 ? (size_t)32 * nf + ((size_t)4 << 20) : 0;
+  w->sort_bytes = sb;
+  o = 0;
+  w->key = o; o += parse_al((size_t)nf * sizeof(unsigned long long));
+  w->skey = o; o += parse_al((size_t)nf * sizeof(unsigned long long));
+  w->val = o; o += parse_al((size_t)nf * sizeof(int));
+  w->sval = o; o += parse_al((size_t)nf * sizeof(int));
+  w->partial = o; o += parse_al((size_t)((nf + RC_WG - 1) / RC_WG) * 6 * sizeof(double));
+  w->box = o; o += 256;
+  w->sort = o; o += parse_al(sb);
+  w->ws_total = o;
+  return true;
+}
+
+size_t neat_raycast_bvh_bytes(int nf) {
+  RaycastLayout w;
+  return raycast_layout(nf, &w) ? w.bvh_total : 0;
+}
+
+size_t neat_raycast_ws_bytes(int nf) {
+  RaycastLayout w;
+  return raycast_layout(nf, &w) ? w.ws_total : 0;
+}
+
+int neat_raycast_build(const double* verts, int nv, const int* faces, int nf, void* bvh, void* ws, void* stream) {
+  RaycastLayout w;
+  if (nv < 0 || !bvh || ((uintptr_t)bvh & 255) || !raycast_layout(nf, &w)) return -1;
+  if (nf > 0 && (!faces || !ws || ((uintptr_t)ws & 255) || (nv > 0 && !verts))) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  char *b = (char*)bvh, *p = (char*)ws;
+  int* status = (int*)b;
+  float* nodes = (float*)(b + w.nodes);
+  double* tris = (double*)(b + w.tris);
+  NEAT_CHECK(hipMemsetAsync(b, 0, 256, st));
+  int* sval = nullptr;
+  if (nf > 0) {
+    unsigned long long *key = (unsigned long long*)(p + w.key), *skey = (unsigned long long*)(p + w.skey);
+    int* val = (int*)(p + w.val);
+    sval = (int*)(p + w.sval);
+    double *partial = (double*)(p + w.partial), *box = (double*)(p + w.box);
+    const int tiles = (nf + RC_WG - 1) / RC_WG;
+    size_t tb = 0;
+    NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, tb, key, skey, val, sval, (size_t)nf, 0u, 64u, st));
+    if (tb > w.sort_bytes) return -2;
+    hipLaunchKernelGGL(raycast_prep_kernel, dim3(tiles), dim3(RC_WG), 0, st, verts, nv, faces, nf, status, partial);
+    hipLaunchKernelGGL(raycast_scene_box_kernel, dim3(1), dim3(RC_WG), 0, st, (const double*)partial, tiles, box);
+    hipLaunchKernelGGL(raycast_key_kernel, dim3(tiles), dim3(RC_WG), 0, st, verts, faces, nf, (const int*)status, (const double*)box, key, val);
+    NEAT_CHECK(hipGetLastError());
+    NEAT_CHECK(rocprim::radix_sort_pairs((void*)(p + w.sort), tb, key, skey, val, sval, (size_t)nf, 0u, 64u, st));
+  }
+  hipLaunchKernelGGL(raycast_leaf_kernel, dim3(w.L / w.per), dim3(RC_WG), 0, st, verts, faces, nf, w.L, w.per, (const int*)status, (const int*)sval,
+                     nodes, tris);
+  if (w.L > w.per) hipLaunchKernelGGL(raycast_top_kernel, dim3(1), dim3(RC_TOP_WG), 0, st, nodes, w.L / w.per);
+  return (int)hipGetLastError();
+}
+
+int neat_raycast_cast(const void* bvh, int nf, const float* origins, const float* dirs, const float* t_min, const float* t_max, int R, int any_hit,
+                      float* t, int* tri, float* uv, unsigned* counts, void* stream) {
+  RaycastLayout w;
+  if (!bvh || ((uintptr_t)bvh & 255) || !raycast_layout(nf, &w) || R < 0 || R > INT_MAX / 4 || (any_hit != 0 && any_hit != 1)) return -1;
+  if (R == 0) return 0;
+  if (!origins || !dirs || !t || !tri || !uv) return -1;
+  const char* b = (const char*)bvh;
+  const float* nodes = (const float*)(b + w.nodes);
+  const double* tris = (const double*)(b + w.tris);
+  if (any_hit)
+    hipLaunchKernelGGL(raycast_cast_kernel<true>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, nodes, tris, nf, w.L, origins, dirs, t_min, t_max,
+                       R, t, tri, uv, counts);
+  else
+    hipLaunchKernelGGL(raycast_cast_kernel<false>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, nodes, tris, nf, w.L, origins, dirs, t_min, t_max,
+                       R, t, tri, uv, counts);
   return (int)hipGetLastError();
 }
 

@@ -1449,3 +1449,48 @@ def trace_target_rays(centres, rows, samples, radius, near, bias):
     _lib.check(_lib.lib().neat_trace_target_rays(_p(centres), F, _p(rows), int(rows.shape[1]), N, S, float(radius), float(near), float(bias),
                                                  _p(o), _p(d), _p(t_end), _p(ok), _stream()), "neat_trace_target_rays")
     return o, d, t_end, ok
+
+
+# ---- ray casting against a triangle mesh (neat_amd/raycast.py; csrc/kernels_raycast.hpp): no gradient ------------------------------------
+RAYCAST_MAX_FACES = 1 << 24
+
+
+def raycast_build(verts, faces):
+    """verts [nv,3] float64, faces [nf,3] int32 on the device -> the tree, a uint8 tensor (its first int32 is the status word: 1 after a
+    face index outside [0, nv), and every cast then misses)."""
+    lib = _lib.lib()
+    if not verts.is_cuda or verts.dtype != torch.float64 or faces.dtype != torch.int32 or faces.device != verts.device:
+        raise RuntimeError("raycast_build: verts float64 and faces int32 on one device (no CPU path)")
+    verts, faces = verts.detach().contiguous(), faces.detach().contiguous()
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    if verts.shape != (nv, 3) or faces.shape != (nf, 3) or nf > RAYCAST_MAX_FACES:
+        raise ValueError("raycast_build: verts [nv,3], faces [nf,3], nf <= 2^24")
+    dev = verts.device
+    bvh = _ws(lib.neat_raycast_bvh_bytes(nf), dev)
+    ws = _ws(lib.neat_raycast_ws_bytes(nf), dev)
+    _lib.check(lib.neat_raycast_build(_p(verts) if nv else None, nv, _p(faces) if nf else None, nf, _p(bvh), _p(ws), _stream()),
+               "neat_raycast_build")
+    return bvh
+
+
+def raycast_cast(bvh, nf, origins, dirs, t_min=None, t_max=None, any_hit=False, counts=None):
+    """origins, dirs [R,3] float32, t_min / t_max [R] or None -> (t [R] float32, +inf on a miss; tri [R] int32, -1 on a miss; uv [R,2]).
+    counts: a contiguous [R,2] tensor of 4-byte integers receives (node boxes tested, triangles tested) per ray."""
+    origins, dirs = _f32c(origins.detach()), _f32c(dirs.detach())
+    R = int(origins.shape[0])
+    if origins.shape != (R, 3) or dirs.shape != (R, 3):
+        raise ValueError("raycast_cast: origins and dirs [R, 3]")
+    lim = []
+    for x in (t_min, t_max):
+        x = None if x is None else _f32c(x.detach()).reshape(-1)
+        if x is not None and x.shape[0] != R:
+            raise ValueError("raycast_cast: t_min and t_max [R]")
+        lim.append(x)
+    if counts is not None and (not counts.is_cuda or counts.element_size() != 4 or counts.is_floating_point() or tuple(counts.shape) != (R, 2)
+                               or not counts.is_contiguous()):
+        raise ValueError("raycast_cast: counts is a contiguous [R, 2] tensor of 4-byte integers on the device")
+    dev = origins.device
+    t, tri, uv = torch.empty(R, device=dev), torch.empty(R, device=dev, dtype=torch.int32), torch.empty(R, 2, device=dev)
+    _lib.check(_lib.lib().neat_raycast_cast(_p(bvh), int(nf), _p(origins), _p(dirs), _p(lim[0]), _p(lim[1]), R, int(bool(any_hit)), _p(t), _p(tri),
+                                            _p(uv), _p(counts), _stream()), "neat_raycast_cast")
+    return t, tri, uv

@@ -1,4 +1,4 @@
-"""PLY files: the one reader of the tools, the mesh writer (neat_amd.mesh, the trainer's --vis_mesh) and the cloud writer (neat_amd.evaluate).
+"""PLY and OBJ files: the one reader of the tools, the mesh writer (neat_amd.mesh, the trainer's --vis_mesh) and the cloud writer (neat_amd.evaluate).
 tests/mesh_f64.read_ply is the tests' own, independent reader."""
 import os
 
@@ -79,6 +79,30 @@ def read_ply(path):
         if out["points"] is None:
             raise ValueError("%s: no vertex element" % path)
         return out
+
+
+def read_obj(path):
+    """A Wavefront OBJ -> (verts float64 [nv,3], faces int32 [nf,3], zero-based).  `v x y z [...]` and `f` records are read, everything else
+    is skipped; an index is `i`, `i/j`, `i//k` or `i/j/k` (the vertex index is the first), a negative one counts back from the vertices
+    read so far; a polygon becomes the fan about its first corner."""
+    verts, faces = [], []
+    with open(path, "r", errors="replace") as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                verts.append((float(tok[1]), float(tok[2]), float(tok[3])))
+            elif tok[0] == "f":
+                idx = []
+                for t in tok[1:]:
+                    i = int(t.split("/")[0])
+                    if i == 0:
+                        raise ValueError("%s: OBJ indices start at 1" % path)
+                    idx.append(i - 1 if i > 0 else len(verts) + i)
+                for k in range(1, len(idx) - 1):
+                    faces.append((idx[0], idx[k], idx[k + 1]))
+    return np.asarray(verts, dtype=np.float64).reshape(-1, 3), np.asarray(faces, dtype=np.int32).reshape(-1, 3)
 
 
 def write_ply(path, verts, faces, normals=None):

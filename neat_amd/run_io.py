@@ -4,7 +4,7 @@
     <run>/checkpoints/ModelParameters/<checkpoint>.pth       {"epoch", "model_state_dict"}, written by neat_amd.runner
     <run>/wireframes/{checkpoint}-{h}-{all,wfi,wfi_checked}.npz, -neat.pth      written by neat_amd.parse
 
-The trainer and every checkpoint tool (parse, mesh, render, trace, post, show, evaluate) stand on this module and on neat_amd.ply; none of
+The trainer and every tool (parse, mesh, render, trace, raycast, post, show, evaluate) stand on this module and on neat_amd.ply; none of
 them reaches into another tool for its files.
 """
 import json
@@ -38,6 +38,11 @@ def conf_class(conf, key):
     """The class a conf key names; the reference's class paths are mapped to their neat_amd counterparts."""
     name = conf.get_string(key)
     return get_class(CLASS_MAP.get(name, name))
+
+
+def parse_conf(conf_path):
+    """The parsed conf of a run (neat_amd.conf.parse_file)."""
+    return conf_mod.parse_file(conf_path)
 
 
 def build_dataset(conf, data_root, scan_id=-1, **overrides):
@@ -108,3 +113,21 @@ def load_cam_json(path):
     """The cam.json neat_amd.show writes, a JSON list of 4 x 4 world-to-camera matrices -> float64 [F,4,4]."""
     with open(path) as fh:
         return np.asarray(json.load(fh), dtype=np.float64).reshape(-1, 4, 4)
+
+
+def keep_rule(frac, min_views=5, min_frac=0.5):
+    """The keep rule of the occlusion checks (neat_amd.trace check, neat_amd.raycast check): frac [F,N], the visible fraction of line n from
+    view f -> (views int32 [N], the views that see at least min_frac of the line; kept bool [N]: at least min_views of them)."""
+    frac = np.asarray(frac, dtype=np.float64)
+    views = (frac >= float(min_frac)).sum(axis=0).astype(np.int32)
+    return views, views >= int(min_views)
+
+
+def write_occl(path, lines3d, views, kept):
+    """The file of an occlusion check: lines3d (the kept lines, as neat_amd.show and evaluate dtu-lines read them), views int32 [N] (the
+    seeing views per input line), kept bool [N]."""
+    lines3d = np.asarray(lines3d).reshape(-1, 2, 3)
+    kept = np.asarray(kept, dtype=bool)
+    tmp = path + ".tmp.npz"
+    np.savez(tmp, lines3d=lines3d[kept], views=np.asarray(views, dtype=np.int32), kept=kept)
+    os.replace(tmp, path)

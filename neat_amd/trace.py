@@ -16,8 +16,9 @@ way out).  A ray that has finished is in no later query; the host reads the acti
 stops at zero.  There is no host fallback.
 
 `check` is the occlusion-aware visibility test the reference runs against the ground-truth mesh (evaluation/abc-analysis.py:44-56,
-open3d ray casts), asked of the learnt SDF instead: a line is kept when at least --min-views of the dataset's cameras see at least
---min-frac of its --samples points.  It writes `<data stem>_occl.npz` beside the input: lines3d (the kept lines, as neat_amd.show and
+open3d ray casts), asked of the learnt SDF instead (against a triangle mesh it is `python -m neat_amd.raycast check`, which shares the
+keep rule and the file layout): a line is kept when at least --min-views of the dataset's cameras see at least --min-frac of its
+--samples points.  It writes `<data stem>_occl.npz` beside the input: lines3d (the kept lines, as neat_amd.show and
 evaluate dtu-lines read them), views int32 [N] (the seeing views per input line), kept bool [N].  The view frustum is not tested: that
 stays the 2-D check of neat_amd.parse (--ckdist --ckview).  A -neat.pth contributes its `lines3d_wfi`.
 """
@@ -173,25 +174,12 @@ def visible_lines(model, lines3d, cams, *, samples=16, bias=0.01, radius=None, *
 
 
 # ------------------------------------------------------------------ command line
-def keep_rule(frac, min_views=5, min_frac=0.5):
-    """frac [F,N], the visible fraction of line n from view f -> (views int32 [N], the views that see at least min_frac of the line;
-    kept bool [N]: at least min_views of them)."""
-    frac = np.asarray(frac, dtype=np.float64)
-    views = (frac >= float(min_frac)).sum(axis=0).astype(np.int32)
-    return views, views >= int(min_views)
+keep_rule, write_occl = run_io.keep_rule, run_io.write_occl          # shared with neat_amd.raycast check
 
 
 def out_path(data):
     """`<data stem>_occl.npz` beside the input."""
     return os.path.splitext(data)[0] + "_occl.npz"
-
-
-def write_occl(path, lines3d, views, kept):
-    lines3d = np.asarray(lines3d).reshape(-1, 2, 3)
-    kept = np.asarray(kept, dtype=bool)
-    tmp = path + ".tmp.npz"
-    np.savez(tmp, lines3d=lines3d[kept], views=np.asarray(views, dtype=np.int32), kept=kept)
-    os.replace(tmp, path)
 
 
 def build_parser():
