@@ -21,7 +21,8 @@
 #include <limits.h>
 #include <math.h>
 
-#include "kernels_parse.hpp"     // parse_block_exscan
+#include "block_util.hpp"      // block_carry_scan
+#include "device_util.hpp"     // rounded
 
 namespace neat {
 
@@ -83,16 +84,11 @@ __global__ __launch_bounds__(EVAL_SCAN_WG) void eval_exscan_kernel(const int* __
   __shared__ int s_bad;
   if (threadIdx.x == 0) s_bad = 0;
   __syncthreads();
-  long long carry = 0;
-  for (int t0 = 0; t0 < n; t0 += EVAL_SCAN_WG) {
-    const int t = t0 + threadIdx.x;
-    int v = t < n ? in[t] : 0;
-    if (v < 0) { s_bad = 1; v = 0; }
-    int tot;
-    const int e = parse_block_exscan(v, s_wave, &tot);
-    if (t < n) out[t] = (int)min(carry + e, (long long)INT_MAX);
-    carry += tot;
-  }
+  const long long carry = block_carry_scan(n, [&](int t) {
+    const int v = in[t];
+    if (v < 0) s_bad = 1;
+    return v < 0 ? 0 : v;
+  }, [&](int t, long long e) { out[t] = (int)min(e, (long long)INT_MAX); }, s_wave);
   __syncthreads();
   if (threadIdx.x == 0) {
     const bool ok = !s_bad && carry <= INT_MAX;

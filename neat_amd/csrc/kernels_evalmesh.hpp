@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "block_util.hpp"        // block_sum, block_minmax
 #include "device_util.hpp"       // rounded
 #include "kernels_mesh.hpp"      // MeshAxes
 
@@ -81,16 +82,6 @@ __global__ __launch_bounds__(EMESH_WG) void grid_points_affine_kernel(float* __r
 }
 
 // ---- (b) surface moments --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double emesh_block_sum(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return s;
-}
-
 // the value of component c of a level's block b: into the next level's [MOMENTS_N][stride], or (last level) into out [10] and the flag
 __device__ __forceinline__ void moments_put(int c, double s, double* __restrict__ dst, long long stride, long long b, bool last,
                                             double* __restrict__ out, int* __restrict__ flag) {
@@ -147,7 +138,7 @@ __global__ __launch_bounds__(EMESH_WG) void mesh_moments_kernel(const float* __r
   }
 #pragma unroll
   for (int c = 0; c < MOMENTS_N; ++c) {
-    const double s = emesh_block_sum(acc[c], sh);
+    const double s = block_sum<EMESH_WG>(acc[c], sh);
     if (threadIdx.x == 0) moments_put(c, s, dst, stride, blockIdx.x, last, out, flag);
   }
 }
@@ -159,7 +150,7 @@ __global__ __launch_bounds__(EMESH_WG) void mesh_moments_level_kernel(const doub
   __shared__ double sh[EMESH_WG / 64];
   const int c = blockIdx.y;
   const long long i = (long long)blockIdx.x * EMESH_WG + threadIdx.x;
-  const double s = emesh_block_sum(i < m ? src[(size_t)c * m + i] : 0.0, sh);
+  const double s = block_sum<EMESH_WG>(i < m ? src[(size_t)c * m + i] : 0.0, sh);
   if (threadIdx.x == 0) moments_put(c, s, dst, stride, blockIdx.x, last, out, flag);
 }
 
@@ -179,23 +170,6 @@ __global__ __launch_bounds__(EMESH_WG) void affine_rows3_kernel(float* __restric
   q[0] = (float)y[0]; q[1] = (float)y[1]; q[2] = (float)y[2];
 }
 
-__device__ __forceinline__ void bounds_block_minmax(double* lo, double* hi, double* sh) {      // sh [6][4]
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[r] = fmin(lo[r], __shfl_xor(lo[r], off));
-      hi[r] = fmax(hi[r], __shfl_xor(hi[r], off));
-    }
-    if ((threadIdx.x & 63) == 0) { sh[4 * r + (threadIdx.x >> 6)] = lo[r]; sh[12 + 4 * r + (threadIdx.x >> 6)] = hi[r]; }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    lo[r] = fmin(fmin(sh[4 * r], sh[4 * r + 1]), fmin(sh[4 * r + 2], sh[4 * r + 3]));
-    hi[r] = fmax(fmax(sh[12 + 4 * r], sh[12 + 4 * r + 1]), fmax(sh[12 + 4 * r + 2], sh[12 + 4 * r + 3]));
-  }
-}
 // partial [6 b .. 6 b + 5] = (min x, min y, min z, max x, max y, max z) of the mapped rows block b strides over; (+inf, -inf) if none
 __global__ __launch_bounds__(EMESH_WG) void affine_bounds3_partial_kernel(const float* __restrict__ v, int n, Affine34 A, double* __restrict__ partial) {
   __shared__ double sh[24];
@@ -206,7 +180,7 @@ __global__ __launch_bounds__(EMESH_WG) void affine_bounds3_partial_kernel(const 
 #pragma unroll
     for (int r = 0; r < 3; ++r) { lo[r] = fmin(lo[r], y[r]); hi[r] = fmax(hi[r], y[r]); }
   }
-  bounds_block_minmax(lo, hi, sh);
+  block_minmax<EMESH_WG>(lo, hi, sh);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) { partial[6 * blockIdx.x + r] = lo[r]; partial[6 * blockIdx.x + 3 + r] = hi[r]; }
@@ -219,7 +193,7 @@ __global__ __launch_bounds__(EMESH_WG) void affine_bounds3_finish_kernel(const d
 #pragma unroll
     for (int r = 0; r < 3; ++r) { lo[r] = fmin(lo[r], partial[6 * b + r]); hi[r] = fmax(hi[r], partial[6 * b + 3 + r]); }
   }
-  bounds_block_minmax(lo, hi, sh);
+  block_minmax<EMESH_WG>(lo, hi, sh);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) { out[r] = lo[r]; out[3 + r] = hi[r]; }

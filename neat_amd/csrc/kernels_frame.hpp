@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "block_util.hpp"      // block_sum, block_minmax
 #include "device_util.hpp"     // rounded
 
 namespace neat {
@@ -61,53 +62,35 @@ __global__ __launch_bounds__(FRAME_WG) void frame_put_kernel(const float* __rest
 }
 
 // ---- (b) the error sum --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double frame_run_sum(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
 template <typename T>
 __global__ __launch_bounds__(FRAME_WG) void frame_sum_kernel(const T* __restrict__ x, long long n, double* __restrict__ out) {
   __shared__ double sh[FRAME_WG / 64];
   const long long i = (long long)blockIdx.x * FRAME_WG + threadIdx.x;
-  const double s = frame_run_sum(i < n ? (double)x[i] : 0.0, sh);
+  const double s = block_sum<FRAME_WG>(i < n ? (double)x[i] : 0.0, sh);
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 // ---- (c) the finite range of a plane and its grey picture -----------------------------------------------------------------------------------
-__device__ __forceinline__ void frame_block_minmax(float& lo, float& hi, float* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, off));
-    hi = fmaxf(hi, __shfl_xor(hi, off));
-  }
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = lo; sh[4 + (threadIdx.x >> 6)] = hi; }
-  __syncthreads();
-  lo = fminf(fminf(sh[0], sh[1]), fminf(sh[2], sh[3]));
-  hi = fmaxf(fmaxf(sh[4], sh[5]), fmaxf(sh[6], sh[7]));
-}
 // partial[2 b], partial[2 b + 1] = (min, max) over the finite values block b strides over; (+inf, -inf) if it met none
 __global__ __launch_bounds__(FRAME_WG) void frame_range_partial_kernel(const float* __restrict__ x, long long n, float* __restrict__ partial) {
   __shared__ float sh[8];
-  float lo = INFINITY, hi = -INFINITY;
+  float lo[1] = {INFINITY}, hi[1] = {-INFINITY};
   for (long long i = (long long)blockIdx.x * FRAME_WG + threadIdx.x; i < n; i += (long long)gridDim.x * FRAME_WG) {
     const float v = x[i];
-    if (isfinite(v)) { lo = fminf(lo, v); hi = fmaxf(hi, v); }
+    if (isfinite(v)) { lo[0] = fminf(lo[0], v); hi[0] = fmaxf(hi[0], v); }
   }
-  frame_block_minmax(lo, hi, sh);
-  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = lo; partial[2 * blockIdx.x + 1] = hi; }
+  block_minmax<FRAME_WG>(lo, hi, sh);
+  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = lo[0]; partial[2 * blockIdx.x + 1] = hi[0]; }
 }
 __global__ __launch_bounds__(FRAME_WG) void frame_range_finish_kernel(const float* __restrict__ partial, int blocks, float* __restrict__ out) {
   __shared__ float sh[8];
-  float lo = INFINITY, hi = -INFINITY;
-  for (int b = threadIdx.x; b < blocks; b += FRAME_WG) { lo = fminf(lo, partial[2 * b]); hi = fmaxf(hi, partial[2 * b + 1]); }
-  frame_block_minmax(lo, hi, sh);
+  float lo[1] = {INFINITY}, hi[1] = {-INFINITY};
+  for (int b = threadIdx.x; b < blocks; b += FRAME_WG) { lo[0] = fminf(lo[0], partial[2 * b]); hi[0] = fmaxf(hi[0], partial[2 * b + 1]); }
+  block_minmax<FRAME_WG>(lo, hi, sh);
   if (threadIdx.x == 0) {
-    const bool any = lo <= hi;
-    out[0] = any ? lo : 0.0f;
-    out[1] = any ? hi : 0.0f;
+    const bool any = lo[0] <= hi[0];
+    out[0] = any ? lo[0] : 0.0f;
+    out[1] = any ? hi[0] : 0.0f;
   }
 }
 __global__ __launch_bounds__(FRAME_WG) void frame_grey_kernel(const float* __restrict__ x, long long n, const float* __restrict__ range,

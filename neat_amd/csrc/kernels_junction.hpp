@@ -13,6 +13,7 @@
 // with -1; *n_match = number of pairs (-1: infeasible, i.e. a non-finite cost).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "block_util.hpp"      // block_compact
 #include "device_util.hpp"
 
 namespace neat {
@@ -52,31 +53,6 @@ __device__ __forceinline__ LsapKey lsap_shfl_xor(const LsapKey& k, int m) {
   return o;
 }
 
-// ordered compaction of the indices i in [0,n) with flag(i) != 0 into out[]; returns the count (all threads)
-template <class F>
-__device__ int lsap_compact(int n, F flag, int* out, int* s_wave, int* s_base) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
-  if (tid == 0) *s_base = 0;
-  __syncthreads();
-  for (int b0 = 0; b0 < n; b0 += blockDim.x) {
-    const int i = b0 + tid;
-    const bool f = i < n && flag(i);
-    const unsigned long long bal = __ballot(f);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(bal);
-    __syncthreads();
-    int off = *s_base;
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
-    if (f) out[off + before] = i;
-    __syncthreads();
-    if (tid == 0) { int t = 0; for (int w = 0; w < nw; ++w) t += s_wave[w]; *s_base += t; }
-    __syncthreads();
-  }
-  const int total = *s_base;
-  __syncthreads();          // everyone has read the count before a later call resets it (a fast thread 0 used to race ahead)
-  return total;
-}
-
 __global__ __launch_bounds__(LSAP_WG) void lsap_kernel(LsapArgs a) {
   // scipy's shortest-augmenting-path algorithm with its tie rules (remaining-list order, "prefer an unassigned column among equal
   // costs"), one workgroup.  Round 5: the phases of a row search were cut from five barriers to two per scan --
@@ -109,8 +85,8 @@ __global__ __launch_bounds__(LSAP_WG) void lsap_kernel(LsapArgs a) {
     for (int j = tid; j < a.nc; j += nt) collist[j] = j;
     n_eff = a.nr; c_eff = a.nc;
   } else {
-    n_eff = lsap_compact(a.nr, [&](int i) { return mask ? mask[i] != 0 : true; }, rowlist, s_wave, &s_base);
-    c_eff = lsap_compact(a.nc, [&](int j) { return cmask ? cmask[j] != 0 : true; }, collist, s_wave, &s_base);
+    n_eff = block_compact(a.nr, [&](int i) { return mask ? mask[i] != 0 : true; }, rowlist, s_wave, &s_base);
+    c_eff = block_compact(a.nc, [&](int j) { return cmask ? cmask[j] != 0 : true; }, collist, s_wave, &s_base);
   }
   const bool T = c_eff < n_eff;
   const int N = T ? c_eff : n_eff, M = T ? n_eff : c_eff;
@@ -230,7 +206,7 @@ __global__ __launch_bounds__(LSAP_WG) void lsap_kernel(LsapArgs a) {
   if (!T) {
     for (int i = tid; i < N; i += nt) { a.row_ind[i] = rowlist[i]; a.col_ind[i] = collist[col4row[i]]; }
   } else {      // problem rows are the original columns: emit pairs sorted by original row
-    const int cnt = lsap_compact(M, [&](int k) { return row4col[k] != -1; }, tmp, s_wave, &s_base);
+    const int cnt = block_compact(M, [&](int k) { return row4col[k] != -1; }, tmp, s_wave, &s_base);
     for (int q = tid; q < cnt; q += nt) { const int k = tmp[q]; a.row_ind[q] = rowlist[k]; a.col_ind[q] = collist[row4col[k]]; }
   }
   if (tid == 0) *a.n_match = N;

@@ -21,8 +21,8 @@
 #include <limits.h>
 #include <math.h>
 
+#include "block_util.hpp"        // block_exscan, block_sum
 #include "device_util.hpp"       // rounded
-#include "kernels_parse.hpp"     // parse_block_exscan
 
 namespace neat {
 
@@ -113,18 +113,6 @@ __device__ __forceinline__ int mesh_cell_faces(unsigned in, unsigned fin) {
   return n;
 }
 
-// fixed-shape sum over the workgroup (wave shuffles, then the waves in order)
-__device__ __forceinline__ int mesh_block_sum(int v, int* s_wave) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int tot = 0;
-  for (int w = 0; w < MESH_WG / 64; ++w) tot += s_wave[w];
-  __syncthreads();
-  return tot;
-}
-
 // pass 1: the edge bits of every node, and per tile the number of vertices and faces
 __global__ __launch_bounds__(MESH_WG) void mesh_count_kernel(MeshArgs a) {
   __shared__ int s_wave[MESH_WG / 64];
@@ -139,8 +127,8 @@ __global__ __launch_bounds__(MESH_WG) void mesh_count_kernel(MeshArgs a) {
     nv += __popc(em);
     nf += mesh_cell_faces(in, fin);
   }
-  nv = mesh_block_sum(nv, s_wave);
-  nf = mesh_block_sum(nf, s_wave);
+  nv = block_sum<MESH_WG>(nv, s_wave);
+  nf = block_sum<MESH_WG>(nf, s_wave);
   if (threadIdx.x == 0) { a.tile_v[blockIdx.x] = nv; a.tile_f[blockIdx.x] = nf; }
 }
 
@@ -148,12 +136,11 @@ __global__ __launch_bounds__(MESH_WG) void mesh_count_kernel(MeshArgs a) {
 __global__ __launch_bounds__(1024) void mesh_scan_kernel(int* __restrict__ tile_v, int* __restrict__ tile_f, int tiles, int* __restrict__ counts) {
   __shared__ int s_wave[16];
   long long cv = 0, cf = 0;
-  for (int t0 = 0; t0 < tiles; t0 += 1024) {
+  for (int t0 = 0; t0 < tiles; t0 += 1024) {      // both counts in one walk (block_carry_scan twice would wait for twice the loads)
     const int t = t0 + threadIdx.x;
     const int v = t < tiles ? tile_v[t] : 0, f = t < tiles ? tile_f[t] : 0;
     int tv, tf;
-    const int ev = parse_block_exscan(v, s_wave, &tv);
-    const int ef = parse_block_exscan(f, s_wave, &tf);
+    const int ev = block_exscan(v, s_wave, &tv), ef = block_exscan(f, s_wave, &tf);
     if (t < tiles) {      // past int32 the offsets are never used: the caller sees counts = -1 and does not emit
       tile_v[t] = (int)min(cv + ev, (long long)INT_MAX);
       tile_f[t] = (int)min(cf + ef, (long long)INT_MAX);
@@ -177,7 +164,7 @@ __global__ __launch_bounds__(MESH_WG) void mesh_verts_kernel(MeshArgs a) {
     const int node = (int)nl;
     const unsigned em = live ? a.emask[nl] : 0u;
     int tot;
-    const int base = carry + parse_block_exscan(__popc(em), s_wave, &tot);
+    const int base = carry + block_exscan(__popc(em), s_wave, &tot);
     carry += tot;
     if (!live) continue;
     a.vbase[node] = base;
@@ -220,7 +207,7 @@ __global__ __launch_bounds__(MESH_WG) void mesh_faces_kernel(MeshArgs a) {
     mesh_corner_bits(a, (int)nl, live, in, fin);
     const int cnt = mesh_cell_faces(in, fin);
     int tot;
-    int f = carry + parse_block_exscan(cnt, s_wave, &tot);
+    int f = carry + block_exscan(cnt, s_wave, &tot);
     carry += tot;
     if (cnt == 0) continue;
     for (int t = 0; t < 6; ++t) {

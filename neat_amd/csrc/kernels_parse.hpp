@@ -7,7 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "kernels_junction.hpp"     // lsap_compact (ordered compaction), project_point (VolSDFNetwork.project2D's arithmetic)
+#include "block_util.hpp"           // block_exscan, block_compact
+#include "kernels_junction.hpp"     // project_point (VolSDFNetwork.project2D's arithmetic)
 
 namespace neat {
 
@@ -92,25 +93,11 @@ __global__ __launch_bounds__(PARSE_WG) void parse_group_tile_kernel(const int* _
 
 // one workgroup of 1024: per label, the per-tile counts become absolute start positions of each tile's rows (exclusive prefix over
 // tiles + the label's start), cnt[l] = rows of label l, slot[l] = rank of l among the labels present (ascending) or -1; *count = L
-__device__ __forceinline__ int parse_block_exscan(int v, int* s_wave, int* total) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-  if (lane == 63) s_wave[wave] = x;
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < nw; ++w) { const int sw = s_wave[w]; off += w < wave ? sw : 0; tot += sw; }
-  __syncthreads();
-  *total = tot;
-  return off + x - v;
-}
-
 __global__ __launch_bounds__(1024) void parse_group_scan_kernel(int* __restrict__ run, int nt, int m, int* __restrict__ cnt,
                                                                 int* __restrict__ start, int* __restrict__ slot, int* __restrict__ count) {
   __shared__ int s_wave[16];
   int carry = 0, carry_present = 0;
-  for (int l0 = 0; l0 < m; l0 += 1024) {
+  for (int l0 = 0; l0 < m; l0 += 1024) {      // both scans in one walk over the labels (as mesh_scan_kernel)
     const int l = l0 + threadIdx.x;
     int c = 0;
     if (l < m) {
@@ -118,8 +105,8 @@ __global__ __launch_bounds__(1024) void parse_group_scan_kernel(int* __restrict_
       cnt[l] = c;
     }
     int tot, totp;
-    const int st = parse_block_exscan(c, s_wave, &tot);
-    const int sp = parse_block_exscan(c > 0 ? 1 : 0, s_wave, &totp);
+    const int st = block_exscan(c, s_wave, &tot);
+    const int sp = block_exscan(c > 0 ? 1 : 0, s_wave, &totp);
     if (l < m) {
       start[l] = carry + st;
       slot[l] = c > 0 ? carry_present + sp : -1;
@@ -238,7 +225,7 @@ __global__ __launch_bounds__(1024) void parse_select_kernel(const float* __restr
   const int tid = threadIdx.x;
   if (blockIdx.x == 0) {
     const int total = V * mcap;
-    const int N = lsap_compact(total, [&](int s) { return (s % mcap) < vcount[s / mcap] && vscores[s] < score_thr; }, idx_ws, s_wave, &s_base);
+    const int N = block_compact(total, [&](int s) { return (s % mcap) < vcount[s / mcap] && vscores[s] < score_thr; }, idx_ws, s_wave, &s_base);
     __syncthreads();
     for (int e = tid; e < 6 * N; e += blockDim.x) lines_out[e] = vlines[6 * (size_t)idx_ws[e / 6] + e % 6];
     if (tid == 0) counts_out[0] = N;
@@ -258,7 +245,7 @@ __global__ __launch_bounds__(1024) void parse_select_kernel(const float* __restr
     }
     for (int j = tid; j < J; j += blockDim.x) K += votes[j] > 1;
     int tot;
-    parse_block_exscan(K, s_wave, &tot);
+    block_exscan(K, s_wave, &tot);
     if (tid == 0) counts_out[1] = tot;
   }
 }
@@ -394,7 +381,7 @@ __global__ __launch_bounds__(1024) void parse_vis_count_kernel(const float* __re
     vis_count[e] = c;
   }
   __syncthreads();
-  const int n = lsap_compact(E, [&](int e) { return vis_count[e] >= ckview; }, idx_ws, s_wave, &s_base);
+  const int n = block_compact(E, [&](int e) { return vis_count[e] >= ckview; }, idx_ws, s_wave, &s_base);
   __syncthreads();
   for (int q = threadIdx.x; q < 6 * n; q += blockDim.x) checked[q] = lines[6 * (size_t)idx_ws[q / 6] + q % 6];
   if (threadIdx.x == 0) *n_checked = n;

@@ -8,76 +8,11 @@
 #include <math.h>
 #include <stddef.h>
 
-#include "kernels_parse.hpp"        // parse_d4, parse_block_exscan, PARSE_WG / PARSE_GT_CHUNK; lsap_compact and project_point behind it
+#include "block_util.hpp"           // block_carry_scan, block_compact
+#include "kernels_parse.hpp"        // parse_d4, PARSE_WG / PARSE_GT_CHUNK; project_point behind it
 
 namespace neat {
 
-constexpr int POST_MAX_GRID = 1024;       // snap: cell keys (ix G + iy) G + iz stay below 2^30
-constexpr int POST_MAX_VIEWS = 65535;     // fuse: the views are the y dimension of one launch
-
-// ---- host side: workspace layouts and bounds (plain C++; scripts/post_host_check.cpp runs them under the host sanitizers) -----------------
-inline size_t post_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// every count that a launch turns into a grid or an int index: lines, views, detections
-inline bool post_counts_ok(long long n, long long V, long long mtot) {
-  return n >= 0 && V >= 0 && mtot >= 0 && n <= 0x7fffffffLL / 6 && V <= POST_MAX_VIEWS && mtot <= 0x7fffffffLL / 8 &&
-         (V == 0 || n <= 0x7fffffffLL / V);
-}
-
-struct PostFuseWs { size_t label, present, rank, idx, total; };        // int [V n] | byte [mtot] | int [mtot] | int [n]
-inline bool post_fuse_layout(long long n, long long V, long long mtot, PostFuseWs* w) {
-  if (!post_counts_ok(n, V, mtot)) return false;
-  size_t o = 0;
-  w->label = o; o += post_al((size_t)n * (size_t)V * sizeof(int));
-  w->present = o; o += post_al((size_t)mtot);
-  w->rank = o; o += post_al((size_t)mtot * sizeof(int));
-  w->idx = o; o += post_al((size_t)n * sizeof(int));
-  w->total = o;
-  return true;
-}
-
-struct PostRefineWs { size_t label, idx, glines, gscores, gcount, group, total; };   // int [2 n] | int [n] | float [6 m] | float [m] | int | parse_group's
-inline bool post_refine_layout(long long n, long long mmax, size_t group_bytes, PostRefineWs* w) {
-  if (!post_counts_ok(n, 1, mmax)) return false;
-  size_t o = 0;
-  w->label = o; o += post_al(2 * (size_t)n * sizeof(int));
-  w->idx = o; o += post_al((size_t)n * sizeof(int));
-  w->glines = o; o += post_al(6 * (size_t)mmax * sizeof(float));
-  w->gscores = o; o += post_al((size_t)mmax * sizeof(float));
-  w->gcount = o; o += post_al(sizeof(int));
-  w->group = o; o += post_al(group_bytes);
-  w->total = o;
-  return true;
-}
-
-inline bool post_grid_ok(long long G) { return G >= 2 && G <= POST_MAX_GRID; }
-
-// snap, M = 2 n end points: box float [9] | counts int [2] (cells, peaks) | key, skey, head, flag, cnt, pidx, near int [M] each |
-// dist2 float [M] | idx int [n] | pkey, spkey 64-bit [n] each | the sort's temporary storage
-struct PostSnapWs { size_t box, counts, key, skey, head, flag, cnt, pidx, near, dist2, idx, pkey, spkey, sort, total; };
-inline bool post_snap_layout(long long n, long long G, size_t sort_bytes, PostSnapWs* w) {
-  if (!post_grid_ok(G) || !post_counts_ok(n, 1, 0)) return false;
-  const size_t M = 2 * (size_t)n, mi = post_al(M * sizeof(int));
-  size_t o = 0;
-  w->box = o; o += post_al(9 * sizeof(float));
-  w->counts = o; o += post_al(2 * sizeof(int));
-  w->key = o; o += mi;
-  w->skey = o; o += mi;
-  w->head = o; o += mi;
-  w->flag = o; o += mi;
-  w->cnt = o; o += mi;
-  w->pidx = o; o += mi;
-  w->near = o; o += mi;
-  w->dist2 = o; o += post_al(M * sizeof(float));
-  w->idx = o; o += post_al((size_t)n * sizeof(int));
-  w->pkey = o; o += post_al((size_t)n * sizeof(unsigned long long));
-  w->spkey = o; o += post_al((size_t)n * sizeof(unsigned long long));
-  w->sort = o; o += post_al(sort_bytes);
-  w->total = o;
-  return true;
-}
-
-#if defined(__HIPCC__)
 // ---- match (fusion.py :105-114, refinement.py :132-150): grid (line tiles, views), view = view0 + blockIdx.y.  The line's end points go
 // through project_point; the view's detections go through LDS in chunks (a broadcast read, as parse_match_kernel).  best = min over the
 // detections j of min(dis1_j, dis2_j) (dis2: the detection against the reversed line), lowest j on ties; a row with a NaN distance never
@@ -145,15 +80,7 @@ __global__ __launch_bounds__(1024) void post_rank_kernel(const unsigned char* __
                                                          int* __restrict__ rank) {
   __shared__ int s_wave[16];
   const int g0 = det_off[blockIdx.x], m = det_off[blockIdx.x + 1] - g0;
-  int carry = 0;
-  for (int l0 = 0; l0 < m; l0 += 1024) {
-    const int l = l0 + threadIdx.x;
-    const int f = l < m ? (present[g0 + l] != 0) : 0;
-    int tot;
-    const int ex = parse_block_exscan(f, s_wave, &tot);
-    if (l < m) rank[g0 + l] = carry + ex;
-    carry += tot;
-  }
+  block_carry_scan(m, [&](int l) { return present[g0 + l] != 0 ? 1 : 0; }, [&](int l, long long e) { rank[g0 + l] = (int)e; }, s_wave);
 }
 
 // one thread per line (:121-122, :131-133): the score sum in view order (the reference's order, so the fp32 sum is the reference's),
@@ -184,7 +111,7 @@ __global__ __launch_bounds__(PARSE_WG) void post_fuse_score_kernel(const int* __
 __global__ __launch_bounds__(1024) void post_keep_kernel(const float* __restrict__ lines, int n, const unsigned char* __restrict__ keep,
                                                          int* __restrict__ idx_ws, float* __restrict__ out, int* __restrict__ n_out) {
   __shared__ int s_wave[16], s_base;
-  const int k = lsap_compact(n, [&](int i) { return keep[i] != 0; }, idx_ws, s_wave, &s_base);
+  const int k = block_compact(n, [&](int i) { return keep[i] != 0; }, idx_ws, s_wave, &s_base);
   __syncthreads();
   for (int q = threadIdx.x; q < 6 * k; q += blockDim.x) out[q] = lines[6 * (size_t)idx_ws[q / 6] + q % 6];
   if (threadIdx.x == 0) *n_out = k;
@@ -198,7 +125,7 @@ __global__ __launch_bounds__(1024) void post_refine_assemble_kernel(const float*
                                                                     float* __restrict__ next, int* __restrict__ n_next) {
   __shared__ int s_wave[16], s_base;
   const int n = min(*n_cur, ncap);
-  const int U = lsap_compact(n, [&](int i) { return label[i] < 0 && label[(size_t)ncap + i] < 0; }, idx_ws, s_wave, &s_base);
+  const int U = block_compact(n, [&](int i) { return label[i] < 0 && label[(size_t)ncap + i] < 0; }, idx_ws, s_wave, &s_base);
   __syncthreads();
   const int L = min(*gcount, ncap - U);
   for (int q = threadIdx.x; q < 6 * U; q += blockDim.x) next[q] = cur[6 * (size_t)idx_ws[q / 6] + q % 6];
@@ -250,7 +177,7 @@ __global__ __launch_bounds__(PARSE_WG) void post_snap_key_kernel(const float* __
 // one workgroup over the sorted keys: head[u] = first position of the u-th occupied cell, *n_cells = occupied cells
 __global__ __launch_bounds__(1024) void post_snap_cells_kernel(const int* __restrict__ skey, int M, int* __restrict__ head, int* __restrict__ n_cells) {
   __shared__ int s_wave[16], s_base;
-  const int U = lsap_compact(M, [&](int i) { return i == 0 || skey[i] != skey[i - 1]; }, head, s_wave, &s_base);
+  const int U = block_compact(M, [&](int i) { return i == 0 || skey[i] != skey[i - 1]; }, head, s_wave, &s_base);
   if (threadIdx.x == 0) *n_cells = U;
 }
 
@@ -294,7 +221,7 @@ __global__ __launch_bounds__(1024) void post_snap_select_kernel(const int* __res
                                                                 float* __restrict__ junc, int* __restrict__ pcount, int* __restrict__ n_peaks) {
   __shared__ int s_wave[16], s_base;
   const int U = min(*n_cells, M);
-  const int P = lsap_compact(U, [&](int u) { return flag[u] != 0; }, pidx, s_wave, &s_base);
+  const int P = block_compact(U, [&](int u) { return flag[u] != 0; }, pidx, s_wave, &s_base);
   __syncthreads();
   for (int p = threadIdx.x; p < P; p += blockDim.x) {
     const int u = pidx[p], k = skey[head[u]];
@@ -341,7 +268,7 @@ __global__ __launch_bounds__(1024) void post_snap_edges_kernel(const int* __rest
                                                                const float* __restrict__ junc, int* __restrict__ idx_ws, int* __restrict__ edges,
                                                                float* __restrict__ lines_out, int* __restrict__ n_edges) {
   __shared__ int s_wave[16], s_base;
-  const int E = lsap_compact(n, [&](int i) { return post_snap_line_kept(near, dist2, max_snap, i); }, idx_ws, s_wave, &s_base);
+  const int E = block_compact(n, [&](int i) { return post_snap_line_kept(near, dist2, max_snap, i); }, idx_ws, s_wave, &s_base);
   __syncthreads();
   for (int q = threadIdx.x; q < 2 * E; q += blockDim.x) {
     const int j = near[2 * idx_ws[q >> 1] + (q & 1)];
@@ -371,7 +298,7 @@ __global__ __launch_bounds__(1024) void post_snap_unique_kernel(const unsigned l
                                                                 int* __restrict__ idx_ws, int* __restrict__ edges, float* __restrict__ lines_out,
                                                                 int* __restrict__ n_edges) {
   __shared__ int s_wave[16], s_base;
-  const int E = lsap_compact(n, [&](int i) { return spkey[i] != POST_NO_PAIR && (i == 0 || spkey[i] != spkey[i - 1]); }, idx_ws, s_wave, &s_base);
+  const int E = block_compact(n, [&](int i) { return spkey[i] != POST_NO_PAIR && (i == 0 || spkey[i] != spkey[i - 1]); }, idx_ws, s_wave, &s_base);
   __syncthreads();
   for (int q = threadIdx.x; q < 2 * E; q += blockDim.x) {
     const unsigned long long k = spkey[idx_ws[q >> 1]];
@@ -382,6 +309,5 @@ __global__ __launch_bounds__(1024) void post_snap_unique_kernel(const unsigned l
   }
   if (threadIdx.x == 0) *n_edges = E;
 }
-#endif  // __HIPCC__
 
 }  // namespace neat

@@ -35,13 +35,13 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "block_util.hpp"      // block_minmax
 #include "device_util.hpp"
 
 namespace neat {
 
 constexpr int RC_WG = 256;
 constexpr int RC_TOP_WG = 1024;
-constexpr int RC_MAX_FACES = 1 << 24;
 constexpr int RC_TRI_STRIDE = 10;            // doubles per sorted triangle: 9 coordinates, then the original face index in the low 4 bytes
 constexpr unsigned long long RC_KEY_LAST = 0x7fffffffffffffffull;
 
@@ -80,9 +80,9 @@ __device__ __forceinline__ void rc_centroid(const double* __restrict__ v, double
 // ---- prep: the index check (before any vertex is read), then each workgroup's box of the centroids of its valid triangles
 __global__ __launch_bounds__(RC_WG) void raycast_prep_kernel(const double* __restrict__ verts, int nv, const int* __restrict__ faces, int nf,
                                                             int* __restrict__ status, double* __restrict__ partial) {
-  __shared__ double s_box[RC_WG][6];
+  __shared__ double sh[24];
   const int g = blockIdx.x * RC_WG + threadIdx.x;
-  double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   if (g < nf) {
     if (!rc_indices_ok(faces, g, nv)) {
       status[0] = 1;                      // every writer stores the same value
@@ -91,53 +91,33 @@ __global__ __launch_bounds__(RC_WG) void raycast_prep_kernel(const double* __res
       if (rc_triangle(verts, faces, g, v)) {
         rc_centroid(v, c);
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { b[a] = c[a]; b[3 + a] = c[a]; }
+        for (int a = 0; a < 3; ++a) { lo[a] = c[a]; hi[a] = c[a]; }
       }
     }
   }
-#pragma unroll
-  for (int a = 0; a < 6; ++a) s_box[threadIdx.x][a] = b[a];
-  for (int w = RC_WG / 2; w >= 1; w >>= 1) {
-    __syncthreads();
-    if ((int)threadIdx.x < w) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        s_box[threadIdx.x][a] = fmin(s_box[threadIdx.x][a], s_box[threadIdx.x + w][a]);
-        s_box[threadIdx.x][3 + a] = fmax(s_box[threadIdx.x][3 + a], s_box[threadIdx.x + w][3 + a]);
-      }
-    }
-  }
+  block_minmax<RC_WG>(lo, hi, sh);
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int a = 0; a < 6; ++a) partial[6 * (size_t)blockIdx.x + a] = s_box[0][a];
+    for (int a = 0; a < 3; ++a) { partial[6 * (size_t)blockIdx.x + a] = lo[a]; partial[6 * (size_t)blockIdx.x + 3 + a] = hi[a]; }
   }
 }
 
 // ---- one workgroup: the partial boxes -> the box of all centroids
 __global__ __launch_bounds__(RC_WG) void raycast_scene_box_kernel(const double* __restrict__ partial, int n, double* __restrict__ box) {
-  __shared__ double s_box[RC_WG][6];
-  double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  __shared__ double sh[24];
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int i = threadIdx.x; i < n; i += RC_WG) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      b[a] = fmin(b[a], partial[6 * (size_t)i + a]);
-      b[3 + a] = fmax(b[3 + a], partial[6 * (size_t)i + 3 + a]);
+      lo[a] = fmin(lo[a], partial[6 * (size_t)i + a]);
+      hi[a] = fmax(hi[a], partial[6 * (size_t)i + 3 + a]);
     }
   }
+  block_minmax<RC_WG>(lo, hi, sh);
+  if (threadIdx.x == 0) {
 #pragma unroll
-  for (int a = 0; a < 6; ++a) s_box[threadIdx.x][a] = b[a];
-  for (int w = RC_WG / 2; w >= 1; w >>= 1) {
-    __syncthreads();
-    if ((int)threadIdx.x < w) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        s_box[threadIdx.x][a] = fmin(s_box[threadIdx.x][a], s_box[threadIdx.x + w][a]);
-        s_box[threadIdx.x][3 + a] = fmax(s_box[threadIdx.x][3 + a], s_box[threadIdx.x + w][3 + a]);
-      }
-    }
+    for (int a = 0; a < 3; ++a) { box[a] = lo[a]; box[3 + a] = hi[a]; }
   }
-  __syncthreads();
-  if (threadIdx.x < 6) box[threadIdx.x] = s_box[0][threadIdx.x];
 }
 
 __device__ __forceinline__ unsigned long long rc_spread21(unsigned long long x) {      // bit i -> bit 3 i

@@ -24,26 +24,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "kernels_parse.hpp"     // parse_block_exscan
+#include "block_util.hpp"     // block_exscan, block_carry_scan
+#include "ws_layout.hpp"      // TraceWs
 
 namespace neat {
 
 constexpr int TRACE_WG = 256;
 enum : unsigned char { TRACE_MISS = 0, TRACE_HIT = 1, TRACE_INSIDE = 2, TRACE_UNCONVERGED = 3,      // what neat_trace_finish reports
                        TRACE_START = 4, TRACE_MARCH = 5, TRACE_REFINE = 6 };                         // rays that still need a query
-
-struct TraceWs {
-  float *t;                 // [R] the point of the pending query; for a finished HIT / INSIDE ray its depth
-  float *ta, *fa;           // [R] march: the previous point and value; refine: the bracket's end with f >= 0
-  float *tb, *fb;           // [R] refine: the bracket's end with f < 0
-  float *t1;                // [R] end of the clipped chord
-  int *steps, *march, *refine;      // [R] queries made, advances made, refinement rounds made
-  unsigned char *phase;     // [R]
-  unsigned char *side;      // [R] refine: the end the last query replaced (1 = a, 2 = b, 0 = none yet)
-  unsigned char *flag;      // [R] by list position: the entry stays active
-  int *ids[2];              // [R] each: the active lists, ping-pong
-  int *tile;                // [ceil(R / TRACE_WG)] active entries per workgroup, then their exclusive offsets
-};
 
 __device__ __forceinline__ void trace_point(const float* __restrict__ o, const float* __restrict__ d, int r, float t, float* __restrict__ out) {
   out[0] = __fmaf_rn(t, d[3 * (size_t)r], o[3 * (size_t)r]);
@@ -55,7 +43,7 @@ __device__ __forceinline__ void trace_point(const float* __restrict__ o, const f
 __device__ __forceinline__ void trace_tile_count(const TraceWs& w, int alive) {
   __shared__ int s_wave[TRACE_WG / 64];
   int tot;
-  parse_block_exscan(alive, s_wave, &tot);
+  block_exscan(alive, s_wave, &tot);
   if (threadIdx.x == 0) w.tile[blockIdx.x] = tot;
 }
 
@@ -89,15 +77,7 @@ __global__ __launch_bounds__(TRACE_WG) void trace_init_kernel(TraceWs w, const f
 // ---- one workgroup of 1024 walks all the tile counts (the host caps R at 2^24 rays = 65536 tiles = 64 rounds): they become exclusive offsets, in order; ctl[0] = the active count, ctl[1] += it (reset: = it)
 __global__ __launch_bounds__(1024) void trace_scan_kernel(int* __restrict__ tile, int tiles, long long* __restrict__ ctl, int reset) {
   __shared__ int s_wave[16];
-  long long carry = 0;
-  for (int t0 = 0; t0 < tiles; t0 += 1024) {
-    const int t = t0 + threadIdx.x;
-    const int v = t < tiles ? tile[t] : 0;
-    int tot;
-    const int e = parse_block_exscan(v, s_wave, &tot);
-    if (t < tiles) tile[t] = (int)(carry + e);
-    carry += tot;
-  }
+  const long long carry = block_carry_scan(tiles, [&](int t) { return tile[t]; }, [&](int t, long long e) { tile[t] = (int)e; }, s_wave);
   if (threadIdx.x == 0) { ctl[0] = carry; ctl[1] = (reset ? 0 : ctl[1]) + carry; }
 }
 
@@ -109,7 +89,7 @@ __global__ __launch_bounds__(TRACE_WG) void trace_emit_kernel(TraceWs w, const i
   const int i = blockIdx.x * TRACE_WG + threadIdx.x;
   const int alive = i < n ? (int)w.flag[i] : 0;
   int tot;
-  const int pos = w.tile[blockIdx.x] + parse_block_exscan(alive, s_wave, &tot);
+  const int pos = w.tile[blockIdx.x] + block_exscan(alive, s_wave, &tot);
   if (!alive) return;
   const int r = ids_in ? ids_in[i] : i;
   if (r < 0 || r >= R || pos < 0 || pos >= R) return;      // never true for lists these kernels wrote

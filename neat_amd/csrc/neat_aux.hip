@@ -15,6 +15,7 @@
 #include "kernels_trace.hpp"
 #include "kernels_post.hpp"
 #include "kernels_raycast.hpp"
+#include "ws_layout.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -466,26 +467,24 @@ int neat_line_losses(const float* pred_px, const float* pred_calib, const float*
   return (int)hipGetLastError();
 }
 
-size_t neat_lsap_ws_bytes(int nr, int nc) {
-  const size_t mx = (size_t)(nr > nc ? nr : nc), mn = (size_t)(nr < nc ? nr : nc);
-  return (mn + 2 * mx) * sizeof(double) + ((size_t)nr + (size_t)nc + 5 * mx + 2 * mn) * sizeof(int);
-}
+size_t neat_lsap_ws_bytes(int nr, int nc) { LsapWs w; lsap_layout(nullptr, nr, nc, &w); return w.total; }
 
 int neat_lsap(const float* cost, int nr, int nc, const unsigned char* row_mask, const unsigned char* col_mask, long long* row_ind,
               long long* col_ind, int* n_match, void* ws, void* stream) {
   if (nr < 0 || nc < 0 || !n_match) return -1;
   if (nr == 0 || nc == 0) return (int)hipMemsetAsync(n_match, 0, sizeof(int), (hipStream_t)stream);
   if (!cost || !row_ind || !col_ind || !ws) return -1;
-  const size_t mx = (size_t)(nr > nc ? nr : nc), mn = (size_t)(nr < nc ? nr : nc);
-  LsapArgs a{cost, nr, nc, row_mask, row_ind, col_ind, n_match, (double*)ws, (int*)((double*)ws + mn + 2 * mx)};
+  LsapWs w;
+  lsap_layout(ws, nr, nc, &w);
+  LsapArgs a{cost, nr, nc, row_mask, row_ind, col_ind, n_match, w.d, w.i};
   a.col_mask = col_mask;
-  const size_t dbytes = (mn + 2 * mx) * sizeof(double), ibytes = ((size_t)nr + (size_t)nc + 5 * mx + 2 * mn) * sizeof(int);
+  const size_t mx = (size_t)(nr > nc ? nr : nc), dbytes = ws_offset(ws, w.i);
   size_t lds = 0;
   constexpr size_t LSAP_LDS_MAX = 156 * 1024;
   a.cost_lds_off = -1;
-  if (dbytes + ibytes <= LSAP_LDS_MAX) {
+  if (w.total <= LSAP_LDS_MAX) {
     NEAT_CHECK(lds_limit<&lsap_kernel>((int)LSAP_LDS_MAX));
-    a.use_lds = 1; a.lds_int_off = (int)dbytes; lds = (dbytes + ibytes + 15) & ~(size_t)15;
+    a.use_lds = 1; a.lds_int_off = (int)dbytes; lds = (w.total + 15) & ~(size_t)15;
     const size_t cbytes = (size_t)nr * nc * sizeof(float);
     if (lds + cbytes <= LSAP_LDS_MAX) { a.cost_lds_off = (int)lds; lds += cbytes; }      // the cost matrix too (8 x 2048 fits)
   }
@@ -496,20 +495,21 @@ int neat_lsap(const float* cost, int nr, int nc, const unsigned char* row_mask, 
   return (int)hipGetLastError();
 }
 
-size_t neat_dbscan_ws_bytes(int n) { return (size_t)n * 2 * sizeof(int); }
+size_t neat_dbscan_ws_bytes(int n) { DbscanWs w; dbscan_layout(nullptr, n, &w); return w.total; }
 
 int neat_dbscan_means(const float* points, int n, double eps, float* centres, unsigned char* valid, int* count, void* ws, void* stream) {
   if (n <= 0 || n > DBSCAN_MAXN || !points || !centres || !valid || !count || !ws || !(eps > 0.0)) return -1;
-  int* parent = (int*)ws; int* has_nb = parent + n;
-  hipLaunchKernelGGL(dbscan_init_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, parent, has_nb, n);
-  hipLaunchKernelGGL(dbscan_union_kernel, dim3(n), dim3(128), 0, (hipStream_t)stream, points, n, eps * eps, parent, has_nb);
+  DbscanWs w;
+  dbscan_layout(ws, n, &w);
+  hipLaunchKernelGGL(dbscan_init_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w.parent, w.has_nb, n);
+  hipLaunchKernelGGL(dbscan_union_kernel, dim3(n), dim3(128), 0, (hipStream_t)stream, points, n, eps * eps, w.parent, w.has_nb);
   // mode 2 (18 n bytes of dynamic LDS fit next to the 32 KB of labels): O(n) fixed-point sums; else one wavefront per cluster over all
   // points, read from LDS (mode 1: 12 n bytes fit) or from global memory (mode 0)
   const size_t acc_bytes = (size_t)(n / 2) * 28 + (size_t)n * 4, pbytes = (size_t)n * 12;
   const int mode = acc_bytes <= 96 * 1024 ? 2 : (pbytes <= 96 * 1024 ? 1 : 0);
   if (mode) NEAT_CHECK(lds_limit<&dbscan_finish_kernel>(96 * 1024));
   hipLaunchKernelGGL(dbscan_finish_kernel, dim3(1), dim3(1024), mode == 2 ? acc_bytes : (mode == 1 ? pbytes : 0), (hipStream_t)stream, points, n,
-                     parent, has_nb, centres, valid, count, mode);
+                     w.parent, w.has_nb, centres, valid, count, mode);
   return (int)hipGetLastError();
 }
 
@@ -520,9 +520,6 @@ int neat_volume_weights(const float* z, const float* sdf, int R, int S, const fl
 }
 
 // ---- ABI v15: wireframe parsing (kernels_parse.hpp) -----------------------------------------------------------------------------
-static inline size_t parse_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline int parse_tiles(int n) { return (2 * n + PARSE_TILE - 1) / PARSE_TILE; }
-
 int neat_parse_match(const float* lines2d, int n, const float* gt, int m, int gt_stride, float threshold, int* label, float* mindis,
                      void* stream) {
   if (n < 0 || m < 0 || (m > 0 && (!gt || gt_stride < 4))) return -1;
@@ -533,106 +530,78 @@ int neat_parse_match(const float* lines2d, int n, const float* gt, int m, int gt
   return (int)hipGetLastError();
 }
 
-size_t neat_parse_group_ws_bytes(int n, int m) {
-  if (n < 0 || m < 0) return 0;
-  const size_t nt = (size_t)parse_tiles(n);
-  return parse_al((nt * m + 3 * (size_t)m) * sizeof(int)) + parse_al(2 * (size_t)n * sizeof(int));
-}
+size_t neat_parse_group_ws_bytes(int n, int m) { ParseGroupWs w; return parse_group_layout(nullptr, n, m, PARSE_TILE, &w) ? w.total : 0; }
 
 int neat_parse_group(const int* label, const float* lines3d, const float* l3d, int n, int m, float* lines, float* scores, int* count,
                      void* ws, void* stream) {
-  if (n < 0 || m < 0 || !count) return -1;
+  ParseGroupWs w;
+  if (!parse_group_layout(ws, n, m, PARSE_TILE, &w) || !count) return -1;
   hipStream_t st = (hipStream_t)stream;
   if (n == 0 || m == 0) return (int)hipMemsetAsync(count, 0, sizeof(int), st);
   if (!label || !lines3d || !l3d || !lines || !scores || !ws) return -1;
-  const int nt = parse_tiles(n);
-  int* run = (int*)ws;
-  int* cnt = run + (size_t)nt * m;
-  int* start = cnt + m;
-  int* slot = start + m;
-  int* order = (int*)((char*)ws + parse_al(((size_t)nt * m + 3 * (size_t)m) * sizeof(int)));
-  NEAT_CHECK(hipMemsetAsync(run, 0, (size_t)nt * m * sizeof(int), st));
-  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 0);
-  hipLaunchKernelGGL(parse_group_scan_kernel, dim3(1), dim3(1024), 0, st, run, nt, m, cnt, start, slot, count);
-  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(nt), dim3(PARSE_WG), 0, st, label, 2 * n, m, run, order, 1);
-  hipLaunchKernelGGL(parse_group_reduce_kernel, dim3(m), dim3(PARSE_WG), 0, st, order, cnt, start, slot, lines3d, l3d, n, lines, scores);
+  NEAT_CHECK(hipMemsetAsync(w.run, 0, (size_t)w.tiles * m * sizeof(int), st));
+  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(w.tiles), dim3(PARSE_WG), 0, st, label, 2 * n, m, w.run, w.order, 0);
+  hipLaunchKernelGGL(parse_group_scan_kernel, dim3(1), dim3(1024), 0, st, w.run, w.tiles, m, w.cnt, w.start, w.slot, count);
+  hipLaunchKernelGGL(parse_group_tile_kernel, dim3(w.tiles), dim3(PARSE_WG), 0, st, label, 2 * n, m, w.run, w.order, 1);
+  hipLaunchKernelGGL(parse_group_reduce_kernel, dim3(m), dim3(PARSE_WG), 0, st, w.order, w.cnt, w.start, w.slot, lines3d, l3d, n, lines, scores);
   return (int)hipGetLastError();
 }
 
-size_t neat_parse_vote_ws_bytes(int J, int mcap) {
-  if (J <= 0 || mcap <= 0) return 0;
-  const size_t nc = 2 * (size_t)mcap, k = std::min((size_t)J, nc);
-  return parse_al((size_t)J * nc * sizeof(float)) + parse_al(nc) + 2 * parse_al(k * sizeof(long long)) + parse_al(sizeof(int)) +
-         parse_al(neat_lsap_ws_bytes(J, (int)nc));
-}
+size_t neat_parse_vote_ws_bytes(int J, int mcap) { ParseVoteWs w; return parse_vote_layout(nullptr, J, mcap, &w) ? w.total : 0; }
 
 int neat_parse_vote(const float* junctions, int J, const float* lines, const int* count, int mcap, float threshold, int view, int* votes,
                     int* first, void* ws, void* stream) {
   if (J < 0 || mcap < 0 || view < 0) return -1;
   if (J == 0 || mcap == 0) return 0;
-  if (!junctions || !lines || !count || !votes || !first || !ws) return -1;
+  ParseVoteWs w;
+  if (!junctions || !lines || !count || !votes || !first || !ws || !parse_vote_layout(ws, J, mcap, &w)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const int nc = 2 * mcap, k = std::min(J, nc);
-  char* p = (char*)ws;
-  float* cost = (float*)p; p += parse_al((size_t)J * nc * sizeof(float));
-  unsigned char* cmask = (unsigned char*)p; p += parse_al(nc);
-  long long* rows = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
-  long long* cols = (long long*)p; p += parse_al((size_t)k * sizeof(long long));
-  int* n_match = (int*)p; p += parse_al(sizeof(int));
-  const size_t total = (size_t)J * nc;
-  hipLaunchKernelGGL(parse_vote_cost_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, junctions, J, lines, count, nc, cost, cmask);
+  const size_t total = (size_t)J * w.nc;
+  hipLaunchKernelGGL(parse_vote_cost_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, junctions, J, lines, count, w.nc, w.cost, w.cmask);
   NEAT_CHECK(hipGetLastError());
-  const int e = neat_lsap(cost, J, nc, nullptr, cmask, rows, cols, n_match, p, stream);
+  const int e = neat_lsap(w.cost, J, w.nc, nullptr, w.cmask, w.rows, w.cols, w.n_match, w.lsap, stream);
   if (e != 0) return e;
-  hipLaunchKernelGGL(parse_vote_apply_kernel, grid1(k), dim3(256), 0, st, rows, cols, n_match, k, cost, nc, threshold, view, votes, first);
+  hipLaunchKernelGGL(parse_vote_apply_kernel, grid1(w.k), dim3(256), 0, st, w.rows, w.cols, w.n_match, w.k, w.cost, w.nc, threshold, view, votes, first);
   return (int)hipGetLastError();
 }
 
-size_t neat_parse_graph_ws_bytes(int V, int mcap, int J) {
-  if (V < 0 || mcap < 0 || J < 0) return 0;
-  return parse_al((size_t)V * mcap * sizeof(int)) + parse_al((size_t)J * sizeof(int));
-}
+size_t neat_parse_graph_ws_bytes(int V, int mcap, int J) { ParseGraphWs w; return parse_graph_layout(nullptr, V, mcap, J, &w) ? w.total : 0; }
 
 int neat_parse_graph(const float* vlines, const float* vscores, const int* vcount, int V, int mcap, float score_threshold,
                      const float* junctions, const int* votes, const int* first, int J, float* lines_out, float* junc_out,
                      unsigned char* graph, int* pairs, float* wfi, int ecap, int* counts, void* ws, void* stream) {
-  if (V < 0 || mcap < 0 || J < 0 || ecap < 0 || !counts) return -1;
+  ParseGraphWs w;
+  if (!parse_graph_layout(ws, V, mcap, J, &w) || ecap < 0 || !counts) return -1;
   hipStream_t st = (hipStream_t)stream;
   if ((V > 0 && mcap > 0 && (!vlines || !vscores || !vcount || !lines_out || !ws)) ||
       (J > 0 && (!junctions || !votes || !first || !junc_out || !graph || !ws)) || (ecap > 0 && (!pairs || !wfi))) return -1;
   NEAT_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(int), st));
   const int ncap = V * mcap;
   if (ncap == 0 && J == 0) return 0;
-  int* idx = (int*)ws;
-  int* rowcnt = (int*)((char*)ws + parse_al((size_t)V * mcap * sizeof(int)));
   hipLaunchKernelGGL(parse_select_kernel, dim3(2), dim3(1024), 0, st, vlines, vscores, vcount, V, mcap, score_threshold, junctions, votes, first,
-                     J, lines_out, junc_out, idx, counts);
+                     J, lines_out, junc_out, w.idx, counts);
   if (J == 0 || ncap == 0) return (int)hipGetLastError();
   NEAT_CHECK(hipMemsetAsync(graph, 0, (size_t)J * J, st));
   hipLaunchKernelGGL(parse_graph_mark_kernel, grid1(ncap, PARSE_WG), dim3(PARSE_WG), 0, st, lines_out, junc_out, counts, ncap, J, graph);
-  hipLaunchKernelGGL(parse_edge_count_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt);
-  hipLaunchKernelGGL(parse_edge_write_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, rowcnt, J, junc_out, ecap, pairs, wfi);
+  hipLaunchKernelGGL(parse_edge_count_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, w.rowcnt);
+  hipLaunchKernelGGL(parse_edge_write_kernel, dim3(J), dim3(64), 0, st, graph, counts, J, w.rowcnt, J, junc_out, ecap, pairs, wfi);
   return (int)hipGetLastError();
 }
 
-size_t neat_parse_visibility_ws_bytes(int ecap, int V) {
-  if (ecap < 0 || V < 0) return 0;
-  return parse_al((size_t)V * ecap) + parse_al((size_t)ecap * sizeof(int));
-}
+size_t neat_parse_visibility_ws_bytes(int ecap, int V) { ParseVisWs w; return parse_vis_layout(nullptr, ecap, V, &w) ? w.total : 0; }
 
 int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, const float* gt, int gt_stride, const int* gt_off,
                           const float* K3, const float* w2c, int V, float ckdist, int ckview, int* vis_count, float* checked,
                           int* n_checked, void* ws, void* stream) {
-  if (ecap < 0 || V < 0 || !n_checked) return -1;
+  ParseVisWs w;
+  if (!parse_vis_layout(ws, ecap, V, &w) || !n_checked) return -1;
   hipStream_t st = (hipStream_t)stream;
   if (ecap == 0) return (int)hipMemsetAsync(n_checked, 0, sizeof(int), st);
   if (!lines || !vis_count || !checked || !ws || (V > 0 && (!gt_off || !K3 || !w2c || gt_stride < 4))) return -1;
-  unsigned char* vis = (unsigned char*)ws;
-  int* idx = (int*)((char*)ws + parse_al((size_t)V * ecap));
   if (V > 0)
     hipLaunchKernelGGL(parse_vis_kernel, dim3((ecap + PARSE_WG - 1) / PARSE_WG, V), dim3(PARSE_WG), 0, st, lines, n_lines, ecap, gt, gt_stride,
-                       gt_off, K3, w2c, ckdist, vis);
-  hipLaunchKernelGGL(parse_vis_count_kernel, dim3(1), dim3(1024), 0, st, lines, n_lines, ecap, V, vis, ckview, vis_count, idx, checked, n_checked);
+                       gt_off, K3, w2c, ckdist, w.vis);
+  hipLaunchKernelGGL(parse_vis_count_kernel, dim3(1), dim3(1024), 0, st, lines, n_lines, ecap, V, w.vis, ckview, vis_count, w.idx, checked, n_checked);
   return (int)hipGetLastError();
 }
 
@@ -645,15 +614,6 @@ static bool mesh_axes(const int* n, const double* b0, const double* b1, MeshAxes
   }
   return true;
 }
-static inline long long mesh_nodes(int nx, int ny, int nz) {      // 0: not a grid this code indexes (an axis under 2 nodes, or 2^31 nodes and more)
-  if (nx < 2 || ny < 2 || nz < 2) return 0;
-  const long long n = (long long)nx * ny;
-  if (n > INT_MAX) return 0;
-  const long long N = n * nz;
-  return N > INT_MAX ? 0 : N;
-}
-static inline size_t mesh_tiles(long long nodes) { return (size_t)((nodes + MESH_TILE - 1) / MESH_TILE); }
-
 int neat_grid_points(float* x_fm, int ldp, long long first_node, int count, const int* n, const double* b0, const double* b1, void* stream) {
   MeshAxes g;
   if (!x_fm || count < 0 || ldp < count || first_node < 0 || !mesh_axes(n, b0, b1, &g)) return -1;
@@ -663,29 +623,22 @@ int neat_grid_points(float* x_fm, int ldp, long long first_node, int count, cons
   return (int)hipGetLastError();
 }
 
-size_t neat_mesh_ws_bytes(int nx, int ny, int nz) {
-  const long long N = mesh_nodes(nx, ny, nz);
-  if (N == 0) return 0;
-  return parse_al((size_t)N) + parse_al((size_t)N * sizeof(int)) + 2 * parse_al(mesh_tiles(N) * sizeof(int));
-}
+size_t neat_mesh_ws_bytes(int nx, int ny, int nz) { MeshWs w; return mesh_layout(nullptr, nx, ny, nz, MESH_TILE, &w) ? w.total : 0; }
 
-static MeshArgs mesh_args(const float* grid, int nx, int ny, int nz, long long N, float level, void* ws) {
-  MeshArgs a{};
-  a.grid = grid; a.nx = nx; a.ny = ny; a.nz = nz; a.nodes = (int)N; a.level = level;
-  char* p = (char*)ws;
-  a.emask = (unsigned char*)p; p += parse_al((size_t)N);
-  a.vbase = (int*)p; p += parse_al((size_t)N * sizeof(int));
-  a.tile_v = (int*)p; p += parse_al(mesh_tiles(N) * sizeof(int));
-  a.tile_f = (int*)p;
-  return a;
+static int mesh_args(const float* grid, int nx, int ny, int nz, float level, void* ws, MeshArgs* a) {      // -> tiles; 0: refused
+  MeshWs w;
+  if (!mesh_layout(ws, nx, ny, nz, MESH_TILE, &w) || !grid || !ws || level != level) return 0;
+  *a = MeshArgs{};
+  a->grid = grid; a->nx = nx; a->ny = ny; a->nz = nz; a->nodes = w.nodes; a->level = level;
+  a->emask = w.emask; a->vbase = w.vbase; a->tile_v = w.tile_v; a->tile_f = w.tile_f;
+  return w.tiles;
 }
 
 int neat_mesh_count(const float* grid, int nx, int ny, int nz, float level, void* ws, int* counts, void* stream) {
-  const long long N = mesh_nodes(nx, ny, nz);
-  if (N == 0 || !grid || !ws || !counts || level != level) return -1;
-  MeshArgs a = mesh_args(grid, nx, ny, nz, N, level, ws);
+  MeshArgs a;
+  const int tiles = mesh_args(grid, nx, ny, nz, level, ws, &a);
+  if (!tiles || !counts) return -1;
   a.counts = counts;
-  const int tiles = (int)mesh_tiles(N);
   hipLaunchKernelGGL(mesh_count_kernel, dim3(tiles), dim3(MESH_WG), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a.tile_v, a.tile_f, tiles, counts);
   return (int)hipGetLastError();
@@ -693,14 +646,11 @@ int neat_mesh_count(const float* grid, int nx, int ny, int nz, float level, void
 
 int neat_mesh_emit(const float* grid, int nx, int ny, int nz, const double* b0, const double* b1, float level, void* ws, float* verts, int nv,
                    int* faces, int nf, void* stream) {
-  const long long N = mesh_nodes(nx, ny, nz);
-  const int n[3] = {nx, ny, nz};
-  if (N == 0 || !grid || !ws || nv < 0 || nf < 0 || (nv > 0 && !verts) || (nf > 0 && !faces) || level != level) return -1;
-  MeshArgs a = mesh_args(grid, nx, ny, nz, N, level, ws);
-  if (!mesh_axes(n, b0, b1, &a.ax)) return -1;
+  MeshArgs a;
+  const int tiles = mesh_args(grid, nx, ny, nz, level, ws, &a), n[3] = {nx, ny, nz};
+  if (!tiles || nv < 0 || nf < 0 || (nv > 0 && !verts) || (nf > 0 && !faces) || !mesh_axes(n, b0, b1, &a.ax)) return -1;
   if (nv == 0) return 0;                 // no vertex, hence no face
   a.verts = verts; a.nv = nv; a.faces = faces; a.nf = nf;
-  const int tiles = (int)mesh_tiles(N);
   hipLaunchKernelGGL(mesh_verts_kernel, dim3(tiles), dim3(MESH_WG), 0, (hipStream_t)stream, a);
   if (nf > 0) hipLaunchKernelGGL(mesh_faces_kernel, dim3(tiles), dim3(MESH_WG), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
@@ -733,35 +683,24 @@ int neat_grid_points_affine(float* x_fm, int ldp, long long first_node, int coun
   return (int)hipGetLastError();
 }
 
-// the levels of the moments' tree above the leaves, each [MOMENTS_N][m]
-size_t neat_mesh_moments_ws_bytes(int nf) {
-  if (nf < 0) return 0;
-  size_t doubles = 0;
-  for (long long m = ((long long)nf + MOMENTS_TILE - 1) / MOMENTS_TILE; m > 1; m = (m + EMESH_WG - 1) / EMESH_WG) doubles += (size_t)MOMENTS_N * (size_t)m;
-  return parse_al(doubles * sizeof(double) + sizeof(double));
-}
+size_t neat_mesh_moments_ws_bytes(int nf) { SumTreeWs t; return sum_tree_layout(nullptr, nf, MOMENTS_TILE, EMESH_WG, MOMENTS_N, &t) ? t.total : 0; }
 
 int neat_mesh_moments(const float* verts, int nv, const int* faces, int nf, const double* origin, void* ws, double* out, int* flag, void* stream) {
-  if (nv < 0 || nf < 0 || !out || !flag || !finite_all(origin, 3) || (nf > 0 && (!faces || !verts || nv == 0))) return -1;
+  SumTreeWs t;
+  if (nv < 0 || !sum_tree_layout(ws, nf, MOMENTS_TILE, EMESH_WG, MOMENTS_N, &t) || !out || !flag || !finite_all(origin, 3) ||
+      (nf > 0 && (!faces || !verts || nv == 0))) return -1;
   hipStream_t st = (hipStream_t)stream;
   if (nf == 0) {
     NEAT_CHECK(hipMemsetAsync(out, 0, (MOMENTS_N - 1) * sizeof(double), st));
     return (int)hipMemsetAsync(flag, 0, sizeof(int), st);
   }
-  long long m = ((long long)nf + MOMENTS_TILE - 1) / MOMENTS_TILE;
-  if (m > 1 && (!ws || ((uintptr_t)ws & 7))) return -1;
+  if (t.levels > 0 && (!ws || ((uintptr_t)ws & 7))) return -1;
   Origin3 o;
   for (int i = 0; i < 3; ++i) o.o[i] = origin[i];
-  double* level = (double*)ws;
-  hipLaunchKernelGGL(mesh_moments_kernel, dim3((unsigned)m), dim3(EMESH_WG), 0, st, verts, nv, faces, nf, o, level, m, m == 1, out, flag);
-  while (m > 1) {
-    const long long up = (m + EMESH_WG - 1) / EMESH_WG;
-    double* next = level + (size_t)MOMENTS_N * (size_t)m;
-    hipLaunchKernelGGL(mesh_moments_level_kernel, dim3((unsigned)up, MOMENTS_N), dim3(EMESH_WG), 0, st, (const double*)level, m, next, up, up == 1, out,
-                       flag);
-    level = next;
-    m = up;
-  }
+  hipLaunchKernelGGL(mesh_moments_kernel, dim3((unsigned)t.m[0]), dim3(EMESH_WG), 0, st, verts, nv, faces, nf, o, t.level[0], t.m[0], t.levels == 0, out, flag);
+  for (int k = 0; k < t.levels; ++k)
+    hipLaunchKernelGGL(mesh_moments_level_kernel, dim3((unsigned)t.m[k + 1], MOMENTS_N), dim3(EMESH_WG), 0, st, (const double*)t.level[k], t.m[k],
+                       t.level[k + 1], t.m[k + 1], k + 1 == t.levels, out, flag);
   return (int)hipGetLastError();
 }
 
@@ -779,14 +718,16 @@ int neat_affine_rows3(float* v, int n, const double* A, void* stream) {
   return (int)hipGetLastError();
 }
 
-size_t neat_affine_bounds3_ws_bytes(void) { return (size_t)BOUNDS_BLOCKS * 6 * sizeof(double); }
+size_t neat_affine_bounds3_ws_bytes(void) { double* p; return partials_layout(nullptr, BOUNDS_BLOCKS, 6, &p); }
 
 int neat_affine_bounds3(const float* v, int n, const double* A, void* ws, double* out, void* stream) {
   Affine34 a;
   if (n < 1 || !v || !out || !ws || ((uintptr_t)ws & 7) || !affine_arg(A, &a)) return -1;
+  double* partial;
+  partials_layout(ws, BOUNDS_BLOCKS, 6, &partial);
   const int blocks = std::max(1, std::min(BOUNDS_BLOCKS, (n + EMESH_WG - 1) / EMESH_WG));
-  hipLaunchKernelGGL(affine_bounds3_partial_kernel, dim3(blocks), dim3(EMESH_WG), 0, (hipStream_t)stream, v, n, a, (double*)ws);
-  hipLaunchKernelGGL(affine_bounds3_finish_kernel, dim3(1), dim3(EMESH_WG), 0, (hipStream_t)stream, (const double*)ws, blocks, out);
+  hipLaunchKernelGGL(affine_bounds3_partial_kernel, dim3(blocks), dim3(EMESH_WG), 0, (hipStream_t)stream, v, n, a, partial);
+  hipLaunchKernelGGL(affine_bounds3_finish_kernel, dim3(1), dim3(EMESH_WG), 0, (hipStream_t)stream, (const double*)partial, blocks, out);
   return (int)hipGetLastError();
 }
 
@@ -838,21 +779,18 @@ static bool eval_grid_args(const neat_eval_grid_t* h, EvalGrid* g) {
   return true;
 }
 
-size_t neat_eval_grid_ws_bytes(int n, int buckets) {
-  if (n < 0 || buckets < 1) return 0;
-  return parse_al((size_t)buckets * sizeof(int)) + parse_al((size_t)std::max(n, 1) * sizeof(int));
-}
+size_t neat_eval_grid_ws_bytes(int n, int buckets) { EvalGridWs w; return eval_grid_layout(nullptr, n, buckets, &w) ? w.total : 0; }
 
 int neat_eval_grid(const double* points, const neat_eval_grid_t* grid, int* start, int* sidx, double* spts, void* ws, void* stream) {
   EvalGrid g;
+  EvalGridWs w;
   if (!eval_grid_args(grid, &g) || !ws || start != grid->start || sidx != grid->sidx || spts != grid->spts || (g.n > 0 && !points)) return -1;
+  if (!eval_grid_layout(ws, g.n, g.buckets, &w)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  int* cnt = (int*)ws;
-  int* bucket_of = (int*)((char*)ws + parse_al((size_t)g.buckets * sizeof(int)));
-  NEAT_CHECK(hipMemsetAsync(cnt, 0, (size_t)g.buckets * sizeof(int), st));
-  if (g.n > 0) hipLaunchKernelGGL(eval_grid_bin_kernel, grid1(g.n, EVAL_WG), dim3(EVAL_WG), 0, st, points, g, bucket_of, cnt);
-  hipLaunchKernelGGL(eval_exscan_kernel, dim3(1), dim3(EVAL_SCAN_WG), 0, st, (const int*)cnt, start, g.buckets, (int*)nullptr);
-  if (g.n > 0) hipLaunchKernelGGL(eval_grid_scatter_kernel, grid1(g.n, EVAL_WG), dim3(EVAL_WG), 0, st, points, g.n, (const int*)bucket_of, cnt,
+  NEAT_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)g.buckets * sizeof(int), st));
+  if (g.n > 0) hipLaunchKernelGGL(eval_grid_bin_kernel, grid1(g.n, EVAL_WG), dim3(EVAL_WG), 0, st, points, g, w.bucket_of, w.cnt);
+  hipLaunchKernelGGL(eval_exscan_kernel, dim3(1), dim3(EVAL_SCAN_WG), 0, st, (const int*)w.cnt, start, g.buckets, (int*)nullptr);
+  if (g.n > 0) hipLaunchKernelGGL(eval_grid_scatter_kernel, grid1(g.n, EVAL_WG), dim3(EVAL_WG), 0, st, points, g.n, (const int*)w.bucket_of, w.cnt,
                                   (const int*)start, sidx, spts);
   return (int)hipGetLastError();
 }
@@ -888,30 +826,27 @@ int neat_eval_obs_mask(const double* points, int n, const double* lo, const doub
   return (int)hipGetLastError();
 }
 
-size_t neat_eval_tri_ws_bytes(int nf) {
-  if (nf < 0) return 0;
-  return 2 * parse_al(((size_t)nf + 1) * sizeof(int));
-}
+size_t neat_eval_tri_ws_bytes(int nf) { EvalTriWs w; return eval_tri_layout(nullptr, nf, &w) ? w.total : 0; }
 
-static inline bool eval_tri_ok(const double* verts, int nv, const int* faces, int nf, double density, void* ws) {
-  return nv >= 0 && nf >= 0 && ws && density > 0.0 && std::isfinite(density) && (nf == 0 || (verts && faces && nv > 0));
+static inline bool eval_tri_ok(const double* verts, int nv, const int* faces, int nf, double density, void* ws, EvalTriWs* w) {
+  return nv >= 0 && eval_tri_layout(ws, nf, w) && ws && density > 0.0 && std::isfinite(density) && (nf == 0 || (verts && faces && nv > 0));
 }
 
 int neat_eval_tri_count(const double* verts, int nv, const int* faces, int nf, double density, void* ws, int* total, void* stream) {
-  if (!eval_tri_ok(verts, nv, faces, nf, density, ws) || !total) return -1;
-  int* counts = (int*)ws;
-  int* offs = (int*)((char*)ws + parse_al(((size_t)nf + 1) * sizeof(int)));
+  EvalTriWs w;
+  if (!eval_tri_ok(verts, nv, faces, nf, density, ws, &w) || !total) return -1;
   hipStream_t st = (hipStream_t)stream;
-  if (nf > 0) hipLaunchKernelGGL(eval_tri_count_kernel, grid1(nf, EVAL_WG / 64), dim3(EVAL_WG), 0, st, verts, nv, faces, nf, density, counts);
-  hipLaunchKernelGGL(eval_exscan_kernel, dim3(1), dim3(EVAL_SCAN_WG), 0, st, (const int*)counts, offs, nf, total);
+  if (nf > 0) hipLaunchKernelGGL(eval_tri_count_kernel, grid1(nf, EVAL_WG / 64), dim3(EVAL_WG), 0, st, verts, nv, faces, nf, density, w.counts);
+  hipLaunchKernelGGL(eval_exscan_kernel, dim3(1), dim3(EVAL_SCAN_WG), 0, st, (const int*)w.counts, w.offs, nf, total);
   return (int)hipGetLastError();
 }
 
 int neat_eval_tri_emit(const double* verts, int nv, const int* faces, int nf, double density, void* ws, double* out, int total, void* stream) {
-  if (!eval_tri_ok(verts, nv, faces, nf, density, ws) || total < 0 || (total > 0 && !out)) return -1;
+  EvalTriWs w;
+  if (!eval_tri_ok(verts, nv, faces, nf, density, ws, &w) || total < 0 || (total > 0 && !out)) return -1;
   if (nf == 0 || total == 0) return 0;
-  const int* offs = (const int*)((char*)ws + parse_al(((size_t)nf + 1) * sizeof(int)));
-  hipLaunchKernelGGL(eval_tri_emit_kernel, grid1(nf, EVAL_WG / 64), dim3(EVAL_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, density, offs, out, total);
+  hipLaunchKernelGGL(eval_tri_emit_kernel, grid1(nf, EVAL_WG / 64), dim3(EVAL_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, density,
+                     (const int*)w.offs, out, total);
   return (int)hipGetLastError();
 }
 
@@ -926,59 +861,40 @@ int neat_eval_line_cost(const double* pred, int n_pred, const double* gt, int n_
 }
 
 // ---- added to ABI v15: pictures of a wireframe and of the mesh behind it (kernels_show.hpp) ---------------------------------------------
-struct ShowWs { unsigned long long* key; unsigned* cov; unsigned* covp; int* status; size_t off[4], bytes; long long total; };
-static bool show_ws(int F, int H, int W, void* ws, ShowWs* s) {
-  if (F < 1 || H < 1 || W < 1 || H > 32768 || W > 32768) return false;
-  const long long total = (long long)F * H * W;
-  if (total > (1ll << 40)) return false;
-  s->total = total;
-  s->off[0] = 0;
-  s->off[1] = parse_al((size_t)total * 8);
-  s->off[2] = s->off[1] + parse_al((size_t)total * 4);
-  s->off[3] = s->off[2] + parse_al((size_t)total * 4);
-  s->bytes = s->off[3] + 256 + (size_t)SHOW_QUEUE_CAP * sizeof(long long);      // status word, queue counter (at +8), the queue of large triangles
-  char* b = (char*)ws;
-  s->key = (unsigned long long*)b; s->cov = (unsigned*)(b + s->off[1]); s->covp = (unsigned*)(b + s->off[2]); s->status = (int*)(b + s->off[3]);
-  return true;
-}
 static inline bool show_grid_ok(long long items, int per_block) { return (items + per_block - 1) / per_block <= (long long)INT_MAX; }
 static inline dim3 show_grid(long long items, int per_block) { return dim3((unsigned)((items + per_block - 1) / per_block)); }
 static inline bool show_common(const double* cams, double near, void* ws) { return cams && ws && near > 0.0 && std::isfinite(near); }
 
-size_t neat_show_ws_bytes(int F, int H, int W) {
-  ShowWs s;
-  return show_ws(F, H, W, nullptr, &s) ? s.bytes : 0;
-}
+size_t neat_show_ws_bytes(int F, int H, int W) { ShowWs s; return show_layout(nullptr, F, H, W, SHOW_QUEUE_CAP, &s) ? s.total : 0; }
 
 int neat_show_ws_layout(int F, int H, int W, size_t* offsets) {
   ShowWs s;
-  if (!offsets || !show_ws(F, H, W, nullptr, &s)) return -1;
-  for (int i = 0; i < 4; ++i) offsets[i] = s.off[i];
+  if (!offsets || !show_layout(nullptr, F, H, W, SHOW_QUEUE_CAP, &s)) return -1;
+  const void* part[4] = {s.key, s.cov, s.covp, s.status};
+  for (int i = 0; i < 4; ++i) offsets[i] = ws_offset(nullptr, part[i]);
   return 0;
 }
 
 int neat_show_clear(void* ws, int F, int H, int W, void* stream) {
   ShowWs s;
-  if (!ws || !show_ws(F, H, W, ws, &s) || !show_grid_ok(s.total, SHOW_WG)) return -1;
-  hipLaunchKernelGGL(show_clear_kernel, show_grid(s.total, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, s.key, s.cov, s.covp, s.status, s.total);
+  if (!ws || !show_layout(ws, F, H, W, SHOW_QUEUE_CAP, &s) || !show_grid_ok(s.pixels, SHOW_WG)) return -1;
+  hipLaunchKernelGGL(show_clear_kernel, show_grid(s.pixels, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, s.key, s.cov, s.covp, s.status, s.pixels);
   return (int)hipGetLastError();
 }
 
 int neat_show_mesh(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, double near, void* ws,
                    void* stream) {
   ShowWs s;
-  if (!show_ws(F, H, W, ws, &s) || !show_common(cams, near, ws) || nv < 0 || nf < 0 || (nf > 0 && (!verts || !faces || nv < 1))) return -1;
+  if (!show_layout(ws, F, H, W, SHOW_QUEUE_CAP, &s) || !show_common(cams, near, ws) || nv < 0 || nf < 0 || (nf > 0 && (!verts || !faces || nv < 1))) return -1;
   const long long items = (long long)F * nf;
   if (!show_grid_ok(items, SHOW_WG)) return -1;
   if (nf == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  unsigned long long* queued = (unsigned long long*)((char*)s.status + 8);
-  long long* queue = (long long*)((char*)s.status + 256);
-  NEAT_CHECK(hipMemsetAsync(queued, 0, sizeof(unsigned long long), st));
+  NEAT_CHECK(hipMemsetAsync(s.queued, 0, sizeof(unsigned long long), st));
   hipLaunchKernelGGL(show_mesh_kernel, show_grid(items, SHOW_WG), dim3(SHOW_WG), 0, st, verts, nv, faces, nf, cams, F, H, W, near, s.key, s.status,
-                     queued, queue, SHOW_QUEUE_CAP);
+                     s.queued, s.queue, SHOW_QUEUE_CAP);
   hipLaunchKernelGGL(show_mesh_large_kernel, dim3(SHOW_LARGE_BLOCKS), dim3(SHOW_WG), 0, st, verts, nv, faces, nf, cams, F, H, W, near, s.key,
-                     (const unsigned long long*)queued, (const long long*)queue, SHOW_QUEUE_CAP);
+                     (const unsigned long long*)s.queued, (const long long*)s.queue, SHOW_QUEUE_CAP);
   return (int)hipGetLastError();
 }
 
@@ -989,7 +905,8 @@ static inline bool show_cover_ok(double size, double bias, double hidden_alpha) 
 int neat_show_lines(const double* lines, int n, const double* cams, int F, int H, int W, double near, double width, double bias,
                     double hidden_alpha, void* ws, void* stream) {
   ShowWs s;
-  if (!show_ws(F, H, W, ws, &s) || !show_common(cams, near, ws) || n < 0 || (n > 0 && !lines) || !show_cover_ok(width, bias, hidden_alpha)) return -1;
+  if (!show_layout(ws, F, H, W, SHOW_QUEUE_CAP, &s) || !show_common(cams, near, ws) || n < 0 || (n > 0 && !lines) || !show_cover_ok(width, bias,
+      hidden_alpha)) return -1;
   const long long items = (long long)F * n;
   if (!show_grid_ok(items, SHOW_WG / 64)) return -1;
   if (n == 0) return 0;
@@ -1001,7 +918,8 @@ int neat_show_lines(const double* lines, int n, const double* cams, int F, int H
 int neat_show_points(const double* points, int n, const double* cams, int F, int H, int W, double near, double radius, double bias,
                      double hidden_alpha, void* ws, void* stream) {
   ShowWs s;
-  if (!show_ws(F, H, W, ws, &s) || !show_common(cams, near, ws) || n < 0 || (n > 0 && !points) || !show_cover_ok(radius, bias, hidden_alpha)) return -1;
+  if (!show_layout(ws, F, H, W, SHOW_QUEUE_CAP, &s) || !show_common(cams, near, ws) || n < 0 || (n > 0 && !points) || !show_cover_ok(radius, bias,
+      hidden_alpha)) return -1;
   const long long items = (long long)F * n;
   if (!show_grid_ok(items, SHOW_WG)) return -1;
   if (n == 0) return 0;
@@ -1013,16 +931,17 @@ int neat_show_points(const double* points, int n, const double* cams, int F, int
 int neat_show_resolve(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, const double* colors, void* ws,
                       unsigned char* out, void* stream) {
   ShowWs s;
-  if (!show_ws(F, H, W, ws, &s) || !cams || !ws || !colors || !out || ((uintptr_t)out & 3) || nv < 0 || nf < 0 || (nf > 0 && (!verts || !faces || nv < 1)))
+  if (!show_layout(ws, F, H, W, SHOW_QUEUE_CAP, &s) || !cams || !ws || !colors || !out || ((uintptr_t)out & 3) || nv < 0 || nf < 0 ||
+      (nf > 0 && (!verts || !faces || nv < 1)))
     return -1;
   ShowStyle st;
   for (int c = 0; c < 3; ++c) {
     st.bg[c] = colors[c]; st.line[c] = colors[3 + c]; st.point[c] = colors[6 + c]; st.mesh[c] = colors[9 + c];
   }
   for (int c = 0; c < 12; ++c) if (!(colors[c] >= 0.0 && colors[c] <= 1.0)) return -1;
-  const long long quads = (s.total + 3) / 4;
+  const long long quads = (s.pixels + 3) / 4;
   if (!show_grid_ok(quads, SHOW_WG)) return -1;
-  hipLaunchKernelGGL(show_resolve_kernel, show_grid(quads, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, cams, H, W, s.total, st,
+  hipLaunchKernelGGL(show_resolve_kernel, show_grid(quads, SHOW_WG), dim3(SHOW_WG), 0, (hipStream_t)stream, verts, nv, faces, nf, cams, H, W, s.pixels, st,
                      (const unsigned long long*)s.key, (const float*)s.cov, (const float*)s.covp, (const int*)s.status, out);
   return (int)hipGetLastError();
 }
@@ -1041,39 +960,30 @@ int neat_frame_put(const float* rgb, const float* normal, const float* depth, co
   return (int)hipGetLastError();
 }
 
-// the levels of the tree above the leaves: ceil(n / 256) run sums, then ceil of that / 256 ... down to the level of at most 256 values
-size_t neat_frame_sum_ws_bytes(long long n) {
-  if (n < 0) return 0;
-  size_t doubles = 0;
-  for (long long m = (n + FRAME_WG - 1) / FRAME_WG; m > 1; m = (m + FRAME_WG - 1) / FRAME_WG) doubles += (size_t)m;
-  return parse_al(doubles * sizeof(double) + sizeof(double));
-}
+size_t neat_frame_sum_ws_bytes(long long n) { SumTreeWs t; return sum_tree_layout(nullptr, n, FRAME_WG, FRAME_WG, 1, &t) ? t.total : 0; }
 
 int neat_frame_sum(const float* x, long long n, void* ws, double* out, void* stream) {
-  if (n < 0 || !out || (n > 0 && !x) || !frame_blocks_ok(n)) return -1;
+  SumTreeWs t;
+  if (!sum_tree_layout(ws, n, FRAME_WG, FRAME_WG, 1, &t) || !out || (n > 0 && !x) || !frame_blocks_ok(n)) return -1;
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) return (int)hipMemsetAsync(out, 0, sizeof(double), st);
-  long long m = (n + FRAME_WG - 1) / FRAME_WG;
-  if (m > 1 && (!ws || ((uintptr_t)ws & 7))) return -1;
-  double* level = (double*)ws;
-  hipLaunchKernelGGL(frame_sum_kernel<float>, dim3((unsigned)m), dim3(FRAME_WG), 0, st, x, n, m > 1 ? level : out);
-  while (m > 1) {
-    const long long up = (m + FRAME_WG - 1) / FRAME_WG;
-    double* next = up > 1 ? level + m : out;
-    hipLaunchKernelGGL(frame_sum_kernel<double>, dim3((unsigned)up), dim3(FRAME_WG), 0, st, (const double*)level, m, next);
-    level = next;
-    m = up;
-  }
+  if (t.levels > 0 && (!ws || ((uintptr_t)ws & 7))) return -1;
+  hipLaunchKernelGGL(frame_sum_kernel<float>, dim3((unsigned)t.m[0]), dim3(FRAME_WG), 0, st, x, n, t.levels ? t.level[0] : out);
+  for (int k = 0; k < t.levels; ++k)
+    hipLaunchKernelGGL(frame_sum_kernel<double>, dim3((unsigned)t.m[k + 1]), dim3(FRAME_WG), 0, st, (const double*)t.level[k], t.m[k],
+                       k + 1 < t.levels ? t.level[k + 1] : out);
   return (int)hipGetLastError();
 }
 
-size_t neat_frame_range_ws_bytes(void) { return (size_t)FRAME_RANGE_BLOCKS * 2 * sizeof(float); }
+size_t neat_frame_range_ws_bytes(void) { float* p; return partials_layout(nullptr, FRAME_RANGE_BLOCKS, 2, &p); }
 
 int neat_frame_range(const float* x, long long n, void* ws, float* range, void* stream) {
   if (n < 0 || !range || !ws || ((uintptr_t)ws & 3) || (n > 0 && !x)) return -1;
+  float* partial;
+  partials_layout(ws, FRAME_RANGE_BLOCKS, 2, &partial);
   const int blocks = (int)std::max(1ll, std::min((long long)FRAME_RANGE_BLOCKS, (n + FRAME_WG - 1) / FRAME_WG));
-  hipLaunchKernelGGL(frame_range_partial_kernel, dim3(blocks), dim3(FRAME_WG), 0, (hipStream_t)stream, x, n, (float*)ws);
-  hipLaunchKernelGGL(frame_range_finish_kernel, dim3(1), dim3(FRAME_WG), 0, (hipStream_t)stream, (const float*)ws, blocks, range);
+  hipLaunchKernelGGL(frame_range_partial_kernel, dim3(blocks), dim3(FRAME_WG), 0, (hipStream_t)stream, x, n, partial);
+  hipLaunchKernelGGL(frame_range_finish_kernel, dim3(1), dim3(FRAME_WG), 0, (hipStream_t)stream, (const float*)partial, blocks, range);
   return (int)hipGetLastError();
 }
 
@@ -1097,43 +1007,22 @@ int neat_frame_grid(const unsigned char* images, int N, int H, int W, int nrow, 
 // ---- added to ABI v15: sphere tracing of an SDF along rays (kernels_trace.hpp) ------------------------------------------------------------
 static inline int trace_tiles(int R) { return (R + TRACE_WG - 1) / TRACE_WG; }
 
-static TraceWs trace_ws(void* ws, int R) {
-  TraceWs w{};
-  char* p = (char*)ws;
-  const size_t fl = parse_al((size_t)R * sizeof(float)), by = parse_al((size_t)R);
-  float** fp[6] = {&w.t, &w.ta, &w.fa, &w.tb, &w.fb, &w.t1};
-  for (auto f : fp) { *f = (float*)p; p += fl; }
-  int** ip[5] = {&w.steps, &w.march, &w.refine, &w.ids[0], &w.ids[1]};
-  for (auto i : ip) { *i = (int*)p; p += fl; }
-  w.phase = (unsigned char*)p; p += by;
-  w.side = (unsigned char*)p; p += by;
-  w.flag = (unsigned char*)p; p += by;
-  w.tile = (int*)p;
-  return w;
-}
-
-constexpr int TRACE_MAX_RAYS = 1 << 24;      // trace_scan_kernel is one workgroup of 1024 over ceil(R / 256) counts: 64 rounds at most
-
-size_t neat_trace_ws_bytes(int R) {
-  if (R < 1 || R > TRACE_MAX_RAYS) return 0;
-  return 11 * parse_al((size_t)R * sizeof(float)) + 3 * parse_al((size_t)R) + parse_al((size_t)trace_tiles(R) * sizeof(int));
-}
+size_t neat_trace_ws_bytes(int R) { TraceWs w; return trace_layout(nullptr, R, TRACE_WG, &w); }
 
 size_t neat_trace_list_offset(int R, int parity) {
-  if (R < 1 || R > TRACE_MAX_RAYS || (parity != 0 && parity != 1)) return 0;
-  char base[1];
-  const TraceWs w = trace_ws(base, R);
-  return (size_t)((char*)w.ids[parity] - base);
+  TraceWs w;
+  if ((parity != 0 && parity != 1) || !trace_layout(nullptr, R, TRACE_WG, &w)) return 0;
+  return ws_offset(nullptr, w.ids[parity]);
 }
 
-static inline bool trace_common(const float* origins, const float* dirs, int R, void* ws) {
-  return origins && dirs && R >= 1 && R <= TRACE_MAX_RAYS && ws && !((uintptr_t)ws & 255);
+static inline bool trace_common(const float* origins, const float* dirs, int R, void* ws, TraceWs* w) {
+  return origins && dirs && ws && !((uintptr_t)ws & 255) && trace_layout(ws, R, TRACE_WG, w);
 }
 
 int neat_trace_init(const float* origins, const float* dirs, const float* t_end, int R, double radius, double near, void* ws, float* points,
                     long long* ctl, void* stream) {
-  if (!trace_common(origins, dirs, R, ws) || !points || !ctl || !(radius > 0.0) || !std::isfinite(radius) || !std::isfinite(near)) return -1;
-  const TraceWs w = trace_ws(ws, R);
+  TraceWs w;
+  if (!trace_common(origins, dirs, R, ws, &w) || !points || !ctl || !(radius > 0.0) || !std::isfinite(radius) || !std::isfinite(near)) return -1;
   const int tiles = trace_tiles(R);
   hipLaunchKernelGGL(trace_init_kernel, dim3(tiles), dim3(TRACE_WG), 0, (hipStream_t)stream, w, origins, dirs, t_end, R, radius, near);
   hipLaunchKernelGGL(trace_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w.tile, tiles, ctl, 1);
@@ -1144,9 +1033,9 @@ int neat_trace_init(const float* origins, const float* dirs, const float* t_end,
 
 int neat_trace_step(const float* origins, const float* dirs, const float* values, int n, int R, int parity, float eps, float relax,
                     int max_steps, int refine_steps, void* ws, float* points, long long* ctl, void* stream) {
-  if (!trace_common(origins, dirs, R, ws) || !points || !ctl || n < 0 || n > R || (n > 0 && !values) || (parity != 0 && parity != 1)) return -1;
+  TraceWs w;
+  if (!trace_common(origins, dirs, R, ws, &w) || !points || !ctl || n < 0 || n > R || (n > 0 && !values) || (parity != 0 && parity != 1)) return -1;
   if (!(eps > 0.f) || !(relax > 0.f) || !std::isfinite(eps) || !std::isfinite(relax) || max_steps < 0 || refine_steps < 0 || refine_steps > 64) return -1;
-  const TraceWs w = trace_ws(ws, R);
   const int tiles = std::max(trace_tiles(n), 1);
   hipLaunchKernelGGL(trace_advance_kernel, dim3(tiles), dim3(TRACE_WG), 0, (hipStream_t)stream, w, (const int*)w.ids[parity], values, n, R,
                      (const long long*)ctl, eps, relax, max_steps, refine_steps);
@@ -1158,8 +1047,9 @@ int neat_trace_step(const float* origins, const float* dirs, const float* values
 
 int neat_trace_finish(const float* origins, const float* dirs, int R, void* ws, float* depth, unsigned char* state, int* steps,
                       float* hit_points, void* stream) {
-  if (!trace_common(origins, dirs, R, ws)) return -1;
-  hipLaunchKernelGGL(trace_finish_kernel, dim3(trace_tiles(R)), dim3(TRACE_WG), 0, (hipStream_t)stream, trace_ws(ws, R), origins, dirs, R, depth,
+  TraceWs w;
+  if (!trace_common(origins, dirs, R, ws, &w)) return -1;
+  hipLaunchKernelGGL(trace_finish_kernel, dim3(trace_tiles(R)), dim3(TRACE_WG), 0, (hipStream_t)stream, w, origins, dirs, R, depth,
                      state, steps, hit_points);
   return (int)hipGetLastError();
 }
@@ -1177,31 +1067,25 @@ int neat_trace_target_rays(const float* centres, int F, const float* rows, int s
 }
 
 // ---- added to ABI v15: fuse, refine and snap of a parsed line soup (kernels_post.hpp) ----------------------------------------------------------
-size_t neat_post_fuse_ws_bytes(int n, int V, int mtot) {
-  PostFuseWs w;
-  return post_fuse_layout(n, V, mtot, &w) ? w.total : 0;
-}
+size_t neat_post_fuse_ws_bytes(int n, int V, int mtot) { PostFuseWs w; return post_fuse_layout(nullptr, n, V, mtot, &w) ? w.total : 0; }
 
 int neat_post_fuse(const float* lines, int n, const float* det, int det_stride, const int* det_off, int mtot, const float* K3, const float* w2c,
                    int V, float dis_threshold, float keep_threshold, int by_label, float* score, int* count, unsigned char* keep, float* kept,
                    int* n_kept, void* ws, void* stream) {
   PostFuseWs w;
-  if (!post_fuse_layout(n, V, mtot, &w) || !n_kept || (by_label != 0 && by_label != 1)) return -1;
+  if (!post_fuse_layout(ws, n, V, mtot, &w) || !n_kept || (by_label != 0 && by_label != 1)) return -1;
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) return (int)hipMemsetAsync(n_kept, 0, sizeof(int), st);
   if (!lines || !score || !count || !keep || !kept || !ws || (V > 0 && (!det_off || !K3 || !w2c)) || (mtot > 0 && (!det || det_stride < 5))) return -1;
-  int* label = (int*)((char*)ws + w.label);
-  unsigned char* present = (unsigned char*)ws + w.present;
-  int* rank = (int*)((char*)ws + w.rank);
   if (V > 0) {
-    if (mtot > 0) NEAT_CHECK(hipMemsetAsync(present, 0, (size_t)mtot, st));
+    if (mtot > 0) NEAT_CHECK(hipMemsetAsync(w.present, 0, (size_t)mtot, st));
     hipLaunchKernelGGL(post_match_kernel, dim3((n + PARSE_WG - 1) / PARSE_WG, V), dim3(PARSE_WG), 0, st, lines, (const int*)nullptr, n, det,
-                       det_stride, det_off, K3, w2c, 0, dis_threshold, 0, 0.f, 0.f, label, present);
-    hipLaunchKernelGGL(post_rank_kernel, dim3(V), dim3(1024), 0, st, present, det_off, rank);
+                       det_stride, det_off, K3, w2c, 0, dis_threshold, 0, 0.f, 0.f, w.label, w.present);
+    hipLaunchKernelGGL(post_rank_kernel, dim3(V), dim3(1024), 0, st, w.present, det_off, w.rank);
   }
-  hipLaunchKernelGGL(post_fuse_score_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, st, label, n, V, det, det_stride, det_off, rank, by_label,
+  hipLaunchKernelGGL(post_fuse_score_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, st, w.label, n, V, det, det_stride, det_off, w.rank, by_label,
                      keep_threshold, score, count, keep);
-  hipLaunchKernelGGL(post_keep_kernel, dim3(1), dim3(1024), 0, st, lines, n, keep, (int*)((char*)ws + w.idx), kept, n_kept);
+  hipLaunchKernelGGL(post_keep_kernel, dim3(1), dim3(1024), 0, st, lines, n, keep, w.idx, kept, n_kept);
   return (int)hipGetLastError();
 }
 
@@ -1213,31 +1097,23 @@ int neat_post_select(const float* lines, int n, const unsigned char* keep, float
   return (int)hipGetLastError();
 }
 
-size_t neat_post_refine_ws_bytes(int ncap, int mmax) {
-  PostRefineWs w;
-  if (ncap < 0 || mmax < 0) return 0;
-  return post_refine_layout(ncap, mmax, neat_parse_group_ws_bytes(ncap, mmax), &w) ? w.total : 0;
-}
+size_t neat_post_refine_ws_bytes(int ncap, int mmax) { PostRefineWs w; return post_refine_layout(nullptr, ncap, mmax, PARSE_TILE, &w) ? w.total : 0; }
 
 int neat_post_refine_view(const float* cur, const int* n_cur, int ncap, const float* det, int det_stride, const int* det_off, int m, int mmax,
                           const float* K3, const float* w2c, int view, float dis_threshold, float width, float height, float* next, int* n_next,
                           void* ws, void* stream) {
   PostRefineWs w;
-  if (ncap < 0 || mmax < 0 || m < 0 || m > mmax || view < 0 || !post_refine_layout(ncap, mmax, neat_parse_group_ws_bytes(ncap, mmax), &w)) return -1;
+  if (m < 0 || m > mmax || view < 0 || !post_refine_layout(ws, ncap, mmax, PARSE_TILE, &w)) return -1;
   if (ncap == 0) return 0;
   if (!cur || !n_cur || !next || !n_next || !ws || !det_off || !K3 || !w2c || (m > 0 && (!det || det_stride < 4))) return -1;
   hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)ws;
-  int* label = (int*)(p + w.label);
-  float* glines = (float*)(p + w.glines);
-  int* gcount = (int*)(p + w.gcount);
   hipLaunchKernelGGL(post_match_kernel, dim3((ncap + PARSE_WG - 1) / PARSE_WG, 1), dim3(PARSE_WG), 0, st, cur, n_cur, ncap, det, det_stride, det_off,
-                     K3, w2c, view, dis_threshold, 1, width, height, label, (unsigned char*)nullptr);
+                     K3, w2c, view, dis_threshold, 1, width, height, w.label, (unsigned char*)nullptr);
   NEAT_CHECK(hipGetLastError());
   // the stable grouping by label and the means of the groups after reversal: parse_group's (its score output is not used; l3d = the lines)
-  const int e = neat_parse_group(label, cur, cur, ncap, m, glines, (float*)(p + w.gscores), gcount, p + w.group, stream);
+  const int e = neat_parse_group(w.label, cur, cur, ncap, m, w.glines, w.gscores, w.gcount, w.group, stream);
   if (e != 0) return e;
-  hipLaunchKernelGGL(post_refine_assemble_kernel, dim3(1), dim3(1024), 0, st, cur, n_cur, ncap, label, glines, gcount, (int*)(p + w.idx), next,
+  hipLaunchKernelGGL(post_refine_assemble_kernel, dim3(1), dim3(1024), 0, st, cur, n_cur, ncap, w.label, w.glines, w.gcount, w.idx, next,
                      n_next);
   return (int)hipGetLastError();
 }
@@ -1250,11 +1126,7 @@ static size_t post_sort_bytes(int n) {
   return std::max(a, b);
 }
 
-size_t neat_post_snap_ws_bytes(int n, int G) {
-  PostSnapWs w;
-  if (n < 0) return 0;
-  return post_snap_layout(n, G, post_sort_bytes(n), &w) ? w.total : 0;
-}
+size_t neat_post_snap_ws_bytes(int n, int G) { PostSnapWs w; return post_snap_layout(nullptr, n, G, post_sort_bytes(n), &w) ? w.total : 0; }
 
 int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique, float* junctions, int* pcount, int* edges, float* lines_out,
                    int* counts, void* ws, void* stream) {
@@ -1263,126 +1135,76 @@ int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique,
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) return (int)hipMemsetAsync(counts, 0, 2 * sizeof(int), st);
   const size_t sort_bytes = post_sort_bytes(n);
-  if (!post_snap_layout(n, G, sort_bytes, &w) || !lines || !junctions || !pcount || !edges || !lines_out || !ws) return -1;
+  if (!post_snap_layout(ws, n, G, sort_bytes, &w) || !lines || !junctions || !pcount || !edges || !lines_out || !ws) return -1;
   const int M = 2 * n;
-  char* p = (char*)ws;
-  float* box = (float*)(p + w.box);
-  int* wcnt = (int*)(p + w.counts);
-  int *key = (int*)(p + w.key), *skey = (int*)(p + w.skey), *head = (int*)(p + w.head), *flag = (int*)(p + w.flag), *cnt = (int*)(p + w.cnt);
-  int *pidx = (int*)(p + w.pidx), *near = (int*)(p + w.near), *idx = (int*)(p + w.idx);
-  float* dist2 = (float*)(p + w.dist2);
-  hipLaunchKernelGGL(post_snap_bbox_kernel, dim3(1), dim3(1024), 0, st, lines, M, G, box);
-  hipLaunchKernelGGL(post_snap_key_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, lines, M, G, (const float*)box, key);
+  hipLaunchKernelGGL(post_snap_bbox_kernel, dim3(1), dim3(1024), 0, st, lines, M, G, w.box);
+  hipLaunchKernelGGL(post_snap_key_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, lines, M, G, (const float*)w.box, w.key);
   NEAT_CHECK(hipGetLastError());
   size_t tb = sort_bytes;
-  NEAT_CHECK(rocprim::radix_sort_keys((void*)(p + w.sort), tb, key, skey, (size_t)M, 0u, 32u, st));
-  hipLaunchKernelGGL(post_snap_cells_kernel, dim3(1), dim3(1024), 0, st, (const int*)skey, M, head, wcnt);
-  hipLaunchKernelGGL(post_snap_peak_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)skey, (const int*)head, (const int*)wcnt, M, G,
-                     flag, cnt);
-  hipLaunchKernelGGL(post_snap_select_kernel, dim3(1), dim3(1024), 0, st, (const int*)skey, (const int*)head, (const int*)wcnt, M, G,
-                     (const float*)box, (const int*)flag, (const int*)cnt, pidx, junctions, pcount, counts);
+  NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.key, w.skey, (size_t)M, 0u, 32u, st));
+  hipLaunchKernelGGL(post_snap_cells_kernel, dim3(1), dim3(1024), 0, st, (const int*)w.skey, M, w.head, w.counts);
+  hipLaunchKernelGGL(post_snap_peak_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)w.skey, (const int*)w.head, (const int*)w.counts, M, G,
+                     w.flag, w.cnt);
+  hipLaunchKernelGGL(post_snap_select_kernel, dim3(1), dim3(1024), 0, st, (const int*)w.skey, (const int*)w.head, (const int*)w.counts, M, G,
+                     (const float*)w.box, (const int*)w.flag, (const int*)w.cnt, w.pidx, junctions, pcount, counts);
   hipLaunchKernelGGL(post_snap_nearest_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, lines, M, (const float*)junctions, (const int*)counts,
-                     near, dist2);
+                     w.near, w.dist2);
   if (!unique) {
-    hipLaunchKernelGGL(post_snap_edges_kernel, dim3(1), dim3(1024), 0, st, (const int*)near, (const float*)dist2, n, max_snap,
-                       (const float*)junctions, idx, edges, lines_out, counts + 1);
+    hipLaunchKernelGGL(post_snap_edges_kernel, dim3(1), dim3(1024), 0, st, (const int*)w.near, (const float*)w.dist2, n, max_snap,
+                       (const float*)junctions, w.idx, edges, lines_out, counts + 1);
     return (int)hipGetLastError();
   }
-  unsigned long long *pkey = (unsigned long long*)(p + w.pkey), *spkey = (unsigned long long*)(p + w.spkey);
-  hipLaunchKernelGGL(post_snap_pairkey_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)near, (const float*)dist2, n, max_snap, pkey);
+  hipLaunchKernelGGL(post_snap_pairkey_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)w.near, (const float*)w.dist2, n, max_snap, w.pkey);
   NEAT_CHECK(hipGetLastError());
   tb = sort_bytes;
-  NEAT_CHECK(rocprim::radix_sort_keys((void*)(p + w.sort), tb, pkey, spkey, (size_t)n, 0u, 64u, st));
-  hipLaunchKernelGGL(post_snap_unique_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long*)spkey, n, (const float*)junctions, idx, edges,
+  NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.pkey, w.spkey, (size_t)n, 0u, 64u, st));
+  hipLaunchKernelGGL(post_snap_unique_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long*)w.spkey, n, (const float*)junctions, w.idx, edges,
                      lines_out, counts + 1);
   return (int)hipGetLastError();
 }
 
 // ---- added to ABI v15: ray casting against a triangle mesh (kernels_raycast.hpp) ---------------------------------------------------------------
-struct RaycastLayout { int L, per; size_t nodes, tris, bvh_total; size_t key, skey, val, sval, partial, box, sort, sort_bytes, ws_total; };
+size_t neat_raycast_bvh_bytes(int nf) { RaycastWs w; return raycast_layout(nullptr, nullptr, nf, RC_WG, RC_TRI_STRIDE, &w) ? w.bvh_total : 0; }
 
-static bool raycast_layout(int nf, RaycastLayout* w) {
-  if (nf < 0 || nf > RC_MAX_FACES) return false;
-  int L = 1;
-  while (L < nf) L <<= 1;
-  w->L = L;
-  w->per = std::min(L, RC_WG);
-  size_t o = 256;                                          // the status word
-  w->nodes = o; o += parse_al((size_t)2 * L * 6 * sizeof(float));
-  w->tris = o; o += parse_al((size_t)nf * RC_TRI_STRIDE * sizeof(double));
-  w->bvh_total = o;
-  // room for the radix sort, fixed by nf alone so that the size does not depend on a device being present: rocprim's temporary keys
-  // and values (12 bytes a triangle), its histograms and per-block look-back states; the build asks rocprim and refuses if it wants more
-  const size_t sb = nf > 0 ? (size_t)32 * nf + ((size_t)4 << 20) : 0;
-  w->sort_bytes = sb;
-  o = 0;
-  w->key = o; o += parse_al((size_t)nf * sizeof(unsigned long long));
-  w->skey = o; o += parse_al((size_t)nf * sizeof(unsigned long long));
-  w->val = o; o += parse_al((size_t)nf * sizeof(int));
-  w->sval = o; o += parse_al((size_t)nf * sizeof(int));
-  w->partial = o; o += parse_al((size_t)((nf + RC_WG - 1) / RC_WG) * 6 * sizeof(double));
-  w->box = o; o += 256;
-  w->sort = o; o += parse_al(sb);
-  w->ws_total = o;
-  return true;
-}
-
-size_t neat_raycast_bvh_bytes(int nf) {
-  RaycastLayout w;
-  return raycast_layout(nf, &w) ? w.bvh_total : 0;
-}
-
-size_t neat_raycast_ws_bytes(int nf) {
-  RaycastLayout w;
-  return raycast_layout(nf, &w) ? w.ws_total : 0;
-}
+size_t neat_raycast_ws_bytes(int nf) { RaycastWs w; return raycast_layout(nullptr, nullptr, nf, RC_WG, RC_TRI_STRIDE, &w) ? w.ws_total : 0; }
 
 int neat_raycast_build(const double* verts, int nv, const int* faces, int nf, void* bvh, void* ws, void* stream) {
-  RaycastLayout w;
-  if (nv < 0 || !bvh || ((uintptr_t)bvh & 255) || !raycast_layout(nf, &w)) return -1;
+  RaycastWs w;
+  if (nv < 0 || !bvh || ((uintptr_t)bvh & 255) || !raycast_layout(bvh, ws, nf, RC_WG, RC_TRI_STRIDE, &w)) return -1;
   if (nf > 0 && (!faces || !ws || ((uintptr_t)ws & 255) || (nv > 0 && !verts))) return -1;
   hipStream_t st = (hipStream_t)stream;
-  char *b = (char*)bvh, *p = (char*)ws;
-  int* status = (int*)b;
-  float* nodes = (float*)(b + w.nodes);
-  double* tris = (double*)(b + w.tris);
-  NEAT_CHECK(hipMemsetAsync(b, 0, 256, st));
-  int* sval = nullptr;
+  NEAT_CHECK(hipMemsetAsync(w.status, 0, 256, st));
   if (nf > 0) {
-    unsigned long long *key = (unsigned long long*)(p + w.key), *skey = (unsigned long long*)(p + w.skey);
-    int* val = (int*)(p + w.val);
-    sval = (int*)(p + w.sval);
-    double *partial = (double*)(p + w.partial), *box = (double*)(p + w.box);
-    const int tiles = (nf + RC_WG - 1) / RC_WG;
     size_t tb = 0;
-    NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, tb, key, skey, val, sval, (size_t)nf, 0u, 64u, st));
+    NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, tb, w.key, w.skey, w.val, w.sval, (size_t)nf, 0u, 64u, st));
     if (tb > w.sort_bytes) return -2;
-    hipLaunchKernelGGL(raycast_prep_kernel, dim3(tiles), dim3(RC_WG), 0, st, verts, nv, faces, nf, status, partial);
-    hipLaunchKernelGGL(raycast_scene_box_kernel, dim3(1), dim3(RC_WG), 0, st, (const double*)partial, tiles, box);
-    hipLaunchKernelGGL(raycast_key_kernel, dim3(tiles), dim3(RC_WG), 0, st, verts, faces, nf, (const int*)status, (const double*)box, key, val);
+    hipLaunchKernelGGL(raycast_prep_kernel, dim3(w.tiles), dim3(RC_WG), 0, st, verts, nv, faces, nf, w.status, w.partial);
+    hipLaunchKernelGGL(raycast_scene_box_kernel, dim3(1), dim3(RC_WG), 0, st, (const double*)w.partial, w.tiles, w.box);
+    hipLaunchKernelGGL(raycast_key_kernel, dim3(w.tiles), dim3(RC_WG), 0, st, verts, faces, nf, (const int*)w.status, (const double*)w.box, w.key, w.val);
     NEAT_CHECK(hipGetLastError());
-    NEAT_CHECK(rocprim::radix_sort_pairs((void*)(p + w.sort), tb, key, skey, val, sval, (size_t)nf, 0u, 64u, st));
+    NEAT_CHECK(rocprim::radix_sort_pairs(w.sort, tb, w.key, w.skey, w.val, w.sval, (size_t)nf, 0u, 64u, st));
   }
-  hipLaunchKernelGGL(raycast_leaf_kernel, dim3(w.L / w.per), dim3(RC_WG), 0, st, verts, faces, nf, w.L, w.per, (const int*)status, (const int*)sval,
-                     nodes, tris);
-  if (w.L > w.per) hipLaunchKernelGGL(raycast_top_kernel, dim3(1), dim3(RC_TOP_WG), 0, st, nodes, w.L / w.per);
+  hipLaunchKernelGGL(raycast_leaf_kernel, dim3(w.L / w.per), dim3(RC_WG), 0, st, verts, faces, nf, w.L, w.per, (const int*)w.status,
+                       (const int*)(nf > 0 ? w.sval : nullptr),
+                     w.nodes, w.tris);
+  if (w.L > w.per) hipLaunchKernelGGL(raycast_top_kernel, dim3(1), dim3(RC_TOP_WG), 0, st, w.nodes, w.L / w.per);
   return (int)hipGetLastError();
 }
 
 int neat_raycast_cast(const void* bvh, int nf, const float* origins, const float* dirs, const float* t_min, const float* t_max, int R, int any_hit,
                       float* t, int* tri, float* uv, unsigned* counts, void* stream) {
-  RaycastLayout w;
-  if (!bvh || ((uintptr_t)bvh & 255) || !raycast_layout(nf, &w) || R < 0 || R > INT_MAX / 4 || (any_hit != 0 && any_hit != 1)) return -1;
+  RaycastWs w;
+  if (!bvh || ((uintptr_t)bvh & 255) || !raycast_layout(const_cast<void*>(bvh), nullptr, nf, RC_WG, RC_TRI_STRIDE, &w) || R < 0 || R > INT_MAX / 4 ||
+      (any_hit != 0 && any_hit != 1)) return -1;
   if (R == 0) return 0;
   if (!origins || !dirs || !t || !tri || !uv) return -1;
-  const char* b = (const char*)bvh;
-  const float* nodes = (const float*)(b + w.nodes);
-  const double* tris = (const double*)(b + w.tris);
   if (any_hit)
-    hipLaunchKernelGGL(raycast_cast_kernel<true>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, nodes, tris, nf, w.L, origins, dirs, t_min, t_max,
+    hipLaunchKernelGGL(raycast_cast_kernel<true>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, (const float*)w.nodes, (const double*)w.tris,
+                         nf, w.L, origins, dirs, t_min, t_max,
                        R, t, tri, uv, counts);
   else
-    hipLaunchKernelGGL(raycast_cast_kernel<false>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, nodes, tris, nf, w.L, origins, dirs, t_min, t_max,
+    hipLaunchKernelGGL(raycast_cast_kernel<false>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, (const float*)w.nodes,
+                         (const double*)w.tris, nf, w.L, origins, dirs, t_min, t_max,
                        R, t, tri, uv, counts);
   return (int)hipGetLastError();
 }

@@ -62,6 +62,30 @@ def test_workspace_queries_are_consistent():
     assert lib.neat_sdf_ldp(0, 2) == 0
 
 
+def test_tool_workspace_sizes_and_offsets_are_pinned():
+    """Python allocates the tools' workspaces from the *_ws_bytes queries and reads parts of them at the offsets neat_show_ws_layout and
+    neat_trace_list_offset report, so these values are part of the ABI.  tests/ws_sizes.json is a table (query, arguments) -> value
+    recorded from the library before the layouts moved to csrc/ws_layout.hpp: arguments around every tile size (0, 1, 255, 256, 257,
+    4096, 4097; grids of 2048 nodes, one tile of the mesh, and of 2050, the nearest above that three axes of two nodes and more can
+    make) and arguments each query refuses (0, or None for neat_show_ws_layout's -1).  The queries touch no device.
+    neat_post_snap_ws_bytes is pinned where it does not include rocprim's own temporary storage (no lines, refusals)."""
+    import json
+    from neat_amd import _lib
+    lib = _lib.lib()
+    table = json.load(open(os.path.join(ROOT, "tests", "ws_sizes.json")))
+    queries = {q for q, _, _ in table}
+    wanted = {n for n in _lib.exported_symbols() if n.endswith("_ws_bytes")} | {"neat_raycast_bvh_bytes", "neat_show_ws_layout", "neat_trace_list_offset"}
+    assert queries == wanted, sorted(queries ^ wanted)
+    assert sum(1 for _, args, v in table if not v and min(args) < 0) >= 25          # refusals (a negative count); an empty workspace is 0 too
+    for query, args, want in table:
+        if query == "neat_show_ws_layout":
+            off = (ctypes.c_size_t * 4)()
+            got = list(off) if lib.neat_show_ws_layout(*args, off) == 0 else None
+        else:
+            got = getattr(lib, query)(*args)
+        assert got == want, (query, args, got, want)
+
+
 def test_tuning_keys_retired_and_surviving():
     """neat_set_tuning only writes host switches, so this runs without a GPU.  Every retired key (closed experiments: the key list in
     include/neat_hip.h) is rejected with -1 for every value it once took, its old default included; every surviving key accepts its

@@ -60,6 +60,26 @@ def test_sampled_points_equal_numpy_bit_for_bit(E, g20):
         E.sample_mesh(t64(np.eye(3)), torch.tensor([[0, 1, 3]]).to(DEV), 0.2)
 
 
+def test_grid_offsets_past_1024_buckets(E):
+    """11^3 = 1331 dense buckets: the one workgroup of 1024 that scans the histogram (eval_exscan_kernel) takes a second round with a
+    carry.  start must be numpy's exclusive cumulative sum of the histogram; the slot of a point within its bucket is handed out by an
+    atomic countdown, so the slots are compared bucket by bucket."""
+    rng = np.random.default_rng(9)
+    p = rng.uniform(0, 1, (1025, 3))
+    p[0], p[1] = 0.0, 1.0                                                 # the box is the unit cube: 10 cells of 0.1 and the far face
+    grid = E.Grid(t64(p), 0.1)
+    assert grid.dense and grid.dim == [11, 11, 11] and grid.buckets == 1331
+    c = np.clip(np.floor((p - 0.0) / grid.cell).astype(np.int64), 0, 10)
+    bucket = (c[:, 0] * 11 + c[:, 1]) * 11 + c[:, 2]
+    hist = np.bincount(bucket, minlength=1331)
+    assert (hist[1024:] > 0).any() and (hist[:1024] > 0).any()
+    start = grid.start.cpu().numpy()
+    assert np.array_equal(start, np.concatenate([[0], np.cumsum(hist)]))
+    sidx = grid.sidx.cpu().numpy()
+    assert np.array_equal(np.sort(sidx), np.arange(1025)) and np.array_equal(bucket[sidx], np.repeat(np.arange(1331), hist))
+    assert np.array_equal(grid.spts.cpu().numpy(), p[sidx])
+
+
 def test_thinning_equals_the_reference_s_data_down(E, g20):
     cloud = E.sample_mesh(t64(g20["verts"]), torch.as_tensor(g20["faces"]).to(DEV), 0.2)
     kept = E.thin(cloud, 0.2, order=g20["mesh_perm"])

@@ -102,6 +102,25 @@ def test_moments_equal_the_restatement(meshes):
     assert (ops.mesh_moments(v, degenerate, o) == 0).all()        # triangles without area add nothing
 
 
+def test_moments_over_two_levels_above_the_leaves(meshes):
+    """WG TILE + 1 triangles are 257 leaf sums, which the tree reduces to 2 and then to 1: two levels above the leaves, where the
+    shapes above stop at one.  The triangles are the sphere's, repeated; judged as test_moments_equal_the_restatement judges."""
+    from neat_amd import ops
+    v, f, hv, hf = meshes["sphere", 65]
+    nf = WG * TILE + 1
+    reps = -(-nf // len(hf))
+    f2, hf2 = f.repeat(reps, 1)[:nf].contiguous(), np.tile(hf, (reps, 1))[:nf]
+    o = np.array([0.02, -0.01, 0.03])
+    got = ops.mesh_moments(v, f2, o)
+    want = E.moments(hv, hf2, o)
+    r = np.linalg.norm(hv[np.unique(hf2)] - o, axis=1).max()
+    bar = 1e-12 * want[0] * r * r
+    err = np.abs(got - want).max()
+    print(f"nf {nf}: area {want[0]:.6e} max error {err:.3e} (bar {bar:.3e})")
+    assert err <= bar
+    assert ops.mesh_moments(v, f2, o).tobytes() == got.tobytes()
+
+
 def test_principal_frame_of_an_ellipsoid():
     from neat_amd import mesh
     Q, centre = rotation(4), np.array([0.04, -0.03, 0.02])

@@ -127,6 +127,30 @@ def test_two_runs_give_the_same_bytes():
     assert torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], b[1])
 
 
+def test_tile_offsets_past_1024_tiles():
+    """129 x 129 x 127 nodes are 1032 tiles of 2048, so the one workgroup of 1024 that turns the tile counts into offsets (mesh_scan_kernel)
+    takes a second round with a carry; every other comparison of this file stays within one round and 512^3 checks the surface alone.
+    The float64 restatement needs about 7 s on the host at this size, so the extraction is judged by what a wrong offset breaks: the
+    vertex count is numpy's count of the edges whose end nodes differ in sign, the surface is closed and a sphere."""
+    from neat_amd import mesh
+    shape = (129, 129, 127)
+    assert shape[0] * shape[1] * shape[2] > 1024 * TILE
+    g = field(shape, "sphere", seed=1)
+    verts, faces = mesh.extract(torch.tensor(g).cuda(), -1.5, 1.5)
+    inside = g < 0
+    edges = 0
+    for c in range(1, 8):                                            # the seven edge classes: offsets (dx, dy, dz) = the bits of c
+        dx, dy, dz = (c >> 2) & 1, (c >> 1) & 1, c & 1
+        a = inside[:shape[0] - dx, :shape[1] - dy, :shape[2] - dz]
+        b = inside[dx:, dy:, dz:]
+        edges += int((a != b).sum())
+    assert verts.shape[0] == edges and bool(torch.isfinite(verts).all())
+    f = faces.cpu().numpy()
+    ne, ok, _ = M.edge_report(f)
+    assert ok.all() and verts.shape[0] - ne + f.shape[0] == 2
+    assert f.min() == 0 and f.max() == verts.shape[0] - 1
+
+
 def test_sphere_at_512():
     from neat_amd import _lib, mesh
     dev = torch.device("cuda:0")

@@ -121,7 +121,8 @@ def test_line_match_vs_torch(n, m):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,m,seed", [(1, 1, 0), (300, 7, 1), (5000, 40, 2), (70000, 300, 3)])
+@pytest.mark.parametrize("n,m,seed", [(1, 1, 0), (300, 7, 1), (5000, 40, 2), (70000, 300, 3),
+                                      (6000, 1500, 4)])      # 1500 labels: the scan over the labels (one workgroup of 1024) carries into a second round
 def test_group_deterministic_and_vs_float64(n, m, seed):
     from neat_amd import ops
     dev = torch.device("cuda:0")

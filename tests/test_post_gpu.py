@@ -118,6 +118,25 @@ def test_fuse_shapes(n, m, V):
 
 
 @pytest.mark.gpu
+def test_fuse_ranks_past_one_scan_round():
+    """Views of 1300 and 1100 detections, a few hundred of them matched at random positions: the workgroup of 1024 that ranks a view's
+    matched detections (post_rank_kernel) takes a second round, and detections past index 1024 carry the count of the first."""
+    for seed in range(20):
+        lines, views = fuse_scene(600, [1300, 1100], 31 + 7919 * seed)
+        if min(F.fuse(lines, views)["margin"], F.fuse(lines, views, by_label=True)["margin"]) > 1e-4:
+            break
+    else:
+        raise AssertionError("no clear draw")
+    for view in views:
+        _, d1, d2 = F.view_costs(lines, view)
+        idx, cost, bad, _ = F._best(d1, d2, 10.0)
+        matched = np.unique(idx[~bad & (cost < 10.0)])
+        assert (matched >= 1024).sum() >= 10 and (matched < 1024).sum() >= 100
+    for by_label in (False, True):
+        check_fuse(lines, views, by_label)
+
+
+@pytest.mark.gpu
 def test_fuse_cases():
     """A duplicated detection (lowest index wins), a NaN line, an empty view between two others, a line matched nowhere, both modes."""
     lines, views = fuse_scene(40, [30, 0, 30], 5)

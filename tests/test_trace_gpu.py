@@ -102,6 +102,25 @@ def test_ray_counts_and_determinism(R):
         assert parts["evals"] == g["evals"] and {r0 for r0, _ in parts["lists"]} == set(range(0, R, 100))
 
 
+def test_scan_carry_past_1024_tiles_equals_two_single_round_halves():
+    """262 145 rays are 1025 workgroups of 256, so the one workgroup of 1024 that turns their counts into offsets (trace_scan_kernel) takes
+    a second round with a carry, which no other test here reaches.  Traced as two halves (513 and 512 workgroups: one round each, the path
+    judged against float64 above) every ray must come out with the same bits."""
+    R = 1024 * 256 + 1
+    o, d = T.scene("sphere", n=R, seed=3)
+    o[-1], d[-1] = (0.0, 0.0, -2.0), (0.0, 0.0, 1.0)                      # the one ray of the last workgroup is alive: it hits head-on
+    g = _run("sphere", o, d)
+    parts = _run("sphere", o, d, chunk=R // 2 + 1)
+    assert {r0 for r0, _ in parts["lists"]} == {0, R // 2 + 1} and {r0 for r0, _ in g["lists"]} == {0}
+    for k in ("depth", "state", "steps", "points"):
+        assert g[k].tobytes() == parts[k].tobytes(), k
+    assert g["evals"] == parts["evals"] == int(g["steps"].sum())
+    assert g["lists"][0][1][-1] == R - 1 and g["state"][-1] == T.HIT and abs(float(g["depth"][-1]) - 1.5) < 1e-3
+    assert (g["state"] == T.HIT).sum() > R // 4 and (g["state"] == T.MISS).sum() > R // 4
+    for _, ids in g["lists"]:
+        assert (np.diff(ids) > 0).all()                                   # ray order across the carry, no ray twice
+
+
 def test_state_cases():
     n = 300
     o, d = T.fan(n, 3, ((0.0, 0.3),))
