@@ -694,6 +694,32 @@ int neat_raycast_build(const double* verts, int nv, const int* faces, int nf, vo
 int neat_raycast_cast(const void* bvh, int nf, const float* origins, const float* dirs, const float* t_min, const float* t_max, int R, int any_hit,
                       float* t, int* tri, float* uv, unsigned* counts, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): 2-D line segments of the views (neat_amd/detect.py), the
+ * files <scene>/<line_detector>/<image>.json that the datasets read.  An a-contrario detector of the LSD family over the line-support
+ * regions of Burns, Hanson and Riseman; the rule: DESIGN 3j and neat_amd/csrc/kernels_detect.hpp, restated in float64 by
+ * tests/detect_f64.py.  Asynchronous on the stream, no allocation, no read-back; integer atomics only and fixed-order float64 sums:
+ * two runs give the same bytes.  Bad arguments return -1 before any launch.
+ *
+ * neat_detect_label : codes uint8 [V,h,w] (255 = unused, any other value a code) -> labels int32 [V,h,w]: the smallest linear index
+ *   y w + x of the pixel's 8-connected component of equal code within its picture, -1 for unused.  The labelling step of the detector
+ *   on its own.  Refused: a negative count, h w or V h w beyond 2^31 - 1.
+ * neat_detect_scratch_bytes : the workspace of neat_detect_lines (256-byte aligned, caller-owned); 0 when refused: V < 0, H or W below
+ *   2 with V > 0 or above 32768, scale outside (0, 1], min_reg < 1, more than 2^31 - 1 map elements.  The grey picture float64
+ *   [V, Hs, Ws], Hs = ceil(scale H), is its first region, at offset 0.
+ * neat_detect_lines : images uint8 [V,H,W,channels], channels 3 (grey = (77 R + 150 G + 29 B + 128) >> 8) or 1.  scale < 1: a sampled
+ *   Gaussian from the host's tables taps_x [Ws][ntaps], taps_y [Hs][ntaps] (ntaps odd; the first tap of output i at source
+ *   floor(i / scale + 0.5) - (ntaps - 1) / 2, sources clamped); scale = 1: ntaps = 0 and no tables.  The host's constants: rho2 =
+ *   (q / sin tau)^2 the squared gradient threshold, c1 = sqrt(2) - 1, cos_tau, density (0.7), logNT = 2.5 (log10 Ws + log10 Hs),
+ *   p = tau / 180 deg, min_reg = floor(-logNT / log10 p) + 1.  Outputs, `cap` rows each with cap >= 2 V ((Hs - 1) (Ws - 1) / min_reg) + 1:
+ *   lines float64 [cap,4] (x1 y1 x2 y2 in the input picture's integer-pixel-centre coordinates), width, nfa (-log10 NFA) float64 [cap],
+ *   n, k int32 [cap] (positions in the rectangle, aligned ones), in ascending (view, partition, label) order; offsets int32 [V + 1]:
+ *   the lines of view v are rows offsets[v] .. offsets[v + 1].  V = 0 or a picture without a gradient grid: offsets all zero. */
+int neat_detect_label(const unsigned char* codes, int V, int h, int w, int* labels, void* stream);
+size_t neat_detect_scratch_bytes(int V, int H, int W, double scale, int min_reg);
+int neat_detect_lines(const unsigned char* images, int V, int H, int W, int channels, double scale, const double* taps_x, const double* taps_y,
+                      int ntaps, double rho2, double c1, double cos_tau, double density, double logNT, double p, int min_reg, void* ws, int cap,
+                      double* lines, double* width, double* nfa, int* n, int* k, int* offsets, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

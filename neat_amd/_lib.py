@@ -193,6 +193,10 @@ _SIGNATURES = {
                                              ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, c_fp]),
     "neat_post_snap_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
     "neat_post_snap": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_detect_label": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
+    "neat_detect_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
+    "neat_detect_lines": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_fp, c_fp, ctypes.c_int]
+                          + [ctypes.c_double] * 6 + [ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 7),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

@@ -15,6 +15,7 @@
 #include "kernels_trace.hpp"
 #include "kernels_post.hpp"
 #include "kernels_raycast.hpp"
+#include "kernels_detect.hpp"
 #include "ws_layout.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
@@ -1206,6 +1207,64 @@ int neat_raycast_cast(const void* bvh, int nf, const float* origins, const float
     hipLaunchKernelGGL(raycast_cast_kernel<false>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, (const float*)w.nodes,
                          (const double*)w.tris, nf, w.L, origins, dirs, t_min, t_max,
                        R, t, tri, uv, counts);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: 2-D line-segment detection in the views (kernels_detect.hpp) ------------------------------------------------------------
+static int detect_label_launch(const unsigned char* code, long long maps, int h, int w, int* label, int* size, int* votes, int* xmin, int* xmax,
+                               int* ymax, hipStream_t st) {
+  const long long tiles = (long long)((h + DET_TILE - 1) / DET_TILE) * ((w + DET_TILE - 1) / DET_TILE), el = maps * h * w;
+  const dim3 per_element((unsigned)((el + DET_WG - 1) / DET_WG));
+  hipLaunchKernelGGL(detect_label_tile_kernel, dim3((unsigned)(maps * tiles)), dim3(DET_WG), 0, st, code, h, w, label, size, votes, xmin, xmax, ymax);
+  hipLaunchKernelGGL(detect_label_merge_kernel, per_element, dim3(DET_WG), 0, st, code, (int)maps, h, w, label);
+  hipLaunchKernelGGL(detect_label_flatten_kernel, per_element, dim3(DET_WG), 0, st, (int)maps, h, w, label, size, xmin, xmax, ymax);
+  return (int)hipGetLastError();
+}
+
+int neat_detect_label(const unsigned char* codes, int V, int h, int w, int* labels, void* stream) {
+  if (!detect_maps_ok(V, h, w, DET_TILE)) return -1;
+  if ((long long)V * h * w == 0) return 0;
+  if (!codes || !labels) return -1;
+  return detect_label_launch(codes, V, h, w, labels, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+size_t neat_detect_scratch_bytes(int V, int H, int W, double scale, int min_reg) {
+  DetectWs d;
+  return detect_layout(nullptr, V, H, W, scale, min_reg, DET_TILE, DET_WG, &d) ? d.total : 0;
+}
+
+int neat_detect_lines(const unsigned char* images, int V, int H, int W, int channels, double scale, const double* taps_x, const double* taps_y,
+                      int ntaps, double rho2, double c1, double cos_tau, double density, double logNT, double p, int min_reg, void* ws, int cap,
+                      double* lines, double* width, double* nfa, int* n, int* k, int* offsets, void* stream) {
+  DetectWs d;
+  if ((channels != 1 && channels != 3) || !offsets || ntaps < 0 || (ntaps > 0 && ntaps % 2 == 0) || !(rho2 > 0.0) || !(c1 > 0.0) ||
+      !(p > 0.0 && p < 1.0) || !std::isfinite(cos_tau) || !std::isfinite(density) || !std::isfinite(logNT) ||
+      !detect_layout(ws, V, H, W, scale, min_reg, DET_TILE, DET_WG, &d))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (d.el == 0) return (int)hipMemsetAsync(offsets, 0, ((size_t)V + 1) * sizeof(int), st);
+  if (!images || !ws || ((uintptr_t)ws & 255) || cap < d.cap || !lines || !width || !nfa || !n || !k) return -1;
+  if ((scale < 1.0) != (ntaps > 0) || (ntaps > 0 && (!taps_x || !taps_y))) return -1;
+  const DetectConsts K = {cos_tau, density, logNT, p};
+  const int hw = d.h * d.w;
+  const dim3 per_pixel((unsigned)((d.px + DET_WG - 1) / DET_WG)), per_pos((unsigned)((d.el + DET_WG - 1) / DET_WG)), per_element((unsigned)d.blocks);
+  hipLaunchKernelGGL(detect_grey_kernel, per_pixel, dim3(DET_WG), 0, st, images, V, H, W, channels, scale, taps_x, taps_y, ntaps, d.Hs, d.Ws, d.grey);
+  hipLaunchKernelGGL(detect_gradient_kernel, per_pos, dim3(DET_WG), 0, st, (const double*)d.grey, V, d.Hs, d.Ws, rho2, c1, d.gx, d.gy, d.code);
+  NEAT_CHECK(hipGetLastError());
+  const int e = detect_label_launch(d.code, 2ll * V, d.h, d.w, d.label, d.size, d.votes, d.xmin, d.xmax, d.ymax, st);
+  if (e != 0) return e;
+  hipLaunchKernelGGL(detect_vote_kernel, per_pos, dim3(DET_WG), 0, st, V, hw, (const int*)d.label, (const int*)d.size, d.votes);
+  hipLaunchKernelGGL(detect_cand_count_kernel, per_element, dim3(DET_WG), 0, st, 2 * d.el, hw, min_reg, (const int*)d.label, (const int*)d.size,
+                     (const int*)d.votes, d.bcnt);
+  hipLaunchKernelGGL(detect_cand_scan_kernel, dim3(1), dim3(1024), 0, st, d.blocks, (const int*)d.bcnt, d.boff, d.cap, d.counters);
+  hipLaunchKernelGGL(detect_cand_emit_kernel, per_element, dim3(DET_WG), 0, st, 2 * d.el, hw, min_reg, (const int*)d.label, (const int*)d.size,
+                     (const int*)d.votes, (const int*)d.boff, d.cap, d.cand);
+  NEAT_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(detect_region_kernel, dim3((unsigned)((d.cap + DET_WAVES - 1) / DET_WAVES)), dim3(DET_WG), 0, st, (const int*)d.cand,
+                     (const int*)d.counters, d.h, d.w, scale, K, (const unsigned char*)d.code, (const int*)d.label, (const int*)d.xmin,
+                     (const int*)d.xmax, (const int*)d.ymax, (const double*)d.gx, (const double*)d.gy, d.rec, d.n, d.k, d.keep);
+  hipLaunchKernelGGL(detect_output_kernel, dim3(1), dim3(1024), 0, st, (const int*)d.cand, d.counters, d.cap, V, hw, (const double*)d.rec,
+                     (const int*)d.n, (const int*)d.k, (const int*)d.keep, d.idx, lines, width, nfa, n, k, offsets);
   return (int)hipGetLastError();
 }
 

@@ -306,4 +306,57 @@ inline bool raycast_layout(void* bvh, void* ws, int nf, int wg, int tri_stride, 
   return true;
 }
 
+// ---- 2-D line-segment detection (kernels_detect.hpp).  The labelling alone: nothing but the caller's label map.  The detector, over
+// px = V Hs Ws grey pixels (Hs = ceil(scale H)), el = V h w gradient positions (h = Hs - 1) and 2 el map elements (view-major, then
+// partition): grey [px] first, at offset 0 (detect.py reads it back for the tests), gx, gy [el] | codes byte [2 el] | label, size, votes,
+// xmin, xmax, ymax int [2 el] each | per-workgroup counts and offsets [blocks], blocks = ceil(2 el / wg) | counters int [2] (candidates,
+// lines) | the candidates: element int [cap], 6 doubles, n, k, keep each [cap] | idx int [cap].  cap = 2 V (h w / min_reg) + 1: a
+// candidate region has min_reg pixels at least and the regions of a map are disjoint.
+inline bool detect_scale_ok(double scale) { return scale > 0.0 && scale <= 1.0; }
+inline int detect_scaled(int size, double scale) {      // ceil(scale size) in float64, as tests/detect_f64.py
+  const double s = scale * (double)size;
+  long long c = (long long)s;
+  if ((double)c < s) ++c;
+  return (int)c;
+}
+inline bool detect_maps_ok(long long maps, long long h, long long w, int tile) {
+  if (maps < 0 || h < 0 || w < 0) return false;
+  const long long tiles = ((h + tile - 1) / tile) * ((w + tile - 1) / tile);
+  return h * w <= 0x7fffffffLL && maps * h * w <= 0x7fffffffLL && maps * tiles <= 0x7fffffffLL;
+}
+struct DetectWs {
+  int Hs, Ws, h, w, blocks, cap;
+  long long px, el;
+  double *grey, *gx, *gy; unsigned char* code; int *label, *size, *votes, *xmin, *xmax, *ymax, *bcnt, *boff, *counters;
+  int* cand; double* rec; int *n, *k, *keep, *idx;
+  size_t total;
+};
+inline bool detect_layout(void* ws, int V, int H, int W, double scale, int min_reg, int tile, int wg, DetectWs* d) {
+  if (V < 0 || !detect_scale_ok(scale) || min_reg < 1 || (V > 0 && (H < 2 || W < 2)) || H > 32768 || W > 32768) return false;
+  d->Hs = V > 0 ? detect_scaled(H, scale) : 0;
+  d->Ws = V > 0 ? detect_scaled(W, scale) : 0;
+  d->h = d->Hs > 1 ? d->Hs - 1 : 0;
+  d->w = d->Ws > 1 ? d->Ws - 1 : 0;
+  if (!detect_maps_ok(2ll * V, d->h, d->w, tile) || (long long)V * d->Hs * d->Ws > 0x7fffffffLL) return false;
+  d->px = (long long)V * d->Hs * d->Ws;
+  d->el = (long long)V * d->h * d->w;
+  d->blocks = (int)((2 * d->el + wg - 1) / wg);
+  d->cap = (int)(2ll * V * (((long long)d->h * d->w) / min_reg) + 1);
+  const size_t el = (size_t)d->el, cap = (size_t)d->cap;
+  WsCarver c(ws);
+  d->grey = c.take<double>((size_t)d->px);
+  d->gx = c.take<double>(el);
+  d->gy = c.take<double>(el);
+  d->code = c.take<unsigned char>(2 * el);
+  for (int** p : {&d->label, &d->size, &d->votes, &d->xmin, &d->xmax, &d->ymax}) *p = c.take<int>(2 * el);
+  d->bcnt = c.take<int>((size_t)d->blocks);
+  d->boff = c.take<int>((size_t)d->blocks);
+  d->counters = c.take<int>(2);
+  d->cand = c.take<int>(cap);
+  d->rec = c.take<double>(6 * cap);
+  for (int** p : {&d->n, &d->k, &d->keep, &d->idx}) *p = c.take<int>(cap);
+  d->total = c.end();
+  return true;
+}
+
 }  // namespace neat

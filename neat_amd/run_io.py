@@ -109,6 +109,28 @@ def dataset_views(dataset):
     return segments, Ks, poses
 
 
+def scene_images(instance_dir):
+    """The views of a scene directory as the dataset classes list them: `images/` (BlenderDataset) or `image/` (SceneDataset), the
+    sorted *.png / *.jpg / *.JPEG / *.JPG files without "mask" in their path."""
+    for sub in ("images", "image"):
+        folder = os.path.join(instance_dir, sub)
+        if os.path.isdir(folder):
+            names = [n for n in sorted(os.listdir(folder)) if os.path.splitext(n)[1] in (".png", ".jpg", ".JPEG", ".JPG")]
+            return [p for p in (os.path.join(folder, n) for n in names) if "mask" not in p]
+    raise FileNotFoundError(f"{instance_dir}: neither images/ nor image/")
+
+
+def write_wireframe_json(path, wireframe, extra=None):
+    """A WireframeGraph as the <scene>/<line_detector>/<image>.json the dataset classes read (`extra`: further keys, which load_json ignores)."""
+    d = wireframe.jsonize()
+    d.update(extra or {})
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + ".tmp"
+    with open(tmp, "w") as fh:
+        json.dump(d, fh)
+    os.replace(tmp, path)
+
+
 def load_cam_json(path):
     """The cam.json neat_amd.show writes, a JSON list of 4 x 4 world-to-camera matrices -> float64 [F,4,4]."""
     with open(path) as fh:

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "kernels_detect.hpp"
 #include "kernels_evalmesh.hpp"
 #include "kernels_frame.hpp"
 #include "kernels_mesh.hpp"
@@ -261,7 +262,37 @@ int main() {
     }
   }
 
+  // ---- line-segment detection: pictures around the labelling's tile (gradient grids of 15, 16, 17) and one scaled down
+  {
+    const int shapes[][3] = {{0, 0, 0}, {1, 2, 2}, {1, 16, 16}, {1, 17, 17}, {3, 18, 33}, {2, 97, 131}, {8, 128, 128}};
+    for (const auto& sh : shapes)
+      for (double scale : {1.0, 0.8})
+        for (int min_reg : {1, 12}) {
+          CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+            DetectWs d;
+            if (!detect_layout(b, sh[0], sh[1], sh[2], scale, min_reg, DET_TILE, DET_WG, &d)) return false;
+            const size_t el = (size_t)d.el, cap = (size_t)d.cap;
+            if (d.h != (d.Hs > 1 ? d.Hs - 1 : 0) || d.el != (long long)sh[0] * d.h * d.w || (long long)d.blocks * DET_WG < 2 * d.el) return false;
+            if (ws_offset(b, d.grey) != 0 || cap < 1 || (long long)cap * min_reg < 2 * d.el - 2ll * sh[0] * (min_reg - 1)) return false;
+            r = {{d.grey, (size_t)d.px * 8, 256}, {d.gx, el * 8, 256}, {d.gy, el * 8, 256}, {d.code, 2 * el, 256}, {d.label, 8 * el, 256},
+                 {d.size, 8 * el, 256}, {d.votes, 8 * el, 256}, {d.xmin, 8 * el, 256}, {d.xmax, 8 * el, 256}, {d.ymax, 8 * el, 256},
+                 {d.bcnt, (size_t)d.blocks * 4, 256}, {d.boff, (size_t)d.blocks * 4, 256}, {d.counters, 8, 256}, {d.cand, cap * 4, 256},
+                 {d.rec, cap * 48, 256}, {d.n, cap * 4, 256}, {d.k, cap * 4, 256}, {d.keep, cap * 4, 256}, {d.idx, cap * 4, 256}};
+            t = d.total;
+            return true;
+          }));
+        }
+    CHECK(detect_scaled(128, 0.8) == 103 && detect_scaled(5, 0.8) == 4 && detect_scaled(10, 1.0) == 10 && detect_scaled(2, 0.3) == 1);
+  }
+
   // the large values: measured only
+  CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+    DetectWs d;
+    if (!detect_layout(b, 64, 1200, 1600, 1.0, 18, DET_TILE, DET_WG, &d)) return false;
+    r = {{d.grey, (size_t)d.px * 8, 256}, {d.label, (size_t)d.el * 8, 256}, {d.idx, (size_t)d.cap * 4, 256}};
+    t = d.total;
+    return true;
+  }));
   CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
     TraceWs w;
     if (!(t = trace_layout(b, TRACE_MAX_RAYS, TRACE_WG, &w))) return false;
@@ -323,6 +354,13 @@ int main() {
   CHECK(!trace_layout(nullptr, 0, TRACE_WG, &wtr) && !trace_layout(nullptr, -1, TRACE_WG, &wtr) && !trace_layout(nullptr, TRACE_MAX_RAYS + 1, TRACE_WG, &wtr));
   RaycastWs wrc;
   CHECK(!raycast_layout(nullptr, nullptr, -1, RC_WG, RC_TRI_STRIDE, &wrc) && !raycast_layout(nullptr, nullptr, RC_MAX_FACES + 1, RC_WG, RC_TRI_STRIDE, &wrc));
+  DetectWs wd;
+  CHECK(!detect_layout(nullptr, -1, 16, 16, 1.0, 5, DET_TILE, DET_WG, &wd) && !detect_layout(nullptr, 1, 1, 16, 1.0, 5, DET_TILE, DET_WG, &wd) &&
+        !detect_layout(nullptr, 1, 16, 1, 1.0, 5, DET_TILE, DET_WG, &wd) && !detect_layout(nullptr, 1, 16, 16, 0.0, 5, DET_TILE, DET_WG, &wd) &&
+        !detect_layout(nullptr, 1, 16, 16, 1.5, 5, DET_TILE, DET_WG, &wd) && !detect_layout(nullptr, 1, 16, 16, 1.0, 0, DET_TILE, DET_WG, &wd) &&
+        !detect_layout(nullptr, 1, 32769, 16, 1.0, 5, DET_TILE, DET_WG, &wd) && !detect_layout(nullptr, 4096, 32768, 32768, 1.0, 5, DET_TILE, DET_WG, &wd));
+  CHECK(detect_maps_ok(3, 129, 129, DET_TILE) && !detect_maps_ok(-1, 4, 4, DET_TILE) && !detect_maps_ok(3, 65536, 65536, DET_TILE) &&
+        !detect_maps_ok(70000, 32768, 1, DET_TILE));
   // the two fixed blocks of partial results
   double* pd;
   float* pf;
