@@ -720,6 +720,37 @@ int neat_detect_lines(const unsigned char* images, int V, int H, int W, int chan
                       int ntaps, double rho2, double c1, double cos_tau, double density, double logNT, double p, int min_reg, void* ws, int cap,
                       double* lines, double* width, double* nfa, int* n, int* k, int* offsets, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): 3-D line segments triangulated from the views' 2-D segments
+ * (neat_amd/triangulate.py), the baseline the reference takes from Line3D++ files.  The rule: DESIGN 3k and
+ * neat_amd/csrc/kernels_triangulate.hpp, restated in float64 by tests/triangulate_f64.py.  Float64 without contraction, counted /
+ * scanned / filled lists, a union-find whose roots are the smallest member: two runs give the same bytes.  Asynchronous on the stream,
+ * no allocation, no read-back.  Bad arguments return -1 before any launch.
+ *
+ * Shared inputs: segments float64 [S,4] = x1 y1 x2 y2 in pixels, all views' in (view, index) order; segoff int32 [V+1] the views' first
+ * rows; nmax = the most segments of one view; nb int32 [V,M] the M nearest other views of a view, nearest first (M < V, or M = 0);
+ * cam float64 [V,48] = K^-1 [9], R [9] world -> camera, t [3], K [9], P = K [R|t] [12], C [3], 3 unused, all row-major.
+ * Refused: a negative count, V > 65535, 10 S, S M or V M ceil(nmax / 256) beyond 2^31 - 1, M >= V > 0, nmax > S, H beyond 2^30 - 1.
+ *
+ * neat_tri_scratch_bytes : the workspace (256-byte aligned, caller-owned) of the three calls, which share it; 0 when refused.
+ * neat_tri_count : the per-segment constants, then the pair test over every (segment, segment of a neighbour) once, counting.
+ *   cos_min = cos(angle_min), overlap_min as in the rule.  view int32 [S] = the segment's view; hoff int32 [S+1] = the segments' first
+ *   hypotheses; *total (device, 64-bit) = the number of hypotheses H, which the host reads to allocate the list.
+ * neat_tri_fill : the same test again, writing the H hypotheses in (view, segment, slot, partner) order: hyp_m int32 [H] the slot,
+ *   hyp_j int32 [H] the partner's index in its view, hyp_s float64 [H,2] the depths s_1, s_2.  Same arguments as the count.
+ * neat_tri_lines : score, link and lines.  Per segment: estimate float64 [S,2,3] (zeros without a hypothesis), score float64 [S],
+ *   kept int32 [S] (score >= min_score), label int32 [S] (the component's lowest kept segment, -1 when not kept), members int32 [S]
+ *   (the segment's line, -1 for none).  Per line, in label order: lines3d float64 [S,2,3], views int32 [S], support float64 [S]
+ *   (capacity S each), *n_lines (device) of them. */
+size_t neat_tri_scratch_bytes(int V, int S, int M, int nmax);
+int neat_tri_count(const double* segments, const int* segoff, int V, int S, int nmax, const int* nb, int M, const double* cam, double cos_min,
+                   double overlap_min, void* ws, int* view, int* hoff, long long* total, void* stream);
+int neat_tri_fill(const int* segoff, int V, int S, int nmax, const int* nb, int M, const double* cam, double cos_min, double overlap_min,
+                  void* ws, long long H, int* hyp_m, int* hyp_j, double* hyp_s, void* stream);
+int neat_tri_lines(const int* segoff, int V, int S, int nmax, const int* nb, int M, const double* cam, void* ws, const int* view, const int* hoff,
+                   long long H, const int* hyp_m, const int* hyp_j, const double* hyp_s, double sigma_px, double min_score, int min_views,
+                   double* estimate, double* score, int* kept, int* label, int* members, double* lines3d, int* views, double* support,
+                   int* n_lines, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

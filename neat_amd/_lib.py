@@ -197,6 +197,13 @@ _SIGNATURES = {
     "neat_detect_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
     "neat_detect_lines": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_fp, c_fp, ctypes.c_int]
                           + [ctypes.c_double] * 6 + [ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 7),
+    "neat_tri_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "neat_tri_count": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_double,
+                                      ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "neat_tri_fill": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_double, ctypes.c_double,
+                                     c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp, c_fp]),
+    "neat_tri_lines": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_longlong,
+                                      c_fp, c_fp, c_fp, ctypes.c_double, ctypes.c_double, ctypes.c_int] + [c_fp] * 10),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

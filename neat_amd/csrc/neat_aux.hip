@@ -16,6 +16,7 @@
 #include "kernels_post.hpp"
 #include "kernels_raycast.hpp"
 #include "kernels_detect.hpp"
+#include "kernels_triangulate.hpp"
 #include "ws_layout.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
@@ -1265,6 +1266,74 @@ int neat_detect_lines(const unsigned char* images, int V, int H, int W, int chan
                      (const int*)d.xmax, (const int*)d.ymax, (const double*)d.gx, (const double*)d.gy, d.rec, d.n, d.k, d.keep);
   hipLaunchKernelGGL(detect_output_kernel, dim3(1), dim3(1024), 0, st, (const int*)d.cand, d.counters, d.cap, V, hw, (const double*)d.rec,
                      (const int*)d.n, (const int*)d.k, (const int*)d.keep, d.idx, lines, width, nfa, n, k, offsets);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: 3-D segments triangulated from the views' 2-D segments (kernels_triangulate.hpp) ---------------------------------------
+size_t neat_tri_scratch_bytes(int V, int S, int M, int nmax) {
+  TriWs w;
+  return tri_layout(nullptr, V, S, M, nmax, TRI_WG, &w) ? w.total : 0;
+}
+
+static bool tri_thresholds_ok(double cos_min, double overlap_min) { return std::isfinite(cos_min) && std::isfinite(overlap_min); }
+
+int neat_tri_count(const double* segments, const int* segoff, int V, int S, int nmax, const int* nb, int M, const double* cam, double cos_min,
+                   double overlap_min, void* ws, int* view, int* hoff, long long* total, void* stream) {
+  TriWs w;
+  if (!tri_thresholds_ok(cos_min, overlap_min) || !tri_layout(ws, V, S, M, nmax, TRI_WG, &w) || !hoff || !total) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (S > 0 && (!segments || !segoff || !cam || !ws || ((uintptr_t)ws & 255) || !view || (M > 0 && !nb))) return -1;
+  if (S > 0) hipLaunchKernelGGL(tri_segment_kernel, grid1(S, TRI_WG), dim3(TRI_WG), 0, st, segments, segoff, V, S, cam, w.sega, w.segb, view);
+  if (S == 0 || M == 0 || w.tiles == 0) {
+    NEAT_CHECK(hipMemsetAsync(hoff, 0, ((size_t)S + 1) * sizeof(int), st));
+    NEAT_CHECK(hipMemsetAsync(total, 0, sizeof(long long), st));
+    return (int)hipGetLastError();
+  }
+  hipLaunchKernelGGL(tri_match_kernel<false>, dim3((unsigned)((long long)V * M * w.tiles)), dim3(TRI_WG), 0, st, segoff, nb, M, w.tiles, cam,
+                     (const double*)w.sega, (const double*)w.segb, cos_min, overlap_min, w.cnt, (const int*)nullptr, 0, (int*)nullptr,
+                     (int*)nullptr, (double*)nullptr);
+  hipLaunchKernelGGL(tri_scan_kernel, dim3(1), dim3(1024), 0, st, S, M, (const int*)w.cnt, w.off, hoff, total);
+  return (int)hipGetLastError();
+}
+
+int neat_tri_fill(const int* segoff, int V, int S, int nmax, const int* nb, int M, const double* cam, double cos_min, double overlap_min,
+                  void* ws, long long H, int* hyp_m, int* hyp_j, double* hyp_s, void* stream) {
+  TriWs w;
+  if (!tri_thresholds_ok(cos_min, overlap_min) || !tri_layout(ws, V, S, M, nmax, TRI_WG, &w) || H < 0 || H > 0x7fffffffLL / 2) return -1;
+  if (H == 0) return 0;
+  if (S == 0 || M == 0 || !segoff || !nb || !cam || !ws || ((uintptr_t)ws & 255) || !hyp_m || !hyp_j || !hyp_s) return -1;
+  hipLaunchKernelGGL(tri_match_kernel<true>, dim3((unsigned)((long long)V * M * w.tiles)), dim3(TRI_WG), 0, (hipStream_t)stream, segoff, nb, M,
+                     w.tiles, cam, (const double*)w.sega, (const double*)w.segb, cos_min, overlap_min, (int*)nullptr, (const int*)w.off, (int)H,
+                     hyp_m, hyp_j, hyp_s);
+  return (int)hipGetLastError();
+}
+
+int neat_tri_lines(const int* segoff, int V, int S, int nmax, const int* nb, int M, const double* cam, void* ws, const int* view, const int* hoff,
+                   long long H, const int* hyp_m, const int* hyp_j, const double* hyp_s, double sigma_px, double min_score, int min_views,
+                   double* estimate, double* score, int* kept, int* label, int* members, double* lines3d, int* views, double* support,
+                   int* n_lines, void* stream) {
+  TriWs w;
+  if (!(sigma_px > 0.0) || !std::isfinite(sigma_px) || !std::isfinite(min_score) || min_views < 0 || !n_lines || H < 0 ||
+      H > 0x7fffffffLL / 2 || !tri_layout(ws, V, S, M, nmax, TRI_WG, &w))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (S == 0) return (int)hipMemsetAsync(n_lines, 0, sizeof(int), st);
+  if (!segoff || !cam || !ws || ((uintptr_t)ws & 255) || !view || !hoff || !estimate || !score || !kept || !label || !members || !lines3d ||
+      !views || !support || (H > 0 && (!nb || !hyp_m || !hyp_j || !hyp_s)))
+    return -1;
+  const dim3 per_seg(grid1(S, TRI_WG)), per_wave(grid1(S, TRI_WAVES));
+  hipLaunchKernelGGL(tri_score_kernel, per_wave, dim3(TRI_WG), 0, st, S, view, hoff, hyp_m, hyp_s, cam, (const double*)w.sega, sigma_px,
+                     min_score, w.best, estimate, score, w.radius, kept);
+  hipLaunchKernelGGL(tri_link_init_kernel, per_seg, dim3(TRI_WG), 0, st, S, (const int*)kept, label, w.last);
+  NEAT_CHECK(hipGetLastError());
+  if (H > 0)
+    hipLaunchKernelGGL(tri_link_kernel, per_wave, dim3(TRI_WG), 0, st, S, M, view, segoff, nb, hoff, hyp_m, hyp_j, (const int*)kept,
+                       (const double*)estimate, (const double*)w.radius, label);
+  hipLaunchKernelGGL(tri_flatten_kernel, per_seg, dim3(TRI_WG), 0, st, S, label, w.last);
+  hipLaunchKernelGGL(tri_component_kernel, per_wave, dim3(TRI_WG), 0, st, S, (const int*)label, (const int*)w.last, view, (const double*)score,
+                     (const double*)estimate, w.nviews, w.axis, w.tau);
+  hipLaunchKernelGGL(tri_output_kernel, dim3(1), dim3(1024), 0, st, S, min_views, (const int*)label, (const int*)w.nviews, (const int*)w.axis,
+                     (const double*)w.tau, (const double*)estimate, (const double*)score, w.idx, members, lines3d, views, support, n_lines);
   return (int)hipGetLastError();
 }
 

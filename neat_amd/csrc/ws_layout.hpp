@@ -359,4 +359,38 @@ inline bool detect_layout(void* ws, int V, int H, int W, double scale, int min_r
   return true;
 }
 
+// ---- triangulation of the views' 2-D segments (kernels_triangulate.hpp) over V views, S segments in all (nmax in one view at most) and
+// M neighbour slots.  Every region is bounded by S; the hypothesis list, whose length only the count pass knows, is the caller's.
+// sega [9 S] (d_1, d_2, n_a), segb [10 S] (pi, q_1, u, u.u, |pi_xyz|) | cnt, off [S M] (hypotheses per (segment, slot), their offsets) |
+// best [S] (the picked hypothesis) | radius [S] | per component, at its root: nviews, axis, last [S] int, tau [2 S] | idx [S] (the kept
+// roots in order)
+constexpr int TRI_MAX_VIEWS = 65535;
+inline bool tri_counts_ok(long long V, long long S, long long M, long long nmax, int tile) {
+  if (V < 0 || S < 0 || M < 0 || nmax < 0 || V > TRI_MAX_VIEWS || nmax > S || S > 0x7fffffffLL / 10) return false;
+  if (M > 0 && (M >= V || S > 0x7fffffffLL / M)) return false;
+  return V * M * ((nmax + tile - 1) / tile) <= 0x7fffffffLL;
+}
+struct TriWs {
+  int tiles;                // tiles of one view in the pair launch: ceil(nmax / tile)
+  double *sega, *segb; int *cnt, *off, *best; double* radius; int *nviews, *axis, *last; double* tau; int* idx;
+  size_t total;
+};
+inline bool tri_layout(void* ws, int V, int S, int M, int nmax, int tile, TriWs* w) {
+  if (!tri_counts_ok(V, S, M, nmax, tile)) return false;
+  w->tiles = (nmax + tile - 1) / tile;
+  const size_t s = (size_t)S;
+  WsCarver c(ws);
+  w->sega = c.take<double>(9 * s);
+  w->segb = c.take<double>(10 * s);
+  w->cnt = c.take<int>(s * (size_t)M);
+  w->off = c.take<int>(s * (size_t)M);
+  w->best = c.take<int>(s);
+  w->radius = c.take<double>(s);
+  for (int** p : {&w->nviews, &w->axis, &w->last}) *p = c.take<int>(s);
+  w->tau = c.take<double>(2 * s);
+  w->idx = c.take<int>(s);
+  w->total = c.end();
+  return true;
+}
+
 }  // namespace neat

@@ -18,6 +18,7 @@
 #include "kernels_raycast.hpp"
 #include "kernels_show.hpp"
 #include "kernels_trace.hpp"
+#include "kernels_triangulate.hpp"
 #include "ws_layout.hpp"
 
 using namespace neat;
@@ -285,7 +286,33 @@ int main() {
     CHECK(detect_scaled(128, 0.8) == 103 && detect_scaled(5, 0.8) == 4 && detect_scaled(10, 1.0) == 10 && detect_scaled(2, 0.3) == 1);
   }
 
+  // ---- triangulation: views, segments in all, neighbour slots, the largest view; segment counts around the pair kernel's tile
+  {
+    const int shapes[][4] = {{0, 0, 0, 0}, {1, 5, 0, 5}, {2, 1, 1, 1}, {3, 255, 2, 255}, {3, 600, 2, 256}, {7, 761, 6, 257}, {64, 32000, 10, 500}};
+    for (const auto& sh : shapes) {
+      CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+        TriWs w;
+        if (!tri_layout(b, sh[0], sh[1], sh[2], sh[3], TRI_WG, &w)) return false;
+        const size_t s = (size_t)sh[1], sm = s * (size_t)sh[2];
+        if ((long long)w.tiles * TRI_WG < sh[3] || (w.tiles > 0 && (long long)(w.tiles - 1) * TRI_WG >= sh[3])) return false;
+        r = {{w.sega, s * TRI_SEGA * 8, 256}, {w.segb, s * TRI_SEGB * 8, 256}, {w.cnt, sm * 4, 256}, {w.off, sm * 4, 256}, {w.best, s * 4, 256},
+             {w.radius, s * 8, 256}, {w.nviews, s * 4, 256}, {w.axis, s * 4, 256}, {w.last, s * 4, 256}, {w.tau, s * 16, 256}, {w.idx, s * 4, 256}};
+        t = w.total;
+        return true;
+      }));
+    }
+    CHECK(tri_counts_ok(64, 32000, 10, 500, TRI_WG) && tri_counts_ok(0, 0, 0, 0, TRI_WG) && tri_counts_ok(TRI_MAX_VIEWS, 100000, 6, 10, TRI_WG));
+    CHECK(TRI_WG * TRI_SEGB * 8 <= 64 * 1024);                             // the pair kernel's tile of partners in LDS
+  }
+
   // the large values: measured only
+  CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+    TriWs w;
+    if (!tri_layout(b, 1000, 0x7fffffff / 10, 10, 400000, TRI_WG, &w)) return false;
+    r = {{w.sega, (size_t)(0x7fffffff / 10) * 72, 256}, {w.cnt, (size_t)(0x7fffffff / 10) * 40, 256}, {w.idx, (size_t)(0x7fffffff / 10) * 4, 256}};
+    t = w.total;
+    return true;
+  }));
   CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
     DetectWs d;
     if (!detect_layout(b, 64, 1200, 1600, 1.0, 18, DET_TILE, DET_WG, &d)) return false;
@@ -361,6 +388,12 @@ int main() {
         !detect_layout(nullptr, 1, 32769, 16, 1.0, 5, DET_TILE, DET_WG, &wd) && !detect_layout(nullptr, 4096, 32768, 32768, 1.0, 5, DET_TILE, DET_WG, &wd));
   CHECK(detect_maps_ok(3, 129, 129, DET_TILE) && !detect_maps_ok(-1, 4, 4, DET_TILE) && !detect_maps_ok(3, 65536, 65536, DET_TILE) &&
         !detect_maps_ok(70000, 32768, 1, DET_TILE));
+  TriWs wtri;
+  CHECK(!tri_layout(nullptr, -1, 0, 0, 0, TRI_WG, &wtri) && !tri_layout(nullptr, 2, -1, 1, 0, TRI_WG, &wtri) &&
+        !tri_layout(nullptr, 2, 4, -1, 4, TRI_WG, &wtri) && !tri_layout(nullptr, 2, 4, 1, -1, TRI_WG, &wtri) &&
+        !tri_layout(nullptr, 2, 4, 2, 4, TRI_WG, &wtri) && !tri_layout(nullptr, 2, 4, 1, 5, TRI_WG, &wtri) &&
+        !tri_layout(nullptr, TRI_MAX_VIEWS + 1, 4, 1, 4, TRI_WG, &wtri) && !tri_layout(nullptr, 2, 0x7fffffff / 10 + 1, 1, 10, TRI_WG, &wtri) &&
+        !tri_layout(nullptr, 20, 1 << 27, 17, 10, TRI_WG, &wtri) && !tri_layout(nullptr, TRI_MAX_VIEWS, 1 << 24, 64, 1 << 24, TRI_WG, &wtri));
   // the two fixed blocks of partial results
   double* pd;
   float* pf;
