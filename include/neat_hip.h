@@ -751,6 +751,36 @@ int neat_tri_lines(const int* segoff, int V, int S, int nmax, const int* nb, int
                    double* estimate, double* score, int* kept, int* label, int* members, double* lines3d, int* views, double* support,
                    int* n_lines, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): a training scene from a mesh and its wireframe
+ * (neat_amd/scenegen.py): shaded anti-aliased pictures of the mesh and the visible runs of the ground-truth edges, view by view.  Both
+ * walk the tree of neat_raycast_build with its rule, in float64; the rule: DESIGN 3l and neat_amd/csrc/kernels_scenegen.hpp, restated
+ * in float64 by tests/scenegen_f64.py, which the device equals byte for byte.  Asynchronous on the stream (but for the one copy of the
+ * count call), no allocation, no read-back.  Bad arguments return -1 before any launch.
+ *
+ * Shared inputs: bvh, nf as neat_raycast_cast takes them; K float64 [V,3,3] and pose float64 [V,4,4], camera-to-world, both row-major.
+ * Refused: V > 65535, H or W outside [1, 32768], V ceil(H / 16) ceil(W / 16) beyond 2^31 - 1.
+ *
+ * neat_scenegen_shade : rgb uint8 [V,H,W,3] and mask uint8 [V,H,W] (255 where a sub-sample hit).  ss x ss sub-samples a pixel,
+ *   1 <= ss <= 16; albedo, ambient, background finite.
+ * neat_scenegen_scratch_bytes : the workspace (256-byte aligned, caller-owned) that the two edge calls share; 0 when refused
+ *   (a negative count, 8 E or 4 V E beyond 2^31 - 1).
+ * neat_scenegen_edge_count : junctions float64 [J,3] on the device; edges int32 [E,2] ON THE HOST: the indices are checked there
+ *   (each in [0, J)) and the list is copied into the workspace on the stream; the call waits for that copy, so the list may be freed
+ *   when it returns.  step > 0 pixels between samples, a run is kept when its 2-D length
+ *   is >= min_len, bias >= 0, near > 0.  Refused as well: ceil(sqrt(W^2 + H^2) / step) + 2 > 65536, the samples the longest edge a
+ *   picture can hold would need.  *total (device, 64-bit) = the number of runs N, which the host reads to allocate the list.
+ * neat_scenegen_edge_fill : the same pass again with the same arguments and the workspace of the count, writing the N runs in
+ *   (view, edge, run) order: idx int32 [N,4] = view, edge, first and last sample; p2 float64 [N,4] = x1 y1 x2 y2 in the picture;
+ *   p3 float64 [N,2,3] the ends in the world; junc uint8 [N,2]: the end is the edge's own junction, not a cut. */
+size_t neat_scenegen_scratch_bytes(int V, int E);
+int neat_scenegen_shade(const void* bvh, int nf, const double* K, const double* pose, int V, int H, int W, int ss, double albedo, double ambient,
+                        double background, unsigned char* rgb, unsigned char* mask, void* stream);
+int neat_scenegen_edge_count(const void* bvh, int nf, const double* junctions, int J, const int* edges, int E, const double* K, const double* pose,
+                             int V, int H, int W, double step, double min_len, double bias, double near, void* ws, long long* total, void* stream);
+int neat_scenegen_edge_fill(const void* bvh, int nf, const double* junctions, int J, int E, const double* K, const double* pose, int V, int H, int W,
+                            double step, double min_len, double bias, double near, void* ws, long long N, int* idx, double* p2, double* p3,
+                            unsigned char* junc, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

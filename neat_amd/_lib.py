@@ -204,6 +204,12 @@ _SIGNATURES = {
                                      c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp, c_fp]),
     "neat_tri_lines": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_longlong,
                                       c_fp, c_fp, c_fp, ctypes.c_double, ctypes.c_double, ctypes.c_int] + [c_fp] * 10),
+    "neat_scenegen_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "neat_scenegen_shade": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp] + [ctypes.c_int] * 4 + [ctypes.c_double] * 3 + [c_fp] * 3),
+    "neat_scenegen_edge_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, c_fp, c_fp]
+                                 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 + [c_fp] * 3),
+    "neat_scenegen_edge_fill": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp] + [ctypes.c_int] * 3
+                                + [ctypes.c_double] * 4 + [c_fp, ctypes.c_longlong] + [c_fp] * 5),
     "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
     "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),

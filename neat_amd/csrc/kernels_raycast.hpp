@@ -318,23 +318,20 @@ __device__ __forceinline__ bool rc_hit(const double* __restrict__ tv, const RcRa
   return true;
 }
 
-// ---- cast: closest hit, or (ANY) the first accepted hit.  counts [R][2]: node boxes tested, triangles tested; null to skip
+// The walk of one ray: the closest accepted hit with t_min <= t < t_max, or (ANY) the first one the walk meets.  best comes in as t_max and
+// goes out as the hit's t; id = the original face index (-1: a miss), leaf = its place among the sorted triangles; n_nodes, n_tris count
+// the node boxes and the triangles tested.  raycast_cast_kernel and the kernels of kernels_scenegen.hpp call it
+struct RcHit {
+  double t, u, v;
+  int id, leaf;
+  unsigned n_nodes, n_tris;
+};
+
 template <bool ANY>
-__global__ __launch_bounds__(RC_WG) void raycast_cast_kernel(const float* __restrict__ nodes, const double* __restrict__ tris, int nf, int L,
-                                                            const float* __restrict__ origins, const float* __restrict__ dirs,
-                                                            const float* __restrict__ t_min_p, const float* __restrict__ t_max_p, int R,
-                                                            float* __restrict__ t_out, int* __restrict__ tri_out, float* __restrict__ uv_out,
-                                                            unsigned* __restrict__ counts) {
-  const int i = blockIdx.x * RC_WG + threadIdx.x;
-  if (i >= R) return;
-  RcRay r;
-  r.ox = origins[3 * (size_t)i]; r.oy = origins[3 * (size_t)i + 1]; r.oz = origins[3 * (size_t)i + 2];
-  r.dx = dirs[3 * (size_t)i]; r.dy = dirs[3 * (size_t)i + 1]; r.dz = dirs[3 * (size_t)i + 2];
-  rc_ray_setup(r);
-  const double t_min = t_min_p ? (double)t_min_p[i] : 0.0;
-  const double t_max = t_max_p ? (double)t_max_p[i] : (double)INFINITY;
+__device__ __forceinline__ RcHit rc_walk(const float* __restrict__ nodes, const double* __restrict__ tris, int nf, int L, const RcRay& r, double t_min,
+                                         double t_max) {
   double best = t_max, bu = 0.0, bv = 0.0;
-  int best_id = -1;
+  int best_id = -1, best_leaf = -1;
   unsigned n_nodes = 1, n_tris = 0;
   int node = 1;
   unsigned trail = 0;
@@ -355,7 +352,7 @@ __global__ __launch_bounds__(RC_WG) void raycast_cast_kernel(const float* __rest
         if (rc_hit(tv, r, t_min, t_max, t, u, v)) {
           const int id = (int)__double_as_longlong(tv[9]);
           if (t < best || (t == best && id < best_id)) {
-            best = t; best_id = id; bu = u; bv = v;
+            best = t; best_id = id; best_leaf = leaf; bu = u; bv = v;
             if (ANY) break;
           }
         }
@@ -387,12 +384,33 @@ __global__ __launch_bounds__(RC_WG) void raycast_cast_kernel(const float* __rest
       if (rc_box(b[0], b[1], b[2], b[3], b[4], b[5], r, t_min, best, e0)) break;
     }
   }
-  const bool hit = best_id >= 0;
-  t_out[i] = hit ? (float)best : INFINITY;
-  tri_out[i] = hit ? best_id : -1;
-  uv_out[2 * (size_t)i] = hit ? (float)bu : 0.f;
-  uv_out[2 * (size_t)i + 1] = hit ? (float)bv : 0.f;
-  if (counts) { counts[2 * (size_t)i] = n_nodes; counts[2 * (size_t)i + 1] = n_tris; }
+  RcHit h;
+  h.t = best; h.u = bu; h.v = bv; h.id = best_id; h.leaf = best_leaf; h.n_nodes = n_nodes; h.n_tris = n_tris;
+  return h;
+}
+
+// ---- cast: closest hit, or (ANY) the first accepted hit.  counts [R][2]: node boxes tested, triangles tested; null to skip
+template <bool ANY>
+__global__ __launch_bounds__(RC_WG) void raycast_cast_kernel(const float* __restrict__ nodes, const double* __restrict__ tris, int nf, int L,
+                                                            const float* __restrict__ origins, const float* __restrict__ dirs,
+                                                            const float* __restrict__ t_min_p, const float* __restrict__ t_max_p, int R,
+                                                            float* __restrict__ t_out, int* __restrict__ tri_out, float* __restrict__ uv_out,
+                                                            unsigned* __restrict__ counts) {
+  const int i = blockIdx.x * RC_WG + threadIdx.x;
+  if (i >= R) return;
+  RcRay r;
+  r.ox = origins[3 * (size_t)i]; r.oy = origins[3 * (size_t)i + 1]; r.oz = origins[3 * (size_t)i + 2];
+  r.dx = dirs[3 * (size_t)i]; r.dy = dirs[3 * (size_t)i + 1]; r.dz = dirs[3 * (size_t)i + 2];
+  rc_ray_setup(r);
+  const double t_min = t_min_p ? (double)t_min_p[i] : 0.0;
+  const double t_max = t_max_p ? (double)t_max_p[i] : (double)INFINITY;
+  const RcHit h = rc_walk<ANY>(nodes, tris, nf, L, r, t_min, t_max);
+  const bool hit = h.id >= 0;
+  t_out[i] = hit ? (float)h.t : INFINITY;
+  tri_out[i] = hit ? h.id : -1;
+  uv_out[2 * (size_t)i] = hit ? (float)h.u : 0.f;
+  uv_out[2 * (size_t)i + 1] = hit ? (float)h.v : 0.f;
+  if (counts) { counts[2 * (size_t)i] = h.n_nodes; counts[2 * (size_t)i + 1] = h.n_tris; }
 }
 
 }  // namespace neat

@@ -15,6 +15,7 @@
 #include "kernels_trace.hpp"
 #include "kernels_post.hpp"
 #include "kernels_raycast.hpp"
+#include "kernels_scenegen.hpp"
 #include "kernels_detect.hpp"
 #include "kernels_triangulate.hpp"
 #include "ws_layout.hpp"
@@ -1334,6 +1335,75 @@ int neat_tri_lines(const int* segoff, int V, int S, int nmax, const int* nb, int
                      (const double*)estimate, w.nviews, w.axis, w.tau);
   hipLaunchKernelGGL(tri_output_kernel, dim3(1), dim3(1024), 0, st, S, min_views, (const int*)label, (const int*)w.nviews, (const int*)w.axis,
                      (const double*)w.tau, (const double*)estimate, (const double*)score, w.idx, members, lines3d, views, support, n_lines);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: a training scene from a mesh and its wireframe (kernels_scenegen.hpp) -------------------------------------------------
+size_t neat_scenegen_scratch_bytes(int V, int E) {
+  ScenegenWs w;
+  return scenegen_layout(nullptr, V, E, &w) ? w.total : 0;
+}
+
+int neat_scenegen_shade(const void* bvh, int nf, const double* K, const double* pose, int V, int H, int W, int ss, double albedo, double ambient,
+                        double background, unsigned char* rgb, unsigned char* mask, void* stream) {
+  RaycastWs t;
+  if (!bvh || ((uintptr_t)bvh & 255) || !raycast_layout(const_cast<void*>(bvh), nullptr, nf, RC_WG, RC_TRI_STRIDE, &t) || ss < 1 || ss > SG_MAX_SS ||
+      !scenegen_picture_ok(V, H, W) || !std::isfinite(albedo) || !std::isfinite(ambient) || !std::isfinite(background))
+    return -1;
+  if (V == 0) return 0;
+  if (!K || !pose || !rgb || !mask) return -1;
+  const SgShade sh = {albedo, ambient, background};
+  hipLaunchKernelGGL(scenegen_shade_kernel, dim3((unsigned)((long long)V * ((H + 15) / 16) * ((W + 15) / 16))), dim3(SG_WG), 0, (hipStream_t)stream,
+                     (const float*)t.nodes, (const double*)t.tris, nf, t.L, K, pose, H, W, ss, sh, rgb, mask);
+  return (int)hipGetLastError();
+}
+
+// every argument of the edge pass that a launch turns into a loop bound or an index; the 2-D segment of an edge is cut to the picture, so
+// no edge needs more samples than the picture's diagonal does
+static bool scenegen_edge_args_ok(const void* bvh, int nf, int V, int E, int H, int W, double step, double min_len, double bias, double near,
+                                  RaycastWs* t) {
+  if (!bvh || ((uintptr_t)bvh & 255) || !raycast_layout(const_cast<void*>(bvh), nullptr, nf, RC_WG, RC_TRI_STRIDE, t)) return false;
+  if (!scenegen_picture_ok(V, H, W) || !scenegen_counts_ok(V, E)) return false;
+  if (!(step > 0.0) || !std::isfinite(step) || !std::isfinite(min_len) || !(bias >= 0.0) || !std::isfinite(bias) || !(near > 0.0) || !std::isfinite(near))
+    return false;
+  return std::ceil(std::sqrt((double)W * W + (double)H * H) / step) + 2.0 <= (double)SG_MAX_SAMPLES;
+}
+
+int neat_scenegen_edge_count(const void* bvh, int nf, const double* junctions, int J, const int* edges, int E, const double* K, const double* pose,
+                             int V, int H, int W, double step, double min_len, double bias, double near, void* ws, long long* total, void* stream) {
+  RaycastWs t;
+  ScenegenWs w;
+  if (!scenegen_edge_args_ok(bvh, nf, V, E, H, W, step, min_len, bias, near, &t) || J < 0 || !total || !scenegen_layout(ws, V, E, &w)) return -1;
+  if (E > 0 && !edges) return -1;
+  for (long long i = 0; i < 2ll * E; ++i)
+    if (edges[i] < 0 || edges[i] >= J) return -1;                      // `edges` is the host's list
+  hipStream_t st = (hipStream_t)stream;
+  NEAT_CHECK(hipMemsetAsync(total, 0, sizeof(long long), st));
+  if ((long long)V * E == 0) return 0;
+  if (!junctions || !K || !pose || !ws || ((uintptr_t)ws & 255)) return -1;
+  NEAT_CHECK(hipMemcpyAsync(w.edges, edges, 2 * (size_t)E * sizeof(int), hipMemcpyHostToDevice, st));
+  NEAT_CHECK(hipStreamSynchronize(st));                                 // the host's list may go away when this call returns
+  const int pairs = V * E;
+  hipLaunchKernelGGL(scenegen_edge_kernel<false>, grid1(pairs, SG_WAVES), dim3(SG_WG), 0, st, (const float*)t.nodes, (const double*)t.tris, nf, t.L,
+                     junctions, (const int*)w.edges, E, K, pose, V, H, W, step, min_len, bias, near, w.cnt, (const int*)nullptr, 0, (int*)nullptr,
+                     (double*)nullptr, (double*)nullptr, (unsigned char*)nullptr);
+  hipLaunchKernelGGL(scenegen_scan_kernel, dim3(1), dim3(1024), 0, st, pairs, (const int*)w.cnt, w.off, total);
+  return (int)hipGetLastError();
+}
+
+int neat_scenegen_edge_fill(const void* bvh, int nf, const double* junctions, int J, int E, const double* K, const double* pose, int V, int H, int W,
+                            double step, double min_len, double bias, double near, void* ws, long long N, int* idx, double* p2, double* p3,
+                            unsigned char* junc, void* stream) {
+  RaycastWs t;
+  ScenegenWs w;
+  if (!scenegen_edge_args_ok(bvh, nf, V, E, H, W, step, min_len, bias, near, &t) || J < 0 || N < 0 || N > 0x7fffffffLL / 8 ||
+      !scenegen_layout(ws, V, E, &w))
+    return -1;
+  if (N == 0) return 0;
+  if ((long long)V * E == 0 || !junctions || !K || !pose || !ws || ((uintptr_t)ws & 255) || !idx || !p2 || !p3 || !junc) return -1;
+  hipLaunchKernelGGL(scenegen_edge_kernel<true>, grid1(V * E, SG_WAVES), dim3(SG_WG), 0, (hipStream_t)stream, (const float*)t.nodes,
+                     (const double*)t.tris, nf, t.L, junctions, (const int*)w.edges, E, K, pose, V, H, W, step, min_len, bias, near, (int*)nullptr,
+                     (const int*)w.off, (int)N, idx, p2, p3, junc);
   return (int)hipGetLastError();
 }
 

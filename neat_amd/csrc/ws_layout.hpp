@@ -393,4 +393,27 @@ inline bool tri_layout(void* ws, int V, int S, int M, int nmax, int tile, TriWs*
   return true;
 }
 
+// ---- scene generation (kernels_scenegen.hpp): the visible runs of E edges in V views.  edges [2 E] (the host's list, checked there and
+// copied in by the count call) | cnt, off [V E] (runs kept per (view, edge), their offsets).  The run list, whose length only the count
+// pass knows, is the caller's.  The picture bounds: one launch over every 16 x 16 tile of every view
+constexpr int SG_MAX_VIEWS = 65535;
+inline bool scenegen_counts_ok(long long V, long long E) {
+  return V >= 0 && E >= 0 && V <= SG_MAX_VIEWS && E <= 0x7fffffffLL / 8 && V * E <= 0x7fffffffLL / 4;
+}
+inline bool scenegen_picture_ok(long long V, long long H, long long W) {
+  if (V < 0 || V > SG_MAX_VIEWS || H < 1 || W < 1 || H > 32768 || W > 32768) return false;
+  return V * ((H + 15) / 16) * ((W + 15) / 16) <= 0x7fffffffLL;
+}
+struct ScenegenWs { int *edges, *cnt, *off; size_t total; };
+inline bool scenegen_layout(void* ws, int V, int E, ScenegenWs* w) {
+  if (!scenegen_counts_ok(V, E)) return false;
+  const size_t pairs = (size_t)V * (size_t)E;
+  WsCarver c(ws);
+  w->edges = c.take<int>(2 * (size_t)E);
+  w->cnt = c.take<int>(pairs);
+  w->off = c.take<int>(pairs);
+  w->total = c.end();
+  return true;
+}
+
 }  // namespace neat

@@ -305,6 +305,24 @@ int main() {
     CHECK(TRI_WG * TRI_SEGB * 8 <= 64 * 1024);                             // the pair kernel's tile of partners in LDS
   }
 
+  // ---- scene generation: views and edges; the edge list, then the runs per (view, edge) and their offsets
+  {
+    const int shapes[][2] = {{0, 0}, {0, 18}, {3, 0}, {1, 1}, {3, 12}, {100, 18}, {7, 257}, {SG_MAX_VIEWS, 4096}};
+    for (const auto& sh : shapes) {
+      CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+        ScenegenWs w;
+        if (!scenegen_layout(b, sh[0], sh[1], &w)) return false;
+        const size_t pairs = (size_t)sh[0] * (size_t)sh[1];
+        r = {{w.edges, (size_t)sh[1] * 8, 256}, {w.cnt, pairs * 4, 256}, {w.off, pairs * 4, 256}};
+        t = w.total;
+        return true;
+      }));
+    }
+    CHECK(scenegen_counts_ok(100, 18) && scenegen_counts_ok(0, 0) && scenegen_counts_ok(SG_MAX_VIEWS, 0x7fffffff / 4 / SG_MAX_VIEWS));
+    CHECK(scenegen_picture_ok(100, 512, 512) && scenegen_picture_ok(0, 1, 1) && scenegen_picture_ok(SG_MAX_VIEWS, 2048, 2048));
+    CHECK((long long)SG_MAX_VIEWS * (2048 / 16) * (2048 / 16) <= 0x7fffffffLL);      // the grid of that launch
+  }
+
   // the large values: measured only
   CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
     TriWs w;
@@ -394,6 +412,11 @@ int main() {
         !tri_layout(nullptr, 2, 4, 2, 4, TRI_WG, &wtri) && !tri_layout(nullptr, 2, 4, 1, 5, TRI_WG, &wtri) &&
         !tri_layout(nullptr, TRI_MAX_VIEWS + 1, 4, 1, 4, TRI_WG, &wtri) && !tri_layout(nullptr, 2, 0x7fffffff / 10 + 1, 1, 10, TRI_WG, &wtri) &&
         !tri_layout(nullptr, 20, 1 << 27, 17, 10, TRI_WG, &wtri) && !tri_layout(nullptr, TRI_MAX_VIEWS, 1 << 24, 64, 1 << 24, TRI_WG, &wtri));
+  ScenegenWs wsg;
+  CHECK(!scenegen_layout(nullptr, -1, 1, &wsg) && !scenegen_layout(nullptr, 1, -1, &wsg) && !scenegen_layout(nullptr, SG_MAX_VIEWS + 1, 1, &wsg) &&
+        !scenegen_layout(nullptr, 1, 0x7fffffff / 8 + 1, &wsg) && !scenegen_layout(nullptr, 1000, 0x7fffffff / 4000 + 1, &wsg));
+  CHECK(!scenegen_picture_ok(-1, 8, 8) && !scenegen_picture_ok(1, 0, 8) && !scenegen_picture_ok(1, 8, 0) && !scenegen_picture_ok(1, 32769, 8) &&
+        !scenegen_picture_ok(1, 8, 32769) && !scenegen_picture_ok(SG_MAX_VIEWS + 1, 8, 8) && !scenegen_picture_ok(1000, 32768, 32768));
   // the two fixed blocks of partial results
   double* pd;
   float* pf;
