@@ -1,8 +1,16 @@
 /* neat_hip.h -- C ABI of libneat_hip.so: the MI355X (gfx950) implementation of NEAT's volumetric-
- * rendering hot path.  Plain pointers and sizes only (no torch types): every pointer is a DEVICE
- * pointer to float32 unless stated, `stream` is a hipStream_t passed as void*, every call is
- * asynchronous on that stream, never synchronises, never allocates, never keeps caller memory.
+ * rendering hot path.  Plain pointers and sizes only (no torch types).  A pointer parameter is a DEVICE
+ * pointer (to float32 unless its type or the text says otherwise) or an opaque handle -- `stream`, a
+ * hipStream_t passed as void*; a workspace `ws`; a `bvh` -- unless it is marked NEAT_HOST: those the entry
+ * point itself reads or writes on the host before it returns, so they must be host memory and may be
+ * freed after the call.  Pointer fields inside the structs are device pointers.  Every call is
+ * asynchronous on its stream, never synchronises, never allocates, never keeps caller memory, unless
+ * its own text says so.
  * Return value: 0 on success, otherwise a hipError_t (or -1 for bad arguments).
+ *
+ * This file is also the one written copy of the signatures: neat_amd/_lib.py builds its ctypes binding by
+ * reading it, so a declaration keeps the plain form `int|size_t neat_x(T a, const T* b, NEAT_HOST const T* c, ...);`
+ * with the scalar types int, float, double, long long and size_t.
  *
  * The reference (cherubicXN/neat) has no native layer: these entry points replace the ATen op
  * sequences issued by the Python lines cited on each function (paths relative to the reference's
@@ -18,6 +26,7 @@
 extern "C" {
 #endif
 
+#define NEAT_HOST             /* marks a pointer parameter the entry point dereferences on the host (expands to nothing) */
 #define NEAT_NUM_LAYERS 19   /* implicit_network.lin0..8, rendering_network.lin0..4, attraction_network.lin0..4 */
 #define NEAT_FEATURE 256
 
@@ -70,7 +79,7 @@ int neat_abi_version(void);      /* 15 */
 /* ---- a15: weight norm + packing (replaces the per-call `_weight_norm` pre-hook) -------------------
  * Computes W = g * v/|v| for all 19 layers once per step and stores W and W^T in MFMA-fragment order. */
 size_t neat_packed_floats(int precision);
-int neat_pack_weights(const neat_net_params* net, float* packed, int precision, void* stream);
+int neat_pack_weights(NEAT_HOST const neat_net_params* net, float* packed, int precision, void* stream);
 
 /* ---- a1: pixel -> unit ray directions (utils/rend_util.py:55-81 get_camera_params, :95-108 lift) --
  * uv [R,2], pose [4,4] cam-to-world, K row stride `kstride` (3 or 4).  dirs [R,3].  Origin = pose[:3,3]. */
@@ -90,30 +99,30 @@ int neat_eik_points(const float* uniform, const float* origins, const float* dir
  * radius > 0 enables the bounding-sphere clamp min(sdf, scale*(radius-|x|)).
  * Any of out257 / sdf / feat / grad may be NULL.  x is row-major [P,3]. */
 size_t neat_sdf_ws_floats(int P, int mode, int precision);
-int neat_sdf_forward(const float* packed, const neat_net_params* net, const float* x, int P, int mode, int precision,
+int neat_sdf_forward(const float* packed, NEAT_HOST const neat_net_params* net, const float* x, int P, int mode, int precision,
                      float radius, float scale, float* ws,
                      float* out257, float* sdf, float* feat, float* grad, void* stream);
 /* Backward of mode-1 forward (autograd incl. the double backward through d sdf/dx, which the reference
  * gets from create_graph=True at :121-127).  Cotangents are row-major and may be NULL (= zero):
  * d_out257 [P,257] (of forward()), d_sdf [P] (of the clamped sdf), d_feat [P,256], d_grad [P,3].
  * Writes grads->dv/dg/db[0..8]. */
-int neat_sdf_backward(const float* packed, const neat_net_params* net, float* ws, int P, int precision,
+int neat_sdf_backward(const float* packed, NEAT_HOST const neat_net_params* net, float* ws, int P, int precision,
                       const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
-                      const neat_net_grads* grads, void* stream);
+                      NEAT_HOST const neat_net_grads* grads, void* stream);
 /* ABI v14: neat_sdf_backward, differentiated in the query points x as well (rend_a :111-137 are plain autograd in x: get_outputs,
  * gradient, forward and get_sdf_vals; the normal, built with create_graph=True at :121-127, included).  Same arguments plus
  * scale (the forward's sphere scale: the clamped sdf s (radius - |x|) and its gradient -s x/|x| depend on it) and d_x [P,3] row-major,
  * which receives dL/dx of L = <d_out257, forward()> + <d_sdf, sdf> + <d_feat, feat> + <d_grad, d sdf/dx>, first order (d_x itself is
  * not differentiable).  grads may be NULL, and so may any layer's dv/dg/db (all three together): no weight gradient is formed for those
  * layers -- a frozen network whose input points are optimised.  The parameter gradients it does write equal neat_sdf_backward's. */
-int neat_sdf_backward_x(const float* packed, const neat_net_params* net, float* ws, int P, int precision, float scale,
+int neat_sdf_backward_x(const float* packed, NEAT_HOST const neat_net_params* net, float* ws, int P, int precision, float scale,
                         const float* d_out257, const float* d_sdf, const float* d_feat, const float* d_grad,
-                        const neat_net_grads* grads, float* d_x, void* stream);
+                        NEAT_HOST const neat_net_grads* grads, float* d_x, void* stream);
 
 /* ---- a6+a7: the two heads on given inputs (RenderingNetwork.forward :235-255,
  * AttractionFieldNetwork.forward :175-197), row-major inputs; rgb [P,3], lines [P,2,3]. */
 size_t neat_heads_ws_floats(int P, int precision);
-int neat_heads_forward(const float* packed, const neat_net_params* net, const float* points, const float* normals,
+int neat_heads_forward(const float* packed, NEAT_HOST const neat_net_params* net, const float* points, const float* normals,
                        const float* view_dirs, const float* feats, int P, int precision, float* ws,
                        float* rgb, float* lines, void* stream);
 
@@ -124,7 +133,7 @@ int neat_heads_forward(const float* packed, const neat_net_params* net, const fl
  * Outputs (row-major, NULL to skip where noted): points [R,S,3] (opt), weights [R,S] (opt),
  * sdf [R,S] (opt), rgb [R,3], lines3d [R,2,3], depth [R], xyz [R,3], normal_map [R,3] (opt). */
 size_t neat_render_ws_floats(int R, int S, int E, int precision);
-int neat_render_forward(const float* packed, const neat_net_params* net, const float* origins, const float* dirs,
+int neat_render_forward(const float* packed, NEAT_HOST const neat_net_params* net, const float* origins, const float* dirs,
                         const float* z, int R, int S, int precision, const float* beta, float beta_min, float radius, float scale, float* ws,
                         float* points, float* weights, float* sdf, float* rgb, float* lines3d, float* depth,
                         float* xyz, float* normal_map, const float* eik_points, int E, float* eik_grad, void* stream);
@@ -137,17 +146,17 @@ int neat_render_forward(const float* packed, const neat_net_params* net, const f
  * per-ray partial derivative wrt the density's beta, dbeta_ray [R].  dbeta (device pointer to one float, or NULL; ABI v12) receives
  * the gradient of *beta itself: sgn(*beta) * sum_r dbeta_ray[r], summed in a fixed order by one more tiny launch (the `.sum()` and the
  * backward of `.abs()` of density.py:29-30). */
-int neat_render_backward(const float* packed, const neat_net_params* net, float* ws, const float* dirs,
+int neat_render_backward(const float* packed, NEAT_HOST const neat_net_params* net, float* ws, const float* dirs,
                          const float* z, int R, int S, int E, int precision, const float* beta, float beta_min,
                          const float* d_rgb, const float* d_lines3d, const float* d_depth, const float* d_xyz,
-                         const float* d_eik_grad, const float* d_acc, const neat_net_grads* grads, float* dbeta_ray, float* dbeta, void* stream);
+                         const float* d_eik_grad, const float* d_acc, NEAT_HOST const neat_net_grads* grads, float* dbeta_ray, float* dbeta, void* stream);
 
 /* Forward-only variant for eval / inference callers (code/neat-final-parsing.py:203-218 drives `model(s)` in 2048-ray chunks under
  * model.eval(); training/volsdf_train.py:312-320 renders validation images the same way): same arguments and results as
  * neat_render_forward with E = 0, but the workspace keeps nothing for a backward pass (hidden activations of the adjoint chain and
  * of the two heads ping-pong between two buffers): about a quarter of neat_render_ws_floats. */
 size_t neat_render_eval_ws_floats(int R, int S, int precision);
-int neat_render_forward_eval(const float* packed, const neat_net_params* net, const float* origins, const float* dirs,
+int neat_render_forward_eval(const float* packed, NEAT_HOST const neat_net_params* net, const float* origins, const float* dirs,
                              const float* z, int R, int S, int precision, const float* beta, float beta_min, float radius, float scale, float* ws,
                              float* points, float* weights, float* sdf, float* rgb, float* lines3d, float* depth,
                              float* xyz, float* normal_map, void* stream);
@@ -203,9 +212,9 @@ int neat_sampler_finish(const float* samples, int N, const float* z, int n, cons
  *                              linspace(0, n-1, n_extra).long() (:266, eval); keys [>= n] -> the indices of the n_extra smallest
  *                              keys, a uniformly random subset like randperm(n)[:n_extra] (:264, training); then as
  *                              neat_sampler_finish.  `pick` [n_extra] receives the indices. */
-int neat_sdf_values_gated(const float* packed, const neat_net_params* net, const float* x, int P, int precision, float radius,
+int neat_sdf_values_gated(const float* packed, NEAT_HOST const neat_net_params* net, const float* x, int P, int precision, float radius,
                           float scale, float* ws, float* sdf, const int* gate, int gate_value, void* stream);
-int neat_sdf_values_rays(const float* packed, const neat_net_params* net, const float* origins, const float* dirs, const float* z, int R,
+int neat_sdf_values_rays(const float* packed, NEAT_HOST const neat_net_params* net, const float* origins, const float* dirs, const float* z, int R,
                          int S, int precision, float radius, float scale, float* ws, float* sdf, const int* gate, int gate_value,
                          void* stream);
 int neat_sampler_init(const float* z, int R, int n, const float* beta, float beta_min, float beta_c, float* beta0, float* beta_ray,
@@ -241,7 +250,7 @@ int neat_sampler_finish_dev(const float* samples, int N, const float* z_final, i
  *  neat_sampler_finish_picked : neat_sampler_finish with the grid size read from *n_final and the picks from
  *                             pick_all[n / n_step - 1] (pick_all == NULL: linspace(0, n - 1, n_extra).long(), eval mode :266). */
 int neat_sdf_ldp(int P, int precision);
-int neat_sdf_values_laid_out(const float* packed, const neat_net_params* net, int P, int precision, float radius, float scale, float* ws,
+int neat_sdf_values_laid_out(const float* packed, NEAT_HOST const neat_net_params* net, int P, int precision, float radius, float scale, float* ws,
                              float* sdf, const int* gate, int gate_value, void* stream);
 int neat_sampler_init_rays(const float* z, int R, int n, const float* beta, float beta_min, float beta_c, float* beta0, float* beta_ray,
                            int* ctl, int nctl, const float* origins, const float* dirs, float* x_fm, int ldp, const float* keys, int n_step,
@@ -281,7 +290,7 @@ int neat_gather_batch(const int* pool, int npool, const long long* draw, int n, 
  * persistent tensors a captured step reads, as ONE launch: copy i moves nbytes[i] bytes from src[i] to dst[i] (n <= 16).  A source may be
  * device memory or pinned host memory (hipHostMalloc: the kernel reads it over the bus -- no separate copy-engine transfer and none of
  * the idle gaps between a copy and the next kernel).  Pointers 4-byte aligned, sizes multiples of 4. */
-int neat_copy_batch(const void* const* src, void* const* dst, const long long* nbytes, int n, void* stream);
+int neat_copy_batch(NEAT_HOST const void* const* src, NEAT_HOST void* const* dst, NEAT_HOST const long long* nbytes, int n, void* stream);
 
 /* ---- a11 / a14 glue as single launches.  neat_project2d = VolSDFNetwork.project2D (model/networks/neat_wfr_rend_a.py:317-326):
  * K [3,3] and w2c [3,4] = [R|T] row-major on the device, X [N,3] -> uv [N,2]; its backward gives d_X from d_uv.
@@ -358,11 +367,11 @@ int neat_line_losses(const float* pred_px, const float* pred_calib, const float*
  * gradients stay where autograd left them: grads[s] (device pointer, or NULL = no gradient this step: that segment is
  * skipped like torch does) covers elements [seg_offsets[s], seg_offsets[s+1]); seg_steps[s] = 1-based count of the steps
  * that segment has taken including this one (torch counts steps per tensor) -- host arrays, nseg <= 96. */
-int neat_adam_step(float* params, const float* const* grads, const long long* seg_offsets, const int* seg_steps, int nseg,
+int neat_adam_step(float* params, NEAT_HOST const float* const* grads, NEAT_HOST const long long* seg_offsets, NEAT_HOST const int* seg_steps, int nseg,
                    float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, void* stream);
 /* ABI v13: neat_adam_step with its step-dependent numbers in DEVICE memory -- coef [2 nseg] = (lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t))
  * per segment -- so that the launch can be captured in the step's HIP graph and replayed; grads[s] == NULL: segment untouched. */
-int neat_adam_step_coef(float* params, const float* const* grads, const long long* seg_offsets, int nseg, float* exp_avg, float* exp_avg_sq,
+int neat_adam_step_coef(float* params, NEAT_HOST const float* const* grads, NEAT_HOST const long long* seg_offsets, int nseg, float* exp_avg, float* exp_avg_sq,
                         const float* coef, float beta1, float beta2, float eps, void* stream);
 
 /* ---- 8f-2 (next row): device-side rectangular assignment = scipy.optimize.linear_sum_assignment as called at
@@ -442,10 +451,10 @@ int neat_parse_visibility(const float* lines, const int* n_lines, int ecap, cons
  * neat_mesh_emit : verts [nv,3] fp32 and faces [nf,3] int32 for the same grid, level and ws; nv, nf as counted (writes beyond them are
  *   dropped).  Bad arguments (an axis under 2 nodes, 2^31 nodes or more, null pointers, a NaN level) return -1 before any launch.
  * neat_unit_rows3 : rows of g [n,3] scaled to unit length in place (vertex normals from the SDF gradient at the vertices). */
-int neat_grid_points(float* x_fm, int ldp, long long first_node, int count, const int* n, const double* b0, const double* b1, void* stream);
+int neat_grid_points(float* x_fm, int ldp, long long first_node, int count, NEAT_HOST const int* n, NEAT_HOST const double* b0, NEAT_HOST const double* b1, void* stream);
 size_t neat_mesh_ws_bytes(int nx, int ny, int nz);
 int neat_mesh_count(const float* grid, int nx, int ny, int nz, float level, void* ws, int* counts, void* stream);
-int neat_mesh_emit(const float* grid, int nx, int ny, int nz, const double* b0, const double* b1, float level, void* ws, float* verts, int nv,
+int neat_mesh_emit(const float* grid, int nx, int ny, int nz, NEAT_HOST const double* b0, NEAT_HOST const double* b1, float level, void* ws, float* verts, int nv,
                    int* faces, int nf, void* stream);
 int neat_unit_rows3(float* g, int n, void* stream);
 
@@ -474,13 +483,13 @@ int neat_unit_rows3(float* g, int n, void* stream);
  *   a + t (b - a), t = d_a / (d_a - d_b) in float64, the axis coordinate exactly `value`) and out_faces [nf_out,3], nf_out = sum of fcnt
  *   (by source face, then by emitted triangle; winding kept).  Writes beyond nv_out / nf_out are dropped.
  * Bad arguments return -1 before any launch. */
-int neat_grid_points_affine(float* x_fm, int ldp, long long first_node, int count, const int* n, const double* b0, const double* b1,
-                            const double* R, const double* c, void* stream);
+int neat_grid_points_affine(float* x_fm, int ldp, long long first_node, int count, NEAT_HOST const int* n, NEAT_HOST const double* b0, NEAT_HOST const double* b1,
+                            NEAT_HOST const double* R, NEAT_HOST const double* c, void* stream);
 size_t neat_mesh_moments_ws_bytes(int nf);
-int neat_mesh_moments(const float* verts, int nv, const int* faces, int nf, const double* origin, void* ws, double* out, int* flag, void* stream);
-int neat_affine_rows3(float* v, int n, const double* A, void* stream);
+int neat_mesh_moments(const float* verts, int nv, const int* faces, int nf, NEAT_HOST const double* origin, void* ws, double* out, int* flag, void* stream);
+int neat_affine_rows3(float* v, int n, NEAT_HOST const double* A, void* stream);
 size_t neat_affine_bounds3_ws_bytes(void);
-int neat_affine_bounds3(const float* v, int n, const double* A, void* ws, double* out, void* stream);
+int neat_affine_bounds3(const float* v, int n, NEAT_HOST const double* A, void* ws, double* out, void* stream);
 int neat_mesh_cut_count(const float* verts, int nv, const int* faces, int nf, int axis, double value, int sign, int* fcnt, long long* ekey,
                         int* used, void* stream);
 int neat_mesh_cut_emit(const float* verts, int nv, const int* faces, int nf, int axis, double value, int sign, const int* used, const int* vmap,
@@ -525,11 +534,11 @@ typedef struct {
   const double* spts;
 } neat_eval_grid_t;
 size_t neat_eval_grid_ws_bytes(int n, int buckets);
-int neat_eval_grid(const double* points, const neat_eval_grid_t* grid, int* start, int* sidx, double* spts, void* ws, void* stream);
-int neat_eval_thin_round(const double* points, const neat_eval_grid_t* grid, double radius, unsigned char* state, int* undecided, void* stream);
-int neat_eval_nearest(const neat_eval_grid_t* grid, const double* queries, int m, double max_dist, double* dist, int* idx, void* stream);
-int neat_eval_obs_mask(const double* points, int n, const double* lo, const double* hi, const double* bb0, double res, const unsigned char* mask,
-                       const int* shape, int f32_quotient, unsigned char* flags, void* stream);
+int neat_eval_grid(const double* points, NEAT_HOST const neat_eval_grid_t* grid, int* start, int* sidx, double* spts, void* ws, void* stream);
+int neat_eval_thin_round(const double* points, NEAT_HOST const neat_eval_grid_t* grid, double radius, unsigned char* state, int* undecided, void* stream);
+int neat_eval_nearest(NEAT_HOST const neat_eval_grid_t* grid, const double* queries, int m, double max_dist, double* dist, int* idx, void* stream);
+int neat_eval_obs_mask(const double* points, int n, NEAT_HOST const double* lo, NEAT_HOST const double* hi, NEAT_HOST const double* bb0, double res, const unsigned char* mask,
+                       NEAT_HOST const int* shape, int f32_quotient, unsigned char* flags, void* stream);
 size_t neat_eval_tri_ws_bytes(int nf);
 int neat_eval_tri_count(const double* verts, int nv, const int* faces, int nf, double density, void* ws, int* total, void* stream);
 int neat_eval_tri_emit(const double* verts, int nv, const int* faces, int nf, double density, void* ws, double* out, int total, void* stream);
@@ -558,7 +567,7 @@ int neat_eval_line_cost(const double* pred, int n_pred, const double* gt, int n_
  * neat_show_points  : points [n,3] float64 as discs of radius + 0.5 - distance, the same visibility rule.
  * neat_show_resolve : out [F,H,W,3] bytes; colors = HOST array of twelve: background, line, point, mesh rgb in [0, 1]. */
 size_t neat_show_ws_bytes(int F, int H, int W);
-int neat_show_ws_layout(int F, int H, int W, size_t* offsets);
+int neat_show_ws_layout(int F, int H, int W, NEAT_HOST size_t* offsets);
 int neat_show_clear(void* ws, int F, int H, int W, void* stream);
 int neat_show_mesh(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, double near, void* ws,
                    void* stream);
@@ -566,7 +575,7 @@ int neat_show_lines(const double* lines, int n, const double* cams, int F, int H
                     double hidden_alpha, void* ws, void* stream);
 int neat_show_points(const double* points, int n, const double* cams, int F, int H, int W, double near, double radius, double bias,
                      double hidden_alpha, void* ws, void* stream);
-int neat_show_resolve(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, const double* colors,
+int neat_show_resolve(const double* verts, int nv, const int* faces, int nf, const double* cams, int F, int H, int W, NEAT_HOST const double* colors,
                       void* ws, unsigned char* out, void* stream);
 
 /* ---- added to ABI v15 (new symbols only, so the version number stays): the frame side of rendering whole views of a checkpoint
@@ -775,7 +784,7 @@ int neat_tri_lines(const int* segoff, int V, int S, int nmax, const int* nb, int
 size_t neat_scenegen_scratch_bytes(int V, int E);
 int neat_scenegen_shade(const void* bvh, int nf, const double* K, const double* pose, int V, int H, int W, int ss, double albedo, double ambient,
                         double background, unsigned char* rgb, unsigned char* mask, void* stream);
-int neat_scenegen_edge_count(const void* bvh, int nf, const double* junctions, int J, const int* edges, int E, const double* K, const double* pose,
+int neat_scenegen_edge_count(const void* bvh, int nf, const double* junctions, int J, NEAT_HOST const int* edges, int E, const double* K, const double* pose,
                              int V, int H, int W, double step, double min_len, double bias, double near, void* ws, long long* total, void* stream);
 int neat_scenegen_edge_fill(const void* bvh, int nf, const double* junctions, int J, int E, const double* K, const double* pose, int V, int H, int W,
                             double step, double min_len, double bias, double near, void* ws, long long N, int* idx, double* p2, double* p3,
@@ -822,7 +831,7 @@ int neat_volume_weights(const float* z, const float* sdf, int R, int S, const fl
  *     (v_mfma_f32_32x32x2_f32: exact fp32 products, fixed summation order) instead of the vector-ALU kernel (default 1) */
 int neat_set_tuning(int key, int value);
 int neat_prof_enable(int on);
-int neat_prof_collect(int cls, double* total_ms, double* total_flops, int* launches, double* total_bytes);
+int neat_prof_collect(int cls, NEAT_HOST double* total_ms, NEAT_HOST double* total_flops, NEAT_HOST int* launches, NEAT_HOST double* total_bytes);
 
 #ifdef __cplusplus
 }

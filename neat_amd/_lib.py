@@ -1,228 +1,105 @@
-"""ctypes binding of libneat_hip.so (C ABI declared in include/neat_hip.h).
+"""ctypes binding of libneat_hip.so, read from include/neat_hip.h: the header is the only written copy of the C ABI.
 
-There is NO fallback: if the shared library is missing or a call fails, a RuntimeError is raised.
+parse_header turns its prototypes into restype / argtypes and its struct typedefs into ctypes.Structure classes, once, on the first lib() or
+exported_symbols() (or the first use of NUM_LAYERS, NetParams, NetGrads, EvalGrid or _SIGNATURES).  A pointer is passed as an integer address
+(c_void_p) unless the header marks it NEAT_HOST: those the library dereferences on the host, and they are typed POINTER(...), so ctypes
+refuses anything but an array or byref of that element type (or None).
+
+There is NO fallback: if the shared library or the header is missing, a declaration is not understood or a call fails, a RuntimeError is raised.
 """
 import ctypes
 import os
+import re
 
 import torch
 
-NUM_LAYERS = 19
-ABI_VERSION = 15
+ABI_VERSION = 15      # what this package expects of the library (checked against neat_abi_version()); not read from the header
 PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2, "fp16": 3, "fp16x3": 4}
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NEAT_HIP_LIB") or os.path.join(_HERE, "csrc", "libneat_hip.so")      # NEAT_HIP_LIB: a probe build (scripts/probes/abl_build.sh)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "neat_hip.h")
 
-c_fp = ctypes.c_void_p      # device float* (passed as integer addresses)
+c_fp = ctypes.c_void_p      # a device pointer or an opaque handle (passed as integer addresses)
 
-
-class NetParams(ctypes.Structure):
-    _fields_ = [("v", c_fp * NUM_LAYERS), ("g", c_fp * NUM_LAYERS), ("b", c_fp * NUM_LAYERS)]
-
-
-class NetGrads(ctypes.Structure):
-    _fields_ = [("dv", c_fp * NUM_LAYERS), ("dg", c_fp * NUM_LAYERS), ("db", c_fp * NUM_LAYERS)]
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+            "size_t": ctypes.c_size_t, "unsigned char": ctypes.c_ubyte}
+_STRUCTS = {"neat_net_params": "NetParams", "neat_net_grads": "NetGrads", "neat_eval_grid_t": "EvalGrid"}      # typedef -> module attribute
 
 
-class EvalGrid(ctypes.Structure):
-    """neat_eval_grid_t: a uniform cell grid over a cloud (neat_amd/evaluate.py builds it)."""
-    _fields_ = [("origin", ctypes.c_double * 3), ("cell", ctypes.c_double), ("dim", ctypes.c_int * 3), ("buckets", ctypes.c_int),
-                ("dense", ctypes.c_int), ("n", ctypes.c_int), ("start", c_fp), ("sidx", c_fp), ("spts", c_fp)]
+def _ctype(decl, structs, consts, owner):
+    """(name, ctype) of one parameter or struct field `T name` / `T name[N]`.  A pointer is c_fp unless NEAT_HOST leads its type: then
+    POINTER(T), or POINTER(c_fp) for a table of pointers (`T* const*`).  Anything else than that raises: nothing defaults to void*."""
+    m = re.fullmatch(r"(.*[\s*])(\w+)(?:\[(\w+)\])?", decl.strip(), flags=re.S)
+    words = re.sub(r"\bconst\b", " ", m.group(1)).replace("*", " * ").split() if m else []
+    host, stars = words[:1] == ["NEAT_HOST"], words.count("*")
+    base = " ".join(w for w in words[host:] if w != "*")
+    elem = _SCALARS.get(base) or structs.get(base)
+    if stars == 0:
+        t = _SCALARS.get(base)
+    elif stars > 2 or not (elem or base == "void"):
+        t = None
+    elif not host:
+        t = c_fp
+    else:
+        t = ctypes.POINTER(c_fp) if stars == 2 else elem and ctypes.POINTER(elem)
+    count = m and m.group(3) and consts.get(m.group(3), m.group(3))
+    if t is None or (count and not str(count).isdigit()):
+        raise RuntimeError(f"neat_hip.h: cannot bind `{' '.join(decl.split())}` of {owner}: not a type the binding knows")
+    return m.group(2), t * int(count) if count else t
 
 
-_SIGNATURES = {
-    "neat_abi_version": (ctypes.c_int, []),
-    "neat_packed_floats": (ctypes.c_size_t, [ctypes.c_int]),
-    "neat_pack_weights": (ctypes.c_int, [ctypes.POINTER(NetParams), c_fp, ctypes.c_int, c_fp]),
-    "neat_eik_points": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "neat_camera_rays": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_sdf_ws_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "neat_sdf_forward": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_sdf_backward": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp,
-                                         ctypes.POINTER(NetGrads), c_fp]),
-    "neat_sdf_backward_x": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, c_fp,
-                                           c_fp, c_fp, ctypes.POINTER(NetGrads), c_fp, c_fp]),
-    "neat_heads_ws_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "neat_heads_forward": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp,
-                                          c_fp, c_fp, c_fp]),
-    "neat_render_ws_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "neat_render_forward": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           c_fp, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_fp,
-                                           c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "neat_render_eval_ws_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "neat_render_forward_eval": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                c_fp, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_fp,
-                                                c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_render_backward": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int, c_fp, ctypes.c_float, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.POINTER(NetGrads), c_fp, c_fp,
-                                            c_fp]),
-    "neat_sampler_bound": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp,
-                                          ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_sampler_resample": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_float,
-                                             c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_sampler_finish": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_float,
-                                           ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_sample_pdf": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "neat_uniform_depths": (ctypes.c_int, [c_fp, ctypes.c_float, c_fp, ctypes.c_float, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "neat_sdf_values_gated": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float,
-                                             ctypes.c_float, c_fp, c_fp, c_fp, ctypes.c_int, c_fp]),
-    "neat_sdf_values_rays": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, ctypes.c_int, c_fp]),
-    "neat_sampler_init": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, ctypes.c_int,
-                                         c_fp]),
-    "neat_sampler_bound_dev": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp,
-                                              ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp]),
-    "neat_sampler_resample_dev": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_float,
-                                                 c_fp, ctypes.c_int, c_fp, c_fp, c_fp,
-                                                 c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, ctypes.c_int,
-                                                 c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp]),
-    "neat_sampler_finish_dev": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_float,
-                                               ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_sdf_ldp": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "neat_adam_step_coef": (ctypes.c_int, [c_fp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, c_fp, c_fp,
-                                           c_fp, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_fp]),
-    "neat_loss_lines_terms": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_float, c_fp, c_fp, ctypes.c_float,
-                                             c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int,
-                                             c_fp, c_fp, c_fp, c_fp, ctypes.c_float, c_fp, c_fp, c_fp, c_fp]),
-    "neat_camera_setup": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_project2d_pair": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_sdf_values_laid_out": (ctypes.c_int, [c_fp, ctypes.POINTER(NetParams), ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, ctypes.c_int, c_fp]),
-    "neat_sampler_init_rays": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "neat_sampler_round": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp]),
-    "neat_sampler_finish_picked": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_encode_lines": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_gather_batch": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_int,
-                                         c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_copy_batch": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, c_fp]),
-    "neat_ffn_forward": (ctypes.c_int, [c_fp, ctypes.c_int] + [c_fp] * 10),
-    "neat_ffn_backward": (ctypes.c_int, [c_fp, ctypes.c_int] + [c_fp] * 15),
-    "neat_l3d": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "neat_junction_cost": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "neat_junction_gate": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp,
-                                          c_fp, c_fp, c_fp]),
-    "neat_loss_terms": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int,
-                                       c_fp, c_fp, c_fp, c_fp, ctypes.c_float, c_fp]),
-    "neat_loss_pairs": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp,
-                                       c_fp, c_fp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_camera_mats": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_inv_small": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "neat_project2d": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "neat_project2d_backward": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_line_loss": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_float, c_fp, c_fp, c_fp, c_fp]),
-    "neat_line_losses": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_float, c_fp, c_fp, ctypes.c_float, c_fp]),
-    "neat_adam_step": (ctypes.c_int, [c_fp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int),
-                                      ctypes.c_int, c_fp, c_fp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_fp]),
-    "neat_lsap_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "neat_lsap": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_dbscan_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "neat_dbscan_means": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_parse_match": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, c_fp, c_fp]),
-    "neat_parse_group_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "neat_parse_group": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_parse_vote_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "neat_parse_vote": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_parse_graph_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "neat_parse_graph": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, c_fp, c_fp, ctypes.c_int,
-                                        c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_parse_visibility_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "neat_parse_visibility": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_float,
-                                             ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_grid_points": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_fp]),
-    "neat_mesh_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "neat_mesh_count": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp, c_fp, c_fp]),
-    "neat_mesh_emit": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
-                                      ctypes.POINTER(ctypes.c_double), ctypes.c_float, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp]),
-    "neat_unit_rows3": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp]),
-    "neat_grid_points_affine": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-                                + [ctypes.POINTER(ctypes.c_double)] * 4 + [c_fp]),
-    "neat_mesh_moments_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "neat_mesh_moments": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), c_fp, c_fp, c_fp, c_fp]),
-    "neat_affine_rows3": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), c_fp]),
-    "neat_affine_bounds3_ws_bytes": (ctypes.c_size_t, []),
-    "neat_affine_bounds3": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), c_fp, c_fp, c_fp]),
-    "neat_mesh_cut_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_mesh_cut_emit": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_fp, c_fp, c_fp, c_fp,
-                                          ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp]),
-    "neat_eval_grid_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "neat_eval_grid": (ctypes.c_int, [c_fp, ctypes.POINTER(EvalGrid), c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_eval_thin_round": (ctypes.c_int, [c_fp, ctypes.POINTER(EvalGrid), ctypes.c_double, c_fp, c_fp, c_fp]),
-    "neat_eval_nearest": (ctypes.c_int, [ctypes.POINTER(EvalGrid), c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, c_fp]),
-    "neat_eval_obs_mask": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                          ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_fp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
-                                          c_fp, c_fp]),
-    "neat_eval_tri_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "neat_eval_tri_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, c_fp]),
-    "neat_eval_tri_emit": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_double, c_fp, c_fp, ctypes.c_int, c_fp]),
-    "neat_eval_line_cost": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "neat_show_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
-    "neat_show_ws_layout": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)]),
-    "neat_show_clear": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "neat_show_mesh": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                      c_fp, c_fp]),
-    "neat_show_lines": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_fp, c_fp]),
-    "neat_show_points": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_fp, c_fp]),
-    "neat_show_resolve": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.POINTER(ctypes.c_double), c_fp, c_fp, c_fp]),
-    "neat_frame_put": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_frame_sum_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
-    "neat_frame_sum": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
-    "neat_frame_range_ws_bytes": (ctypes.c_size_t, []),
-    "neat_frame_range": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
-    "neat_frame_grey": (ctypes.c_int, [c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp]),
-    "neat_frame_grid": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "neat_trace_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "neat_trace_list_offset": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "neat_trace_init": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_fp, c_fp, c_fp, c_fp]),
-    "neat_trace_step": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
-                                       ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "neat_trace_finish": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_trace_target_rays": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                              ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_raycast_bvh_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "neat_raycast_ws_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "neat_raycast_build": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_raycast_cast": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_post_fuse_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
-    "neat_post_fuse": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float,
-                                      ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_post_select": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_post_refine_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
-    "neat_post_refine_view": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp,
-                                             ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_fp, c_fp, c_fp, c_fp]),
-    "neat_post_snap_ws_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
-    "neat_post_snap": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_detect_label": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "neat_detect_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
-    "neat_detect_lines": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_fp, c_fp, ctypes.c_int]
-                          + [ctypes.c_double] * 6 + [ctypes.c_int, c_fp, ctypes.c_int] + [c_fp] * 7),
-    "neat_tri_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
-    "neat_tri_count": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_double,
-                                      ctypes.c_double, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "neat_tri_fill": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_double, ctypes.c_double,
-                                     c_fp, ctypes.c_longlong, c_fp, c_fp, c_fp, c_fp]),
-    "neat_tri_lines": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_longlong,
-                                      c_fp, c_fp, c_fp, ctypes.c_double, ctypes.c_double, ctypes.c_int] + [c_fp] * 10),
-    "neat_scenegen_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
-    "neat_scenegen_shade": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp] + [ctypes.c_int] * 4 + [ctypes.c_double] * 3 + [c_fp] * 3),
-    "neat_scenegen_edge_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, c_fp, c_fp]
-                                 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 + [c_fp] * 3),
-    "neat_scenegen_edge_fill": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp] + [ctypes.c_int] * 3
-                                + [ctypes.c_double] * 4 + [c_fp, ctypes.c_longlong] + [c_fp] * 5),
-    "neat_volume_weights": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "neat_set_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "neat_prof_enable": (ctypes.c_int, [ctypes.c_int]),
-    "neat_prof_collect": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
-}
+def parse_header(text):
+    """(constants, structs, signatures) of a header written like include/neat_hip.h: `#define NAME integer`, `typedef struct [tag] {...} name;`
+    -> ctypes.Structure classes with the header's field names and order, `int|size_t name(parameters);` -> name -> (restype, argtypes).
+    Whatever else is left outside comments and preprocessor lines raises a RuntimeError."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts = {k: int(v) for k, v in re.findall(r"^#define (\w+) (-?\d+)\s*$", text, flags=re.M)}
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    structs, signatures = {}, {}
+
+    def struct(m):
+        fields = [_ctype(d, structs, consts, m.group(2)) for d in m.group(1).split(";") if d.strip()]
+        structs[m.group(2)] = type(_STRUCTS.get(m.group(2), m.group(2)), (ctypes.Structure,), {"_fields_": fields})
+        return ""
+
+    def function(m):
+        res, name, params = m.groups()
+        params = [] if params.strip() == "void" else params.split(",")
+        signatures[name] = (_SCALARS[res], [_ctype(p, structs, consts, name)[1] for p in params])
+        return ""
+
+    text = re.sub(r"\btypedef struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+    text = re.sub(r"\b(int|size_t)\s+(\w+)\s*\(([^()]*)\)\s*;", function, text)
+    rest = re.sub(r'extern "C" \{|\}', "", text).split()
+    if rest:
+        raise RuntimeError(f"neat_hip.h: not a declaration the binding knows, near `{' '.join(rest[:8])}`")
+    return consts, structs, signatures
+
+
+def _bind():
+    """Reads the header once: from then on NUM_LAYERS, NetParams, NetGrads, EvalGrid and _SIGNATURES are module attributes."""
+    g = globals()
+    if "_SIGNATURES" not in g:
+        if not os.path.exists(HEADER_PATH):
+            raise RuntimeError(f"{HEADER_PATH} is missing: neat_amd reads its ctypes binding from that header and keeps no second copy of it.")
+        consts, structs, signatures = parse_header(open(HEADER_PATH).read())
+        g.update({attr: structs[name] for name, attr in _STRUCTS.items()}, NUM_LAYERS=consts["NEAT_NUM_LAYERS"], _SIGNATURES=signatures)
+    return g["_SIGNATURES"]
+
+
+def __getattr__(name):      # the header-derived attributes, on their first use
+    if name in ("NUM_LAYERS", "_SIGNATURES", *_STRUCTS.values()):
+        _bind()
+        return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 
 _lib = None
 
 
 def exported_symbols():
-    """Names declared in include/neat_hip.h (kept in sync by tests/test_abi.py)."""
-    return sorted(_SIGNATURES)
+    """Names of the entry points that include/neat_hip.h declares (the binding is read from that header)."""
+    return sorted(_bind())
 
 
 tuning_overrides = []      # the NEAT_TUNING key=value pairs applied when the library was loaded (bench.py records them)
@@ -236,7 +113,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or neat_amd/csrc/build.sh).  neat_amd has no CPU/PyTorch fallback for the hot path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in _bind().items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

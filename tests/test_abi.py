@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol that
-include/neat_hip.h declares; the Python binding declares the same set.  No compute calls (no GPU here)."""
+include/neat_hip.h declares; the Python binding, which neat_amd/_lib.py reads from that header, declares the same set with the
+types an independent reading of the header gives.  No compute calls (no GPU here)."""
 import ctypes
 import os
 import re
@@ -27,6 +28,138 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"{n} declared in include/neat_hip.h but not exported"
     assert names == _lib.exported_symbols()
     assert _lib.lib().neat_abi_version() == _lib.ABI_VERSION
+
+
+def test_binding_agrees_with_an_independent_reading_of_the_header():
+    """neat_amd/_lib.py derives restype / argtypes from include/neat_hip.h; this reads the header a second time, with its own
+    expressions and without _lib's parser, and checks every entry: return type, argument count, every scalar's ctype, c_void_p for
+    every unmarked pointer, and for every NEAT_HOST pointer a POINTER whose element type is the declared base type."""
+    from neat_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "neat_hip.h")).read(), flags=re.S)
+    scalar = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+              "size_t": ctypes.c_size_t, "unsigned char": ctypes.c_ubyte}
+    struct = {"neat_net_params": _lib.NetParams, "neat_net_grads": _lib.NetGrads, "neat_eval_grid_t": _lib.EvalGrid}
+    assert _lib.c_fp is ctypes.c_void_p
+    seen, host = [], 0
+    for res, name, params in re.findall(r"^(int|size_t) (neat_[a-z0-9_]+)\(([^)]*)\);", text, flags=re.M):
+        seen.append(name)
+        restype, argtypes = _lib._SIGNATURES[name]
+        assert restype is scalar[res], name
+        params = [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+        assert len(params) == len(argtypes), (name, params)
+        for p, got in zip(params, argtypes):
+            ty = p[:p.rindex(" ")]                                   # without the parameter's name
+            if "*" not in ty:
+                assert got is scalar[ty], (name, p)
+            elif not ty.startswith("NEAT_HOST "):
+                assert "NEAT_HOST" not in ty and got is ctypes.c_void_p, (name, p)
+            else:
+                host += 1
+                base, stars = re.fullmatch(r"NEAT_HOST (?:const )?([a-z_ ]+?)(\*| ?\* ?const ?\*)", ty).groups()
+                want = ctypes.c_void_p if stars.count("*") == 2 else scalar.get(base) or struct[base]
+                assert got is ctypes.POINTER(want) and got._type_ is want, (name, p)
+    assert len(seen) >= 134 and len(set(seen)) == len(seen) and sorted(seen) == _lib.exported_symbols() == header_functions()
+    assert host >= 49          # the 46 positions the hand-written table typed, and neat_copy_batch's three tables
+
+
+HEADER_FORMS = """
+/* a comment, with (parentheses), commas and a prototype: int neat_not_this(int a, float b); */
+#ifndef X_H
+#define X_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define NEAT_HOST   /* expands to nothing */
+#define NEAT_NUM_LAYERS 3   /* layers */
+#define NEAT_F32 0
+typedef struct neat_tagged {
+  const float* v[NEAT_NUM_LAYERS];
+  float* dv[2];
+} neat_tagged;
+typedef struct {
+  double origin[3];
+  double cell;
+  int n;
+  const int* start;
+} neat_plain_t;
+int neat_none(void);
+size_t neat_scalars(int a, float b, double c, long long d, size_t e);
+int neat_pointers(const float* a /* [n,3], (row-major), see f(x, y) */, float* b, unsigned char* c, const long long* d,
+                  const void* bvh, void* stream);
+int neat_host(NEAT_HOST const double* a, NEAT_HOST int* b, NEAT_HOST const void* const* c, NEAT_HOST void* const* d,
+              NEAT_HOST const long long* e, NEAT_HOST size_t* f, NEAT_HOST unsigned char* g, NEAT_HOST const neat_tagged* s,
+              NEAT_HOST const neat_plain_t* t, const neat_plain_t* dev);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_parser_on_every_declaration_form():
+    from ctypes import POINTER, c_double, c_float, c_int, c_longlong, c_size_t, c_ubyte, c_void_p
+    from neat_amd import _lib
+    consts, structs, sigs = _lib.parse_header(HEADER_FORMS)
+    assert consts == {"NEAT_NUM_LAYERS": 3, "NEAT_F32": 0}
+    assert list(structs) == ["neat_tagged", "neat_plain_t"] and all(issubclass(s, ctypes.Structure) for s in structs.values())
+    tagged, plain = structs["neat_tagged"], structs["neat_plain_t"]
+    assert [(n, t._type_, t._length_) for n, t in tagged._fields_] == [("v", c_void_p, 3), ("dv", c_void_p, 2)]
+    assert [n for n, _ in plain._fields_] == ["origin", "cell", "n", "start"]
+    assert plain._fields_[0][1]._type_ is c_double and plain._fields_[0][1]._length_ == 3
+    assert [t for _, t in plain._fields_[1:]] == [c_double, c_int, c_void_p]
+    assert ctypes.sizeof(tagged) == 40 and ctypes.sizeof(plain) == 48 and plain.start.offset == 40
+    assert list(sigs) == ["neat_none", "neat_scalars", "neat_pointers", "neat_host"]
+    assert sigs["neat_none"] == (c_int, [])
+    assert sigs["neat_scalars"] == (c_size_t, [c_int, c_float, c_double, c_longlong, c_size_t])
+    assert sigs["neat_pointers"] == (c_int, [c_void_p] * 6)
+    assert sigs["neat_host"] == (c_int, [POINTER(c_double), POINTER(c_int), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_longlong),
+                                         POINTER(c_size_t), POINTER(c_ubyte), POINTER(tagged), POINTER(plain), c_void_p])
+    # what the parser does not know raises and names the entry and the parameter; nothing becomes void* by default
+    for bad, words in (("int neat_bad(int a, short b);", ("neat_bad", "short b")),
+                       ("int neat_bad(const short* p);", ("neat_bad", "short* p")),
+                       ("int neat_bad(NEAT_HOST const neat_unknown_t* p);", ("neat_bad", "neat_unknown_t* p")),
+                       ("int neat_bad(const float NEAT_HOST* p);", ("neat_bad", "float NEAT_HOST* p")),
+                       ("int neat_bad(NEAT_HOST const void* p);", ("neat_bad", "void* p")),
+                       ("int neat_bad(float*** p);", ("neat_bad", "float*** p")),
+                       ("int neat_bad(int a,);", ("neat_bad",)),
+                       ("typedef struct { int n[NEAT_UNKNOWN]; } neat_bad_t;", ("neat_bad_t", "n[NEAT_UNKNOWN]")),
+                       ("short neat_bad(int a);", ("short neat_bad",)),
+                       ("unsigned int neat_bad(void);", ("unsigned",)),
+                       ("int neat_bad(int a)", ("neat_bad",))):
+        with pytest.raises(RuntimeError) as e:
+            _lib.parse_header(HEADER_FORMS + bad)
+        assert all(w in str(e.value) for w in words), (bad, str(e.value))
+
+
+def test_missing_header_raises_like_a_missing_library(monkeypatch):
+    from neat_amd import _lib
+    monkeypatch.delitem(vars(_lib), "_SIGNATURES", raising=False)          # as before the first read; put back afterwards
+    monkeypatch.setattr(_lib, "HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
+    with pytest.raises(RuntimeError, match="no_such_header.h is missing"):
+        _lib.exported_symbols()
+
+
+def test_struct_layouts_and_header_constants_are_pinned():
+    """The structs Python fills are built from the header's typedefs: their sizes, field names and order are what the call sites
+    (.v[i], .dv[i], positional EvalGrid(...)) and the library's own layout rely on."""
+    from neat_amd import _lib
+    assert _lib.NUM_LAYERS == 19
+    assert ctypes.sizeof(_lib.NetParams) == ctypes.sizeof(_lib.NetGrads) == 3 * 19 * 8
+    assert ctypes.sizeof(_lib.EvalGrid) == 80
+    assert [n for n, _ in _lib.EvalGrid._fields_] == ["origin", "cell", "dim", "buckets", "dense", "n", "start", "sidx", "spts"]
+    assert _lib.EvalGrid.start.offset == 56
+    assert [n for n, _ in _lib.NetParams._fields_] == ["v", "g", "b"] and [n for n, _ in _lib.NetGrads._fields_] == ["dv", "dg", "db"]
+    for cls in (_lib.NetParams, _lib.NetGrads):
+        assert all(t._type_ is ctypes.c_void_p and t._length_ == 19 for _, t in cls._fields_)
+    text = open(os.path.join(ROOT, "include", "neat_hip.h")).read()
+    defines = {k: int(v) for k, v in re.findall(r"^#define (NEAT_[A-Z0-9_]+) (\d+)\b", text, flags=re.M)}
+    assert defines["NEAT_NUM_LAYERS"] == _lib.NUM_LAYERS
+    names = {"fp32": "NEAT_F32", "bf16": "NEAT_BF16", "bf16x3": "NEAT_BF16X3", "fp16": "NEAT_F16", "fp16x3": "NEAT_F16X3"}
+    assert set(names) == set(_lib.PRECISIONS)
+    for key, define in names.items():
+        assert _lib.PRECISIONS[key] == defines[define], key
+    assert _lib.ABI_VERSION == 15
 
 
 def test_workspace_queries_are_consistent():
