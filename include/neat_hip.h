@@ -703,6 +703,23 @@ int neat_raycast_build(const double* verts, int nv, const int* faces, int nf, vo
 int neat_raycast_cast(const void* bvh, int nf, const float* origins, const float* dirs, const float* t_min, const float* t_max, int R, int any_hit,
                       float* t, int* tri, float* uv, unsigned* counts, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): the closest point on the mesh of a tree that neat_raycast_build
+ * made (neat_amd/raycast.py closest, line_distance; what open3d's and sklearn's nearest-neighbour queries against the vertices of the
+ * ground-truth mesh stand in for in code/evaluation/eval-lsr-scannet.py).  The rule (Ericson, Real-Time Collision Detection 5.1.5,
+ * decided in float64 without fused multiply-adds, ties in the squared distance to the lowest face index), the bound of the walk and
+ * its argument: neat_amd/csrc/kernels_closest.hpp; tests/closest_f64.py restates the rule in float64.  The result is the
+ * brute-force minimum over all triangles under that rule.  Asynchronous on the stream, no workspace, no allocation, no atomics: two
+ * runs give the same bytes.
+ *
+ * neat_raycast_closest : bvh, nf as neat_raycast_cast takes them; points [N,3] float64; a triangle is accepted iff its squared
+ *   distance is <= max_d2 (inclusive; +inf: no bound).  d2 [N] the squared distance (+inf on a miss), tri [N] the original face index
+ *   (-1 on a miss), point [N,3] the closest point and uv [N,2] its barycentrics (point = (1 - u - v) v0 + u v1 + v v2; both 0 on a
+ *   miss), counts [N,2] uint32 (node boxes tested, triangles tested) or null.  A query with a non-finite coordinate, the empty tree and
+ *   the tree of a refused build (status 1) give misses.  Returns -1 before any launch for N < 0, nf outside the build's range, max_d2
+ *   negative or NaN, or a null bvh, points, d2, tri, point or uv with N > 0. */
+int neat_raycast_closest(const void* bvh, int nf, const double* points, int N, double max_d2, double* d2, int* tri, double* point, double* uv,
+                         unsigned* counts, void* stream);
+
 /* ---- added to ABI v15 (new symbols only, so the version number stays): 2-D line segments of the views (neat_amd/detect.py), the
  * files <scene>/<line_detector>/<image>.json that the datasets read.  An a-contrario detector of the LSD family over the line-support
  * regions of Burns, Hanson and Riseman; the rule: DESIGN 3j and neat_amd/csrc/kernels_detect.hpp, restated in float64 by

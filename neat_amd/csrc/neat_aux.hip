@@ -15,6 +15,7 @@
 #include "kernels_trace.hpp"
 #include "kernels_post.hpp"
 #include "kernels_raycast.hpp"
+#include "kernels_closest.hpp"
 #include "kernels_scenegen.hpp"
 #include "kernels_detect.hpp"
 #include "kernels_triangulate.hpp"
@@ -1209,6 +1210,19 @@ int neat_raycast_cast(const void* bvh, int nf, const float* origins, const float
     hipLaunchKernelGGL(raycast_cast_kernel<false>, grid1(R, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, (const float*)w.nodes,
                          (const double*)w.tris, nf, w.L, origins, dirs, t_min, t_max,
                        R, t, tri, uv, counts);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: the closest point on the mesh of a tree (kernels_closest.hpp) ------------------------------------------------------------
+int neat_raycast_closest(const void* bvh, int nf, const double* points, int N, double max_d2, double* d2, int* tri, double* point, double* uv,
+                         unsigned* counts, void* stream) {
+  RaycastWs w;
+  if (!bvh || ((uintptr_t)bvh & 255) || !raycast_layout(const_cast<void*>(bvh), nullptr, nf, RC_WG, RC_TRI_STRIDE, &w) || N < 0 || N > INT_MAX / 4 ||
+      !(max_d2 >= 0.0)) return -1;                                        // a NaN bound too
+  if (N == 0) return 0;
+  if (!points || !d2 || !tri || !point || !uv) return -1;
+  hipLaunchKernelGGL(raycast_closest_kernel, grid1(N, RC_WG), dim3(RC_WG), 0, (hipStream_t)stream, (const float*)w.nodes, (const double*)w.tris, nf,
+                     w.L, points, N, max_d2, d2, tri, point, uv, counts);
   return (int)hipGetLastError();
 }
 

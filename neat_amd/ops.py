@@ -1494,3 +1494,25 @@ def raycast_cast(bvh, nf, origins, dirs, t_min=None, t_max=None, any_hit=False, 
     _lib.check(_lib.lib().neat_raycast_cast(_p(bvh), int(nf), _p(origins), _p(dirs), _p(lim[0]), _p(lim[1]), R, int(bool(any_hit)), _p(t), _p(tri),
                                             _p(uv), _p(counts), _stream()), "neat_raycast_cast")
     return t, tri, uv
+
+
+def raycast_closest(bvh, nf, points, max_d2=float("inf"), counts=None):
+    """points [N,3] float64 on the device -> (d2 [N] float64, +inf on a miss; tri [N] int32, -1 on a miss; point [N,3] float64, the closest
+    point of the mesh; uv [N,2] float64, its barycentrics: both zero on a miss).  A triangle is accepted iff its squared distance is
+    <= max_d2.  counts: a contiguous [N,2] tensor of 4-byte integers receives (node boxes tested, triangles tested) per query."""
+    if not points.is_cuda or points.dtype != torch.float64:
+        raise RuntimeError("raycast_closest: points float64 on the device (no CPU path): got %s on %s" % (points.dtype, points.device))
+    points = points.detach().contiguous()
+    N = int(points.shape[0])
+    max_d2 = float(max_d2)
+    if points.shape != (N, 3) or not max_d2 >= 0.0:
+        raise ValueError("raycast_closest: points [N, 3], max_d2 >= 0")
+    if counts is not None and (not counts.is_cuda or counts.element_size() != 4 or counts.is_floating_point() or tuple(counts.shape) != (N, 2)
+                               or not counts.is_contiguous()):
+        raise ValueError("raycast_closest: counts is a contiguous [N, 2] tensor of 4-byte integers on the device")
+    dev = points.device
+    d2, tri = torch.empty(N, device=dev, dtype=torch.float64), torch.empty(N, device=dev, dtype=torch.int32)
+    point, uv = torch.empty(N, 3, device=dev, dtype=torch.float64), torch.empty(N, 2, device=dev, dtype=torch.float64)
+    _lib.check(_lib.lib().neat_raycast_closest(_p(bvh), int(nf), _p(points), N, max_d2, _p(d2), _p(tri), _p(point), _p(uv), _p(counts), _stream()),
+               "neat_raycast_closest")
+    return d2, tri, point, uv

@@ -6,11 +6,15 @@
     depth, normal, tri = raycast.view(scene, pose, intrinsics, H, W)
     seen = raycast.visible_points(scene, points, cams, bias=0.01)        # bool [F, N]
     frac = raycast.visible_lines(scene, lines3d, cams, samples=16)       # float32 [F, N]
+    dist, tri, point, uv = raycast.closest(scene, points, max_dist=inf)  # float64: the closest point of the surface
+    dist = raycast.line_distance(scene, lines3d, samples=32)             # float64 [n, samples]
 
     python -m neat_amd.raycast check --mesh M.ply|M.obj --data X-wfi.npz|X-neat.pth (--conf <run>/runconf.conf | --cams cameras.npz)
         [--min-views 5] [--min-frac 0.5] [--bias 0.01] [--samples 16] [--data_root ../data] [--gpu 0] [--json] [--overwrite]
     python -m neat_amd.raycast analysis --conf <conf> --scan <dir with lines.json, offset_scale.txt, mesh.obj> [--data_root ../data]
         [--gpu 0] [--json]
+    python -m neat_amd.raycast distance --mesh M.ply|M.obj (--data X.npz | --points P.ply) [--samples 32] [--threshold 0.05] [--max-dist d]
+        [--scale-file offset_scale.txt] [--gpu 0] [--json] [--overwrite]
 
 The mesh may be ground truth, a surface_*.ply of neat_amd.mesh or anyone's reconstruction; no checkpoint is needed.  The rule of
 intersection (Woop, Benthin, Wald 2013, decided in float64: both windings, edges inclusive, a hit has t_min <= t < t_max, ties in t go to
@@ -23,6 +27,12 @@ every ray misses.  There is no host fallback.
 cameras see at least --min-frac of its --samples points) and the same three arrays, written to `<data stem>_occlmesh.npz`.
 `analysis` is the reference's occlusion-aware ceiling (evaluation/abc-analysis.py :58-182): which ground-truth junctions and lines of an
 ABC scan each camera really sees past the ground-truth mesh, and how many of those the 2-D detections of the view recover.
+`distance` asks how far things are from the surface itself, not from its vertices (the closest point on the mesh by the region
+rule of Ericson 5.1.5 in float64, the brute-force minimum over all triangles, ties to the lowest face index).  With --data it samples
+every line as evaluation/eval-lsr-scannet.py :94-95 does and writes `<data stem>_dist.npz`: dist [n,samples], mean [n], max [n], tri
+[n,samples], on_surface [n] (max <= --threshold).  With --points the vertices of a PLY are the queries and `<stem>_dist.npz` holds dist,
+tri and point; it prints Acc (the mean distance), the median and Prec (the share nearer than --threshold); run it both ways round for
+the two-sided figures.  A mesh with a face index outside its vertices is an error (exit code 1), not a result.
 """
 import argparse
 import json
@@ -155,6 +165,47 @@ def visible_lines(scene, lines3d, cams, *, samples=16, bias=0.01):
     return _visible(scene, lines3d, cams, int(samples), bias).float().mean(dim=-1)
 
 
+@torch.no_grad()
+def closest(scene, points, max_dist=float("inf"), counts=None):
+    """points [N,3] (any float type, on the scene's device; they are widened to float64) -> (dist [N] float64, the distance to the closest
+    point of the mesh, +inf on a miss; tri [N] int32, its face index, -1 on a miss; point [N,3] float64, the closest point; uv [N,2]
+    float64, its barycentrics, point = (1 - u - v) v0 + u v1 + v v2: both zero on a miss).  A triangle further than max_dist is not
+    accepted (the bound is inclusive on the squared distance, max_dist^2 in float64).  A point with a non-finite coordinate misses, and
+    so does every point when scene.status = 1.  counts: a [N,2] tensor of 4-byte integers on the device receives (node boxes tested,
+    triangles tested) per query.  The rule: DESIGN 3m, tests/closest_f64.py."""
+    from . import ops
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise ValueError("raycast.closest: max_dist >= 0")
+    max_d2 = max_dist * max_dist
+    dev = scene.device
+    pts = torch.as_tensor(points).detach().to(dev, torch.float64).reshape(-1, 3).contiguous()
+    with torch.cuda.device(dev):
+        # the queries go in the order given: sorting them along a Morton curve first was measured and is not worth its code (DESIGN 3m)
+        d2, tri, point, uv = ops.raycast_closest(scene.bvh, scene.nf, pts, max_d2, counts)
+        return torch.sqrt(d2), tri, point, uv
+
+
+def line_points(lines3d, samples):
+    """lines3d [n,2,3] float64 tensor -> the sample points a t + b (1 - t), t = linspace(0, 1, samples), [n, samples, 3]
+    (evaluation/eval-lsr-scannet.py :94-95: the first sample is the second end point)."""
+    t = torch.from_numpy(np.linspace(0.0, 1.0, samples)).to(lines3d.device).view(1, -1, 1)       # numpy's linspace, to the last bit
+    return lines3d[:, :1] * t + lines3d[:, 1:] * (1.0 - t)
+
+
+@torch.no_grad()
+def line_distance(scene, lines3d, samples=32, max_dist=float("inf"), with_tri=False):
+    """lines3d [n,2,3] -> dist float64 [n, samples] on the device: the distance of each sample point of line_points to the mesh
+    (with_tri: also tri int32 [n, samples])."""
+    if samples < 2:
+        raise ValueError("raycast.line_distance: samples >= 2")
+    lines = torch.as_tensor(lines3d).detach().to(scene.device, torch.float64).reshape(-1, 2, 3)
+    n = int(lines.shape[0])
+    dist, tri, _, _ = closest(scene, line_points(lines, int(samples)).reshape(-1, 3), max_dist)
+    dist, tri = dist.view(n, samples), tri.view(n, samples)
+    return (dist, tri) if with_tri else dist
+
+
 # ------------------------------------------------------------------ command line
 def out_path(data):
     """`<data stem>_occlmesh.npz` beside the input."""
@@ -202,6 +253,17 @@ def build_parser():
     an.add_argument("--data_root", default="../data", help="root of the dataset's data_dir")
     an.add_argument("--gpu", default=0, type=int, help="device index")
     an.add_argument("--json", default=False, action="store_true", help="print one JSON object with the six numbers")
+    di = sub.add_parser("distance", help="how far the lines of a wireframe, or the points of a cloud, are from a triangle mesh")
+    di.add_argument("--mesh", type=str, required=True, help="the surface: a .ply or .obj triangle mesh")
+    di.add_argument("--data", type=str, default=None, help="a wireframe: an .npz with `lines3d`, or a -neat.pth")
+    di.add_argument("--points", type=str, default=None, help="a .ply cloud or mesh: its vertices are the queries")
+    di.add_argument("--samples", default=32, type=int, help="points per line")
+    di.add_argument("--threshold", default=0.05, type=float, help="a line lies on the surface when no sample is further; Prec counts the points nearer")
+    di.add_argument("--max-dist", default=float("inf"), type=float, help="nothing further than this is looked for: the distance is then inf")
+    di.add_argument("--scale-file", type=str, default=None, help="an offset_scale.txt: the lines or points are x / scale - offset in the mesh's frame")
+    di.add_argument("--gpu", default=0, type=int, help="device index")
+    di.add_argument("--json", default=False, action="store_true", help="print one JSON object with the summary and the seconds")
+    di.add_argument("--overwrite", default=False, action="store_true", help="rewrite a _dist.npz that is already on disk")
     return ap
 
 
@@ -215,6 +277,15 @@ def parse_args(argv=None):
             ap.error("one of --conf and --cams")
         if os.path.splitext(opt.mesh)[1].lower() not in (".ply", ".obj"):
             ap.error("--mesh is a .ply or an .obj file")
+    if opt.command == "distance":
+        if opt.samples < 2 or not opt.threshold >= 0.0 or not opt.max_dist >= 0.0:
+            ap.error("--samples >= 2, --threshold >= 0, --max-dist >= 0")
+        if (opt.data is None) == (opt.points is None):
+            ap.error("one of --data and --points")
+        if os.path.splitext(opt.mesh)[1].lower() not in (".ply", ".obj"):
+            ap.error("--mesh is a .ply or an .obj file")
+        if opt.points is not None and not opt.points.lower().endswith(".ply"):
+            ap.error("--points is a .ply file")
     return opt
 
 
@@ -380,9 +451,80 @@ def main_analysis(opt):
     return 0
 
 
+# ---- distance
+def dist_path(data):
+    """`<stem>_dist.npz` beside the wireframe or the cloud."""
+    return os.path.splitext(data)[0] + "_dist.npz"
+
+
+def to_mesh_frame(x, scale_file):
+    """x [..., 3] in the model frame -> the frame of the scan's mesh, x / scale - offset with the four numbers of offset_scale.txt (as
+    evaluate.abc_scores maps the predictions)."""
+    with open(scale_file) as fh:
+        off = np.array([float(v) for v in fh.read().split()], dtype=np.float64)
+    return np.asarray(x, dtype=np.float64) * (1.0 / off[3]) - off[:3]
+
+
+def _savez(path, **arrays):
+    tmp = path + ".tmp.npz"
+    np.savez(tmp, **arrays)
+    os.replace(tmp, path)
+
+
+def main_distance(opt):
+    _lib.lib()
+    source = opt.data if opt.data is not None else opt.points
+    path = dist_path(source)
+    if os.path.exists(path) and not opt.overwrite:
+        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+        return 0
+    torch.cuda.set_device(opt.gpu)
+    device = torch.device("cuda", opt.gpu)
+    verts, faces = read_mesh(opt.mesh)
+    if opt.data is not None:
+        queries = run_io.load_lines(opt.data)[0]
+    else:
+        queries = np.asarray(ply.read_ply(opt.points)["points"], dtype=np.float64).reshape(-1, 3)
+    if opt.scale_file is not None:
+        queries = to_mesh_frame(queries, opt.scale_file)
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    scene = build(verts, faces, device)
+    if scene.status != 0:
+        print("error: {}: a face index lies outside the vertices".format(opt.mesh), file=sys.stderr, flush=True)
+        return 1
+    if opt.data is not None:
+        dist, tri = line_distance(scene, torch.from_numpy(queries), opt.samples, opt.max_dist, with_tri=True)
+        dist, tri = dist.cpu().numpy(), tri.cpu().numpy()
+        query_s = time.perf_counter() - t0
+        n = dist.shape[0]
+        mean, worst = dist.mean(axis=1), dist.max(axis=1)
+        on = worst <= opt.threshold
+        _savez(path, dist=dist, mean=mean, max=worst, tri=tri, on_surface=on)
+        report = {"path": path, "lines": n, "on_surface": int(on.sum()), "mean": float(mean.mean()) if n else float("nan"),
+                  "median": float(np.median(mean)) if n else float("nan"), "samples": opt.samples, "threshold": opt.threshold,
+                  "triangles": scene.nf, "query_s": query_s}
+        print("{}: {} / {} lines on the surface (every one of {} samples within {:g}); mean distance {:.6g}, median {:.6g} ({} triangles, {:.3f} s)".format(
+            path, report["on_surface"], n, opt.samples, opt.threshold, report["mean"], report["median"], scene.nf, query_s), flush=True)
+    else:
+        dist, tri, point, _ = closest(scene, torch.from_numpy(queries), opt.max_dist)
+        dist, tri, point = dist.cpu().numpy(), tri.cpu().numpy(), point.cpu().numpy()
+        query_s = time.perf_counter() - t0
+        n = dist.shape[0]
+        _savez(path, dist=dist, tri=tri, point=point)
+        report = {"path": path, "points": n, "acc": float(dist.mean()) if n else float("nan"), "median": float(np.median(dist)) if n else float("nan"),
+                  "prec": float((dist < opt.threshold).mean()) if n else float("nan"), "threshold": opt.threshold, "triangles": scene.nf,
+                  "query_s": query_s}
+        print("{}: {} points; Acc {:.6g}, median {:.6g}, Prec {:.4f} (nearer than {:g}) ({} triangles, {:.3f} s)".format(
+            path, n, report["acc"], report["median"], report["prec"], opt.threshold, scene.nf, query_s), flush=True)
+    if opt.json:
+        print(json.dumps(report), flush=True)
+    return 0
+
+
 def main(argv=None):
     opt = parse_args(argv)
-    return main_check(opt) if opt.command == "check" else main_analysis(opt)
+    return {"check": main_check, "analysis": main_analysis, "distance": main_distance}[opt.command](opt)
 
 
 if __name__ == "__main__":
