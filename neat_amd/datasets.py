@@ -198,7 +198,7 @@ class DeviceBatches:
     colours, labels, segments, camera) are uploaded once and stay in HBM (23 MB per DTU image); per step the host makes the n draws
     (`Dataset.draw_rays`: the same RNG stream and therefore the same pixels as __getitem__), sends 8 KB, and ONE launch
     (`neat_gather_batch`) writes uv, uv_proj, rgb, lines2d and labels.  `batch()` returns what the DataLoader's collate returns for
-    batch size 1 -- same keys, shapes and values (tests/test_gpu_parity.py::test_device_batches_equal_getitem), tensors on the device."""
+    batch size 1 -- same keys, shapes and values (tests/test_runner.py::test_device_batches_equal_getitem), tensors on the device."""
 
     def __init__(self, dataset, device):
         self.ds, self.device = dataset, torch.device(device)
