@@ -807,6 +807,32 @@ int neat_scenegen_edge_fill(const void* bvh, int nf, const double* junctions, in
                             double step, double min_len, double bias, double near, void* ws, long long N, int* idx, double* p2, double* p3,
                             unsigned char* junc, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): the crease lines of a triangle mesh (neat_amd/creases.py):
+ * the junctions and straight edges of a model read from its triangles, the lines.json that scenegen, raycast analysis and evaluate abc
+ * start from.  The rule: DESIGN 3n and neat_amd/csrc/kernels_crease.hpp, restated in float64 by tests/creases_f64.py, which the device
+ * equals array for array.  Float64 products and sums without contraction, no division or square root; stable sorts, scans and one
+ * union-find whose roots are the smallest member: two runs give the same bytes.  No allocation.  Each call reads a few words back
+ * from the workspace (so it waits for the stream once); bad arguments return -1 before any launch, -2: the sort wants more temporary
+ * storage than the workspace holds.
+ *
+ * neat_crease_scratch_bytes : the workspace (256-byte aligned, caller-owned) that the three calls share, fixed by (nv, nf); 0 when
+ *   refused: a negative count, nv > 2^26, nf > 2^24.
+ * neat_crease_edges : verts float64 [nv,3], faces int32 [nf,3]; cos_angle = cos(angle) in (-1, 1); boundary 0 / 1: keep the edges of
+ *   one face.  counts int32 [8] on the device: [0] status (0; 1 a face index outside the vertices; 2 a non-finite coordinate: nothing
+ *   else is then made), [1] welded vertices, [2] dropped faces, [3] feature edges E, [4..6] E of kind 0 crease, 1 boundary, 2
+ *   non-manifold.
+ * neat_crease_chains : E as the edges call counted it (-1 otherwise); sin2_turn = sin^2(turn) in [0, 1]; dev >= 0 the deviation as a
+ *   length.  counts int32 [4] on the device: [0] chains, [1] lines, [2] junctions.
+ * neat_crease_fill : E, n_lines, n_junc as the two calls counted them (-1 otherwise).  junctions float64 [n_junc,3] the coordinates as
+ *   given, vertex int32 [n_junc] the original index (the lowest of its welded group), ascending; lines int32 [n_lines,2] into that list,
+ *   in ascending (vertex a, vertex b), then kind, then curved; kind uint8 [n_lines]; curved uint8 [n_lines]: a piece of a chain that is
+ *   not one straight line. */
+size_t neat_crease_scratch_bytes(int nv, int nf);
+int neat_crease_edges(const double* verts, int nv, const int* faces, int nf, double cos_angle, int boundary, void* ws, int* counts, void* stream);
+int neat_crease_chains(const double* verts, int nv, int nf, int E, double sin2_turn, double dev, void* ws, int* counts, void* stream);
+int neat_crease_fill(const double* verts, int nv, int nf, int E, void* ws, int n_lines, int n_junc, double* junctions, int* vertex, int* lines,
+                     unsigned char* kind, unsigned char* curved, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

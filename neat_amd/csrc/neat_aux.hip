@@ -19,6 +19,7 @@
 #include "kernels_scenegen.hpp"
 #include "kernels_detect.hpp"
 #include "kernels_triangulate.hpp"
+#include "kernels_crease.hpp"
 #include "ws_layout.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
@@ -1418,6 +1419,166 @@ int neat_scenegen_edge_fill(const void* bvh, int nf, const double* junctions, in
   hipLaunchKernelGGL(scenegen_edge_kernel<true>, grid1(V * E, SG_WAVES), dim3(SG_WG), 0, (hipStream_t)stream, (const float*)t.nodes,
                      (const double*)t.tris, nf, t.L, junctions, (const int*)w.edges, E, K, pose, V, H, W, step, min_len, bias, near, (int*)nullptr,
                      (const int*)w.off, (int)N, idx, p2, p3, junc);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"
+
+// ---- added to ABI v15: the crease lines of a triangle mesh (kernels_crease.hpp) -----------------------------------------------------------
+namespace {
+
+// out [n] = the exclusive scan of f over [0, n) (null: the total alone), *total = its sum
+template <class F>
+void crease_scan(int n, F f, const CreaseWs& w, int* out, int* total, hipStream_t st) {
+  const int tiles = (n + CR_SCAN_WG - 1) / CR_SCAN_WG;
+  if (tiles > 0) hipLaunchKernelGGL(crease_scan_tile_kernel<F>, dim3(tiles), dim3(CR_SCAN_WG), 0, st, n, f, w.tile);
+  hipLaunchKernelGGL(crease_scan_top_kernel, dim3(1), dim3(CR_SCAN_WG), 0, st, tiles, w.tile, total);
+  if (tiles > 0 && out) hipLaunchKernelGGL(crease_scan_apply_kernel<F>, dim3(tiles), dim3(CR_SCAN_WG), 0, st, n, f, (const int*)w.tile, out);
+}
+
+int crease_sort_pairs(const CreaseWs& w, unsigned long long* kin, unsigned long long* kout, int* vin, int* vout, size_t n, unsigned bit0,
+                      unsigned bit1, hipStream_t st) {
+  size_t tb = 0;
+  NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, bit0, bit1, st));
+  if (tb > w.sort_bytes) return -2;
+  return (int)rocprim::radix_sort_pairs(w.sort, tb, kin, kout, vin, vout, n, bit0, bit1, st);
+}
+
+int crease_sort_keys(const CreaseWs& w, unsigned long long* kin, unsigned long long* kout, size_t n, hipStream_t st) {
+  size_t tb = 0;
+  NEAT_CHECK(rocprim::radix_sort_keys(nullptr, tb, kin, kout, n, 0u, 64u, st));
+  if (tb > w.sort_bytes) return -2;
+  return (int)rocprim::radix_sort_keys(w.sort, tb, kin, kout, n, 0u, 64u, st);
+}
+
+// the counts that an earlier call left in the workspace are the ones the host passes back
+int crease_state_is(const CreaseWs& w, int first, int n, const int* want, hipStream_t st) {
+  int got[3] = {0, 0, 0};
+  NEAT_CHECK(hipMemcpyAsync(got, w.state + first, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  NEAT_CHECK(hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i)
+    if (got[i] != want[i]) return -1;
+  return 0;
+}
+
+#define NEAT_PASS(expr) do { const int r_ = (expr); if (r_ != 0) return r_; } while (0)
+constexpr int CR_ST_HALVES = 2, CR_ST_CHAINS = 3, CR_ST_EDGES = 4, CR_ST_LINES = 5, CR_ST_JUNCTIONS = 6;
+
+}  // namespace
+
+extern "C" {
+
+size_t neat_crease_scratch_bytes(int nv, int nf) {
+  CreaseWs w;
+  return crease_layout(nullptr, nv, nf, CR_SCAN_WG, &w) ? w.total : 0;
+}
+
+int neat_crease_edges(const double* verts, int nv, const int* faces, int nf, double cos_angle, int boundary, void* ws, int* counts, void* stream) {
+  CreaseWs w;
+  if (!crease_layout(ws, nv, nf, CR_SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || !counts || !(cos_angle > -1.0 && cos_angle < 1.0) ||
+      (boundary != 0 && boundary != 1) || (nv > 0 && !verts) || (nf > 0 && !faces))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  NEAT_CHECK(hipMemsetAsync(counts, 0, 8 * sizeof(int), st));
+  NEAT_CHECK(hipMemsetAsync(w.state, 0, 64 * sizeof(int), st));
+  const long long words = 3ll * std::max(nv, nf);
+  if (words > 0) {
+    hipLaunchKernelGGL(crease_check_kernel, dim3((unsigned)((words + CR_WG - 1) / CR_WG)), dim3(CR_WG), 0, st, verts, nv, faces, nf, w.state);
+    NEAT_CHECK(hipGetLastError());
+  }
+  int status[2] = {0, 0};
+  NEAT_CHECK(hipMemcpyAsync(status, w.state, sizeof(status), hipMemcpyDeviceToHost, st));
+  NEAT_CHECK(hipStreamSynchronize(st));                                 // nothing below reads a vertex through an index that was not checked
+  if (status[0] || status[1]) {
+    const int s = status[0] ? 1 : 2;
+    NEAT_CHECK(hipMemcpyAsync(counts, &s, sizeof(int), hipMemcpyHostToDevice, st));
+    return (int)hipStreamSynchronize(st);
+  }
+  if (nv > 0) {
+    for (int axis = 2; axis >= 0; --axis) {
+      hipLaunchKernelGGL(crease_vkey_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, verts, nv, axis, (const int*)(axis == 2 ? nullptr : w.vb), w.ka, w.va);
+      NEAT_CHECK(hipGetLastError());
+      NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.va, w.vb, (size_t)nv, 0u, 64u, st));
+    }
+    hipLaunchKernelGGL(crease_vhead_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, verts, nv, (const int*)w.vb, w.vhead);
+    crease_scan(nv, CrNonzero{w.vhead}, w, w.vslot, counts + 1, st);
+    hipLaunchKernelGGL(crease_vrep_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, nv, (const int*)w.vb, (const int*)w.vhead, (const int*)w.vslot, w.rep);
+    hipLaunchKernelGGL(crease_weld_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, nv, (const int*)w.vb, (const int*)w.vhead, (const int*)w.vslot,
+                       (const int*)w.rep, w.weld);
+  }
+  if (nf > 0) {
+    hipLaunchKernelGGL(crease_face_kernel, grid1(nf, CR_WG), dim3(CR_WG), 0, st, verts, faces, nf, (const int*)w.weld, w.fn, w.ka, w.va);
+    NEAT_CHECK(hipGetLastError());
+    NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.va, w.vb, (size_t)w.M, 0u, 64u, st));
+    hipLaunchKernelGGL(crease_kind_kernel, grid1(w.M, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.kb, (const int*)w.vb, w.M, faces,
+                       (const int*)w.weld, (const double*)w.fn, cos_angle, boundary, w.mark, w.state + CR_ST_HALVES);
+    crease_scan(w.M, CrNonzero{w.mark}, w, w.slot, counts + 3, st);
+    for (int kind = 0; kind < 3; ++kind) crease_scan(w.M, CrEquals{w.mark, kind + 1}, w, nullptr, counts + 4 + kind, st);
+    hipLaunchKernelGGL(crease_edge_kernel, grid1(w.M, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.kb, w.M, (const int*)w.mark,
+                       (const int*)w.slot, w.elo, w.ehi, w.ekind);
+  }
+  hipLaunchKernelGGL(crease_edges_counts_kernel, dim3(1), dim3(1), 0, st, nf, (const int*)(w.state + CR_ST_HALVES), counts);
+  NEAT_CHECK(hipGetLastError());
+  return (int)hipMemcpyAsync(w.state + CR_ST_EDGES, counts + 3, sizeof(int), hipMemcpyDeviceToDevice, st);
+}
+
+int neat_crease_chains(const double* verts, int nv, int nf, int E, double sin2_turn, double dev, void* ws, int* counts, void* stream) {
+  CreaseWs w;
+  if (!crease_layout(ws, nv, nf, CR_SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || !counts || E < 0 || E > w.M || !(sin2_turn >= 0.0 && sin2_turn <= 1.0) ||
+      !(dev >= 0.0) || !std::isfinite(dev) || (E > 0 && !verts))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  NEAT_PASS(crease_state_is(w, CR_ST_EDGES, 1, &E, st));
+  NEAT_CHECK(hipMemsetAsync(counts, 0, 4 * sizeof(int), st));
+  NEAT_CHECK(hipMemsetAsync(w.state + CR_ST_LINES, 0, 2 * sizeof(int), st));
+  if (E == 0) return 0;
+  NEAT_CHECK(hipMemsetAsync(w.vstate, 0, (size_t)nv * sizeof(int), st));
+  NEAT_CHECK(hipMemsetAsync(w.jflag, 0, (size_t)nv * sizeof(int), st));
+  hipLaunchKernelGGL(crease_incidence_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, E, (const int*)w.elo, (const int*)w.ehi, w.ka, w.parent);
+  NEAT_CHECK(hipGetLastError());
+  NEAT_PASS(crease_sort_keys(w, w.ka, w.kb, 2 * (size_t)E, st));
+  hipLaunchKernelGGL(crease_vertex_kernel, grid1(2 * E, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.kb, 2 * E, verts, (const int*)w.elo,
+                     (const int*)w.ehi, (const int*)w.ekind, sin2_turn, w.vstate, w.parent);
+  hipLaunchKernelGGL(crease_label_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, E, w.parent, w.ka);
+  NEAT_CHECK(hipGetLastError());
+  NEAT_PASS(crease_sort_keys(w, w.ka, w.ckey, (size_t)E, st));
+  hipLaunchKernelGGL(crease_chain_head_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.ckey, E, w.mark);
+  crease_scan(E, CrNonzero{w.mark}, w, w.slot, w.state + CR_ST_CHAINS, st);
+  hipLaunchKernelGGL(crease_chain_start_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, E, (const int*)w.mark, (const int*)w.slot, w.cstart);
+  hipLaunchKernelGGL(crease_chain_kernel<false>, grid1(E, CR_WAVES), dim3(CR_WG), 0, st, (const unsigned long long*)w.ckey, E,
+                     (const int*)(w.state + CR_ST_CHAINS), (const int*)w.cstart, verts, (const int*)w.elo, (const int*)w.ehi, (const int*)w.ekind,
+                     (const int*)w.vstate, dev, w.cinfo, w.cnl, w.jflag, (const int*)nullptr, 0, (unsigned long long*)nullptr, (int*)nullptr);
+  crease_scan(E, CrValue{w.cnl}, w, w.coff, counts + 1, st);
+  crease_scan(nv, CrNonzero{w.jflag}, w, w.jmap, counts + 2, st);
+  NEAT_CHECK(hipGetLastError());
+  NEAT_CHECK(hipMemcpyAsync(counts, w.state + CR_ST_CHAINS, sizeof(int), hipMemcpyDeviceToDevice, st));
+  return (int)hipMemcpyAsync(w.state + CR_ST_LINES, counts + 1, 2 * sizeof(int), hipMemcpyDeviceToDevice, st);
+}
+
+int neat_crease_fill(const double* verts, int nv, int nf, int E, void* ws, int n_lines, int n_junc, double* junctions, int* vertex, int* lines,
+                     unsigned char* kind, unsigned char* curved, void* stream) {
+  CreaseWs w;
+  if (!crease_layout(ws, nv, nf, CR_SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || E < 0 || E > w.M || n_lines < 0 || n_lines > E || n_junc < 0 ||
+      n_junc > nv || (long long)n_junc > 2ll * n_lines || (n_lines > 0 && n_junc < 2))
+    return -1;
+  if (n_lines == 0) return 0;
+  if (!verts || !junctions || !vertex || !lines || !kind || !curved) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int want[3] = {E, n_lines, n_junc};
+  NEAT_PASS(crease_state_is(w, CR_ST_EDGES, 3, want, st));
+  hipLaunchKernelGGL(crease_chain_kernel<true>, grid1(E, CR_WAVES), dim3(CR_WG), 0, st, (const unsigned long long*)w.ckey, E,
+                     (const int*)(w.state + CR_ST_CHAINS), (const int*)w.cstart, verts, (const int*)w.elo, (const int*)w.ehi, (const int*)w.ekind,
+                     (const int*)w.vstate, 0.0, w.cinfo, (int*)nullptr, (int*)nullptr, (const int*)w.coff, n_lines, w.lab, w.ltag);
+  hipLaunchKernelGGL(crease_tagkey_kernel, grid1(n_lines, CR_WG), dim3(CR_WG), 0, st, n_lines, (const int*)w.ltag, w.ka, w.va);
+  NEAT_CHECK(hipGetLastError());
+  NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.va, w.vb, (size_t)n_lines, 0u, 3u, st));
+  hipLaunchKernelGGL(crease_abkey_kernel, grid1(n_lines, CR_WG), dim3(CR_WG), 0, st, n_lines, (const int*)w.vb, (const unsigned long long*)w.lab, w.ka);
+  NEAT_CHECK(hipGetLastError());
+  NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.vb, w.va, (size_t)n_lines, 0u, 64u, st));
+  hipLaunchKernelGGL(crease_lines_kernel, grid1(n_lines, CR_WG), dim3(CR_WG), 0, st, n_lines, (const unsigned long long*)w.kb, (const int*)w.va,
+                     (const int*)w.ltag, (const int*)w.jmap, lines, kind, curved);
+  hipLaunchKernelGGL(crease_junction_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, verts, nv, (const int*)w.jflag, (const int*)w.jmap, n_junc, junctions,
+                     vertex);
   return (int)hipGetLastError();
 }
 

@@ -416,4 +416,48 @@ inline bool scenegen_layout(void* ws, int V, int E, ScenegenWs* w) {
   return true;
 }
 
+// ---- crease lines of a mesh (kernels_crease.hpp): one workspace for the three calls, fixed by (nv, nf) alone.  M = 3 nf bounds the
+// half-edges, the feature edges E, the chains and the lines; N = max(nv, 2 M) bounds every sort (vertices, half-edges, 2 E incidences).
+// state: two status words, the half-edges kept, then chains, E, lines and junctions as the calls left them | ka, kb, va, vb [N] the
+// sorts' keys and values, in and out | per vertex: weld, vhead, vslot, rep (the weld), vstate, jflag, jmap | fn [nf][4] | mark, slot [M]
+// (flags and their scans: kinds, then chain heads) | elo, ehi, ekind, parent [M] | ckey [M] the edges in chain order, cstart [M + 1],
+// cinfo [M][4], cnl, coff [M] | lab, ltag [M] the lines before their sort | tile: the scans' tile sums | the radix sort's temporary
+// storage, fixed as raycast_layout fixes it; a call asks rocprim and refuses if it wants more
+constexpr int CR_MAX_VERTS = 1 << 26;
+struct CreaseWs {
+  int M; size_t N;
+  int* state; unsigned long long *ka, *kb; int *va, *vb;
+  int *weld, *vhead, *vslot, *rep, *vstate, *jflag, *jmap;
+  double* fn; int *mark, *slot, *elo, *ehi, *ekind, *parent;
+  unsigned long long* ckey; int *cstart, *cinfo, *cnl, *coff;
+  unsigned long long* lab; int *ltag, *tile; void* sort; size_t sort_bytes, total;
+};
+inline bool crease_layout(void* ws, int nv, int nf, int scan_tile, CreaseWs* w) {
+  if (nv < 0 || nf < 0 || nv > CR_MAX_VERTS || nf > RC_MAX_FACES) return false;
+  w->M = 3 * nf;
+  const size_t M = (size_t)w->M, V = (size_t)nv;
+  w->N = V > 2 * M ? V : 2 * M;
+  w->sort_bytes = (size_t)32 * w->N + ((size_t)4 << 20);
+  WsCarver c(ws);
+  w->state = c.take<int>(64);
+  w->ka = c.take<unsigned long long>(w->N);
+  w->kb = c.take<unsigned long long>(w->N);
+  w->va = c.take<int>(w->N);
+  w->vb = c.take<int>(w->N);
+  for (int** p : {&w->weld, &w->vhead, &w->vslot, &w->rep, &w->vstate, &w->jflag, &w->jmap}) *p = c.take<int>(V);
+  w->fn = c.take<double>(4 * (size_t)nf);
+  for (int** p : {&w->mark, &w->slot, &w->elo, &w->ehi, &w->ekind, &w->parent}) *p = c.take<int>(M);
+  w->ckey = c.take<unsigned long long>(M);
+  w->cstart = c.take<int>(M + 1);
+  w->cinfo = c.take<int>(4 * M);
+  w->cnl = c.take<int>(M);
+  w->coff = c.take<int>(M);
+  w->lab = c.take<unsigned long long>(M);
+  w->ltag = c.take<int>(M);
+  w->tile = c.take<int>(w->N / (size_t)scan_tile + 1);
+  w->sort = c.take<char>(w->sort_bytes);
+  w->total = c.end();
+  return true;
+}
+
 }  // namespace neat

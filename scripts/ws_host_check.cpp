@@ -323,6 +323,38 @@ int main() {
     CHECK((long long)SG_MAX_VIEWS * (2048 / 16) * (2048 / 16) <= 0x7fffffffLL);      // the grid of that launch
   }
 
+  // ---- crease lines: vertices and faces; M = 3 nf half-edges, N = max(nv, 2 M) elements in a sort, tiles of 1024 in a scan
+  {
+    const int shapes[][2] = {{0, 0}, {1, 1}, {3, 0}, {0, 4}, {255, 256}, {256, 257}, {4097, 4096}, {100000, 7}, {12291, 16388}};
+    for (const auto& sh : shapes) {
+      CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+        CreaseWs w;
+        if (!crease_layout(b, sh[0], sh[1], 1024, &w)) return false;
+        const size_t V = (size_t)sh[0], M = 3 * (size_t)sh[1], N = V > 2 * M ? V : 2 * M;
+        if (w.N != N || (size_t)w.M != M || w.sort_bytes < 32 * N) return false;
+        r = {{w.state, 256, 256}, {w.ka, N * 8, 256}, {w.kb, N * 8, 256}, {w.va, N * 4, 256}, {w.vb, N * 4, 256}};
+        for (int* p : {w.weld, w.vhead, w.vslot, w.rep, w.vstate, w.jflag, w.jmap}) r.push_back({p, V * 4, 256});
+        r.push_back({w.fn, (size_t)sh[1] * 32, 256});
+        for (int* p : {w.mark, w.slot, w.elo, w.ehi, w.ekind, w.parent}) r.push_back({p, M * 4, 256});
+        r.push_back({w.ckey, M * 8, 256});
+        r.push_back({w.cstart, (M + 1) * 4, 256});
+        r.push_back({w.cinfo, M * 16, 256});
+        r.push_back({w.cnl, M * 4, 256});
+        r.push_back({w.coff, M * 4, 256});
+        r.push_back({w.lab, M * 8, 256});
+        r.push_back({w.ltag, M * 4, 256});
+        r.push_back({w.tile, ((N + 1023) / 1024) * 4, 256});
+        r.push_back({w.sort, w.sort_bytes, 256});
+        t = w.total;
+        return true;
+      }));
+    }
+    CreaseWs wc;
+    CHECK(!crease_layout(nullptr, -1, 1, 1024, &wc) && !crease_layout(nullptr, 1, -1, 1024, &wc) && !crease_layout(nullptr, CR_MAX_VERTS + 1, 1, 1024, &wc) &&
+          !crease_layout(nullptr, 1, RC_MAX_FACES + 1, 1024, &wc));
+    CHECK(crease_layout(nullptr, CR_MAX_VERTS, RC_MAX_FACES, 1024, &wc) && 2 * (long long)wc.M <= 0x7fffffffLL);      // every index is an int
+  }
+
   // the large values: measured only
   CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
     TriWs w;
