@@ -16,7 +16,6 @@ numpy, which the device equals array for array.  There is no host fallback.
 """
 import argparse
 import collections
-import json
 import math
 import os
 import sys
@@ -24,7 +23,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, ply, raycast
+from . import _lib, ply, run_io
 
 KINDS = ("crease", "boundary", "non_manifold")      # the meaning of `kind` 0, 1, 2
 DEFAULTS = {"angle": 30.0, "turn": 1.0, "deviation": 1e-6}
@@ -104,13 +103,6 @@ def lines(verts, faces, angle=DEFAULTS["angle"], turn=DEFAULTS["turn"], deviatio
 
 
 # ------------------------------------------------------------------ files
-def _replace(path, write):
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = path + ".tmp"
-    write(tmp)
-    os.replace(tmp, path)
-
-
 def _host(x):
     return np.asarray(torch.as_tensor(x).detach().cpu().numpy())
 
@@ -119,14 +111,9 @@ def write_lines(path, res):
     """lines.json: `junctions` [J,3] and `lines` [L,2] as scenegen.read_lines, raycast.scan_wireframe and evaluate abc read them, and
     `kind`, `curved` [L] beside them.  Floats are written with repr, so they read back to the same float64.  Written to a .tmp beside
     the file and moved into place."""
-    doc = {"junctions": [[float(x) for x in p] for p in _host(res.junctions).reshape(-1, 3)],
-           "lines": [[int(a), int(b)] for a, b in _host(res.lines).reshape(-1, 2)],
-           "kind": [int(k) for k in _host(res.kind).reshape(-1)], "curved": [bool(c) for c in _host(res.curved).reshape(-1)]}
-
-    def write(tmp):
-        with open(tmp, "w") as fh:
-            json.dump(doc, fh)                       # json writes a float with float.__repr__
-    _replace(path, write)
+    run_io.write_json(path, {"junctions": [[float(x) for x in p] for p in _host(res.junctions).reshape(-1, 3)],
+                             "lines": [[int(a), int(b)] for a, b in _host(res.lines).reshape(-1, 2)],
+                             "kind": [int(k) for k in _host(res.kind).reshape(-1)], "curved": [bool(c) for c in _host(res.curved).reshape(-1)]})
 
 
 def write_tubes(path, res, radius):
@@ -143,7 +130,7 @@ def write_tubes(path, res, radius):
     verts = np.stack([a + radius * r for r in ring] + [b + radius * r for r in ring], axis=1).reshape(-1, 3)      # six per line
     local = [(0, 2, 1), (3, 4, 5)] + [t for k in range(3) for t in ((k, (k + 1) % 3, 3 + (k + 1) % 3), (k, 3 + (k + 1) % 3, 3 + k))]
     faces = (6 * np.arange(len(pairs))[:, None, None] + np.asarray(local)[None]).reshape(-1, 3)
-    _replace(path, lambda tmp: ply.write_ply(tmp, verts, faces))
+    ply.write_ply(path, verts, faces)
 
 
 # ------------------------------------------------------------------ command line
@@ -180,11 +167,10 @@ def parse_args(argv=None):
 
 def main(argv=None):
     opt = parse_args(argv)
-    if os.path.exists(opt.out) and not opt.overwrite:
-        print("exists: {} (--overwrite to replace it)".format(opt.out), flush=True)
+    if run_io.skip_existing(opt.out, opt.overwrite):
         return 0
     _lib.lib()
-    verts, faces = raycast.read_mesh(opt.mesh)
+    verts, faces = ply.read_mesh(opt.mesh)
     torch.cuda.set_device(opt.gpu)
     res = lines(verts, faces, angle=opt.angle, turn=opt.turn, deviation=opt.deviation, boundary=not opt.no_boundary, drop_curved=opt.drop_curved,
                 min_len=opt.min_len, device=torch.device("cuda", opt.gpu))

@@ -146,15 +146,7 @@ def build_parser():
     return ap
 
 
-def parse_views(text, n):
-    """'a:b' (either side may be empty) -> the range of views."""
-    if text is None:
-        return range(n)
-    parts = text.split(":")
-    if len(parts) != 2:
-        raise ValueError(f"--views {text}: expected a:b")
-    a, b = (int(p) if p.strip() else None for p in parts)
-    return range(n)[slice(a, b)]
+parse_views = run_io.parse_views              # 'a:b'; its home is neat_amd.run_io
 
 
 def load_image(path):

@@ -510,13 +510,11 @@ def run_dtu_junctions(opt, dev):
 
 def run_abc(opt, dev):
     data = torch.load(opt.data, map_location="cpu")
-    with open(os.path.join(opt.scan, "lines.json")) as f:
-        gt = json.load(f)
-    with open(os.path.join(opt.scan, "offset_scale.txt")) as f:
-        offset_scale = f.read().split()
+    junctions, edges = run_io.read_lines_json(os.path.join(opt.scan, "lines.json"))
+    offset_scale = run_io.read_offset_scale(os.path.join(opt.scan, "offset_scale.txt"))
     t0 = time.perf_counter()
     with torch.cuda.device(dev):
-        res = abc_scores(data["junctions3d_initial"], data["lines3d_wfi_checked"], gt["junctions"], gt["lines"], offset_scale)
+        res = abc_scores(data["junctions3d_initial"], data["lines3d_wfi_checked"], junctions, edges, offset_scale)
     torch.cuda.synchronize(dev)
     _emit(opt, res, {"abc_s": time.perf_counter() - t0}, abc_lines(res))
     return 0

@@ -29,7 +29,7 @@ import torch
 
 from . import ply
 from ._lib import PRECISIONS
-from .run_io import implicit_network_of, load_model
+from .run_io import implicit_network_of, load_model, skip_existing
 
 DEFAULT_RESOLUTION = 100
 DEFAULT_BOUNDARY = (-1.5, 1.5)
@@ -413,8 +413,7 @@ def eval_bbox(opt):
 
 def main_eval(opt, model, epoch, root, plot):
     path = eval_out_path(root, epoch, opt.scan_id)
-    if os.path.exists(path) and not opt.overwrite:
-        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+    if skip_existing(path, opt.overwrite):
         return 0
     scale_mat = None
     if opt.cams is not None and not opt.no_world:
@@ -429,7 +428,6 @@ def main_eval(opt, model, epoch, root, plot):
     if res is None:
         print("a grid does not cross level {} (or the box cuts everything away): no surface, nothing written".format(opt.level), flush=True)
         return 0
-    os.makedirs(os.path.dirname(path), exist_ok=True)
     ply.write_ply(path, res["verts"], res["faces"], res["normals"])
     print("{}: {} vertices, {} faces, aligned grid {} x {} x {}".format(path, res["verts"].shape[0], res["faces"].shape[0], *res["frame"]["shape"]),
           flush=True)
@@ -445,8 +443,7 @@ def main(argv=None):
     if opt.eval:
         return main_eval(opt, model, epoch, root, plot)
     path = out_path(root, epoch)
-    if os.path.exists(path) and not opt.overwrite:
-        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+    if skip_existing(path, opt.overwrite):
         return 0
     timings = {}
     res = surface(model, opt.resolution, tuple(opt.grid_boundary) if opt.grid_boundary else None, level=opt.level,
@@ -456,7 +453,6 @@ def main(argv=None):
     if res is None:
         print("the grid does not cross level {}: no surface, nothing written".format(opt.level), flush=True)
         return 0
-    os.makedirs(os.path.dirname(path), exist_ok=True)
     ply.write_ply(path, res["verts"], res["faces"], res["normals"])
     print("{}: {} vertices, {} faces".format(path, res["verts"].shape[0], res["faces"].shape[0]), flush=True)
     return 0

@@ -376,6 +376,12 @@ def render_rays(handle, origins, dirs, z, beta, radius, scale, want_normal_map=F
     return RenderRaysFn.apply(handle, origins, dirs, z, beta, beta_min, radius, scale, want_normal_map, eik_points, bg_color, *handle.tensors())
 
 
+def pixel_grid(H, W, device=None):
+    """uv [H*W, 2] float32 in the datasets' order: x fastest, integer pixel coordinates."""
+    ys, xs = torch.meshgrid(torch.arange(H, device=device), torch.arange(W, device=device), indexing="ij")
+    return torch.stack([xs, ys], -1).reshape(-1, 2).float()
+
+
 def camera_rays(uv, pose, intrinsics, with_origins=False):
     """rend_util.get_camera_params for pose matrices: uv [1,R,2], pose [1,4,4], K [1,3|4,3|4] -> dirs [1,R,3], cam [1,3]
     (with_origins: also the camera centre repeated per ray, [R,3], written by the same launch)."""

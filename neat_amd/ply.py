@@ -1,9 +1,9 @@
-"""PLY and OBJ files: the one reader of the tools, the mesh writer (neat_amd.mesh, the trainer's --vis_mesh) and the cloud writer (neat_amd.evaluate).
-tests/mesh_f64.read_ply is the tests' own, independent reader."""
-import os
-
+"""PLY and OBJ files: the one reader of the tools, the mesh writers (neat_amd.mesh, the trainer's --vis_mesh, neat_amd.scenegen) and the
+cloud writer (neat_amd.evaluate).  tests/mesh_f64.read_ply is the tests' own, independent reader."""
 import numpy as np
 import torch
+
+from .run_io import replace_file
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
@@ -105,6 +105,26 @@ def read_obj(path):
     return np.asarray(verts, dtype=np.float64).reshape(-1, 3), np.asarray(faces, dtype=np.int32).reshape(-1, 3)
 
 
+def read_mesh(path):
+    """A .ply or .obj mesh -> (verts float64 [nv,3], faces int32 [nf,3])."""
+    if path.lower().endswith(".obj"):
+        return read_obj(path)
+    m = read_ply(path)
+    if m["faces"] is None:
+        raise ValueError("%s: no faces" % path)
+    return m["points"], m["faces"]
+
+
+def write_obj(path, verts, faces):
+    """A Wavefront OBJ that read_obj reads back to the same float64 values."""
+    def write(tmp):
+        with open(tmp, "w") as fh:
+            fh.write("# neat_amd.scenegen\n")
+            fh.writelines("v %r %r %r\n" % tuple(float(x) for x in v) for v in np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+            fh.writelines("f %d %d %d\n" % tuple(int(i) + 1 for i in f) for f in np.asarray(faces).reshape(-1, 3))
+    replace_file(path, write)
+
+
 def write_ply(path, verts, faces, normals=None):
     """Binary little-endian PLY: float32 x y z [nx ny nz] per vertex, `uchar 3 + 3 x int32` per face."""
     v = np.ascontiguousarray(torch.as_tensor(verts).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
@@ -122,12 +142,13 @@ def write_ply(path, verts, faces, normals=None):
     rec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
     rec["n"] = 3
     rec["i"] = f
-    tmp = path + ".tmp"
-    with open(tmp, "wb") as fh:
-        fh.write(("\n".join(header) + "\n").encode("ascii"))
-        fh.write(np.concatenate(cols, axis=1).astype("<f4").tobytes())
-        fh.write(rec.tobytes())
-    os.replace(tmp, path)
+
+    def write(tmp):
+        with open(tmp, "wb") as fh:
+            fh.write(("\n".join(header) + "\n").encode("ascii"))
+            fh.write(np.concatenate(cols, axis=1).astype("<f4").tobytes())
+            fh.write(rec.tobytes())
+    replace_file(path, write)
 
 
 def write_ply_cloud(path, points, colors=None):

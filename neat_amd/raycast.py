@@ -43,7 +43,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, ply, run_io
+from . import _lib, ply, run_io, visibility
 
 
 class Scene:
@@ -107,9 +107,7 @@ def view(scene, pose, intrinsics, H, W):
     K = torch.as_tensor(intrinsics).detach().to(dev, torch.float32)
     K = K.reshape(1, *K.shape[-2:]).contiguous()
     with torch.cuda.device(dev):
-        ys, xs = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
-        uv = torch.stack([xs, ys], -1).reshape(1, -1, 2).float()             # x fastest, integer pixel coordinates: the datasets' order
-        dirs, _, origins = ops.camera_rays(uv, pose, K, with_origins=True)
+        dirs, _, origins = ops.camera_rays(ops.pixel_grid(H, W, dev)[None], pose, K, with_origins=True)
         dirs = dirs.reshape(-1, 3)
         t, tri, _ = cast(scene, origins, dirs)
         hit = tri >= 0
@@ -125,28 +123,13 @@ def view(scene, pose, intrinsics, H, W):
     return depth.view(H, W), normal.view(H, W, 3), tri.view(H, W)
 
 
-def camera_centres(cams):
-    """4 x 4 world-to-camera matrices [F,4,4] (any array) -> the camera centres -R^T t, float64 [F,3] on the host."""
-    cams = np.asarray(torch.as_tensor(cams).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 4, 4)
-    return -np.einsum("fji,fj->fi", cams[:, :3, :3], cams[:, :3, 3])
-
-
 def _visible(scene, rows, cams, samples, bias):
-    from . import ops
-    dev = scene.device
-    centres64 = camera_centres(cams)
-    rows = torch.as_tensor(rows).detach().to(dev, torch.float32).reshape(-1, 3 if samples == 1 else 6).contiguous()
-    F, N = centres64.shape[0], int(rows.shape[0])
-    if F * N == 0:
-        return torch.zeros(F, N, samples, device=dev, dtype=torch.bool)
     # neat_trace_target_rays refuses targets outside a sphere: one that holds every centre and target (float64, on the host)
-    far = max(float(np.linalg.norm(centres64, axis=1).max()), float(rows.double().reshape(-1, 3).norm(dim=1).max().item()))
-    radius = 2.0 * far + 1.0
-    centres = torch.from_numpy(centres64.astype(np.float32)).to(dev)
-    with torch.cuda.device(dev):
-        o, d, t_end, ok = ops.trace_target_rays(centres, rows, samples, radius, 0.0, bias)
-        t, _, _ = cast(scene, o, d, t_max=t_end, any_hit=True)
-    return (torch.isinf(t) & (ok != 0)).view(F, N, samples)
+    def radius(centres, rows):
+        far = max(float(np.linalg.norm(centres, axis=1).max()), float(rows.double().reshape(-1, 3).norm(dim=1).max().item()))
+        return 2.0 * far + 1.0
+    return visibility.visible(scene.device, rows, cams, samples, bias, radius, 0.0,
+                              lambda o, d, t_end: torch.isinf(cast(scene, o, d, t_max=t_end, any_hit=True)[0]))
 
 
 @torch.no_grad()
@@ -212,23 +195,7 @@ def out_path(data):
     return os.path.splitext(data)[0] + "_occlmesh.npz"
 
 
-def read_mesh(path):
-    """A .ply or .obj mesh -> (verts float64 [nv,3], faces int32 [nf,3])."""
-    if path.lower().endswith(".obj"):
-        return ply.read_obj(path)
-    m = ply.read_ply(path)
-    if m["faces"] is None:
-        raise ValueError("%s: no faces" % path)
-    return m["points"], m["faces"]
-
-
-def read_cams(path):
-    """World-to-camera matrices float64 [F,4,4] of a cameras.npz (`extrinsics`: camera-to-world poses, as the datasets') or of the
-    cam.json neat_amd.show writes (world-to-camera)."""
-    if path.lower().endswith(".json"):
-        return run_io.load_cam_json(path)
-    with np.load(path) as z:
-        return np.linalg.inv(np.asarray(z["extrinsics"], dtype=np.float64).reshape(-1, 4, 4))
+read_mesh = ply.read_mesh              # its home is neat_amd.ply
 
 
 def build_parser():
@@ -236,16 +203,10 @@ def build_parser():
     sub = ap.add_subparsers(dest="command", required=True)
     ck = sub.add_parser("check", help="keep the lines of a wireframe that enough cameras see past a triangle mesh")
     ck.add_argument("--mesh", type=str, required=True, help="the occluder: a .ply or .obj triangle mesh")
-    ck.add_argument("--data", type=str, required=True, help="the wireframe: an .npz with `lines3d`, or a -neat.pth (its lines3d_wfi)")
+    visibility.add_check_flags(ck, "--data")
     ck.add_argument("--conf", type=str, default=None, help="a run's conf: the cameras of its dataset")
     ck.add_argument("--cams", type=str, default=None, help="a cameras.npz (extrinsics: camera-to-world) or a cam.json (world-to-camera)")
-    ck.add_argument("--min-views", default=5, type=int, help="views that must see a line")
-    ck.add_argument("--min-frac", default=0.5, type=float, help="fraction of a line's samples a view must see")
-    ck.add_argument("--bias", default=0.01, type=float, help="a ray stops this far in front of its target")
-    ck.add_argument("--samples", default=16, type=int, help="points per line")
-    ck.add_argument("--data_root", default="../data", help="root of the dataset's data_dir")
-    ck.add_argument("--gpu", default=0, type=int, help="device index")
-    ck.add_argument("--json", default=False, action="store_true", help="print one JSON object with the counts and the seconds")
+    visibility.add_check_flags(ck, "--min-views", "--min-frac", "--bias", "--samples", "--data_root", "--gpu", "--json")
     ck.add_argument("--overwrite", default=False, action="store_true", help="rewrite an _occlmesh.npz that is already on disk")
     an = sub.add_parser("analysis", help="what the cameras see of a scan's ground-truth wireframe, and what the detections recover of it")
     an.add_argument("--conf", type=str, required=True)
@@ -271,8 +232,7 @@ def parse_args(argv=None):
     ap = build_parser()
     opt = ap.parse_args(argv)
     if opt.command == "check":
-        if opt.samples < 2 or opt.min_views < 0 or not 0.0 <= opt.min_frac <= 1.0 or not opt.bias >= 0.0:
-            ap.error("--samples >= 2, --min-views >= 0, 0 <= --min-frac <= 1, --bias >= 0")
+        visibility.validate_check(ap, opt)
         if (opt.conf is None) == (opt.cams is None):
             ap.error("one of --conf and --cams")
         if os.path.splitext(opt.mesh)[1].lower() not in (".ply", ".obj"):
@@ -289,39 +249,25 @@ def parse_args(argv=None):
     return opt
 
 
-def dataset_cams(conf_path, data_root):
-    """The world-to-camera matrices float64 [F,4,4] of a conf's dataset."""
-    dataset = run_io.build_dataset(run_io.parse_conf(conf_path), data_root)
-    poses = np.stack([np.asarray(torch.as_tensor(dataset.pose_all[i]).numpy(), dtype=np.float64) for i in range(len(dataset))])
-    return np.linalg.inv(poses)                      # the datasets hold camera-to-world
-
-
 def main_check(opt):
     _lib.lib()
     path = out_path(opt.data)
-    if os.path.exists(path) and not opt.overwrite:
-        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+    if run_io.skip_existing(path, opt.overwrite):
         return 0
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
-    cams = dataset_cams(opt.conf, opt.data_root) if opt.conf is not None else read_cams(opt.cams)
+    if opt.conf is not None:
+        cams = run_io.dataset_cams(run_io.build_dataset(run_io.parse_conf(opt.conf), opt.data_root))
+    else:
+        cams = run_io.read_cams(opt.cams)
     verts, faces = read_mesh(opt.mesh)
-    lines3d = run_io.load_lines(opt.data, pth_key="lines3d_wfi")[0]
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    scene = build(verts, faces, device)
-    if scene.status != 0:
-        raise ValueError("%s: a face index lies outside the vertices" % opt.mesh)
-    frac = visible_lines(scene, torch.from_numpy(lines3d), cams, samples=opt.samples, bias=opt.bias).cpu().numpy()
-    cast_s = time.perf_counter() - t0
-    views, kept = run_io.keep_rule(frac, opt.min_views, opt.min_frac)
-    run_io.write_occl(path, lines3d, views, kept)
-    print("{}: kept {} / {} lines ({} views, {} samples per line, {} triangles), casting {:.3f} s".format(
-        path, int(kept.sum()), len(kept), len(cams), opt.samples, scene.nf, cast_s), flush=True)
-    if opt.json:
-        print(json.dumps({"path": path, "kept": int(kept.sum()), "total": int(len(kept)), "views": int(len(cams)), "triangles": scene.nf,
-                          "cast_s": cast_s}), flush=True)
-    return 0
+
+    def fraction(lines3d):
+        scene = build(verts, faces, device)
+        if scene.status != 0:
+            raise ValueError("%s: a face index lies outside the vertices" % opt.mesh)
+        return visible_lines(scene, lines3d, cams, samples=opt.samples, bias=opt.bias).cpu().numpy(), {"triangles": scene.nf}
+    return visibility.run_check(opt, path, device, cams, fraction, "casting", "cast_s")
 
 
 # ---- analysis (evaluation/abc-analysis.py)
@@ -358,16 +304,13 @@ def cast_check(scene, points2d, points3d, intrinsics, pose, tol):
 
 def scan_wireframe(scan):
     """<scan>/lines.json, offset_scale.txt -> (inv(scale_mat) float64 [4,4], junctions float32 [J,3] in the training frame, edges [L,2])."""
-    with open(os.path.join(scan, "lines.json")) as fh:
-        gt = json.load(fh)
-    with open(os.path.join(scan, "offset_scale.txt")) as fh:
-        off = np.array([float(x) for x in fh.read().split()])
+    junctions, edges = run_io.read_lines_json(os.path.join(scan, "lines.json"))
+    off = run_io.read_offset_scale(os.path.join(scan, "offset_scale.txt"))
     s = 1.0 / float(off[-1])
     scale_mat = np.array([[s, 0, 0, -float(off[0])], [0, s, 0, -float(off[1])], [0, 0, s, -float(off[2])], [0, 0, 0, 1.0]])
     inv_scale = np.linalg.inv(scale_mat)
-    junctions = np.asarray(gt["junctions"], dtype=np.float64).reshape(-1, 3)
     junctions = (inv_scale[:3, :3] @ junctions.T + inv_scale[:3, 3:]).T
-    return inv_scale, junctions.astype(np.float32), np.asarray(gt["lines"], dtype=np.int64).reshape(-1, 2)
+    return inv_scale, junctions.astype(np.float32), edges
 
 
 def _assign(cost, device):
@@ -442,9 +385,7 @@ def main_analysis(opt):
     for x in six:
         print(x, flush=True)
     path = os.path.join(opt.scan, "wireframe_visibility.npz")
-    tmp = path + ".tmp.npz"
-    np.savez(tmp, **res)
-    os.replace(tmp, path)
+    run_io.replace_file(path, lambda tmp: np.savez(tmp, **res))
     if opt.json:
         print(json.dumps({"junctions": six[0], "lines": six[1], "junctions_hit": six[2], "junction_rate": six[3], "line_rate": six[4],
                           "lines_kept": six[5], "lines_hit": int((res["lines_hit"] > 0).sum()), "views": len(dataset), "path": path}), flush=True)
@@ -460,23 +401,15 @@ def dist_path(data):
 def to_mesh_frame(x, scale_file):
     """x [..., 3] in the model frame -> the frame of the scan's mesh, x / scale - offset with the four numbers of offset_scale.txt (as
     evaluate.abc_scores maps the predictions)."""
-    with open(scale_file) as fh:
-        off = np.array([float(v) for v in fh.read().split()], dtype=np.float64)
+    off = run_io.read_offset_scale(scale_file)
     return np.asarray(x, dtype=np.float64) * (1.0 / off[3]) - off[:3]
-
-
-def _savez(path, **arrays):
-    tmp = path + ".tmp.npz"
-    np.savez(tmp, **arrays)
-    os.replace(tmp, path)
 
 
 def main_distance(opt):
     _lib.lib()
     source = opt.data if opt.data is not None else opt.points
     path = dist_path(source)
-    if os.path.exists(path) and not opt.overwrite:
-        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+    if run_io.skip_existing(path, opt.overwrite):
         return 0
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
@@ -500,7 +433,7 @@ def main_distance(opt):
         n = dist.shape[0]
         mean, worst = dist.mean(axis=1), dist.max(axis=1)
         on = worst <= opt.threshold
-        _savez(path, dist=dist, mean=mean, max=worst, tri=tri, on_surface=on)
+        run_io.replace_file(path, lambda tmp: np.savez(tmp, dist=dist, mean=mean, max=worst, tri=tri, on_surface=on))
         report = {"path": path, "lines": n, "on_surface": int(on.sum()), "mean": float(mean.mean()) if n else float("nan"),
                   "median": float(np.median(mean)) if n else float("nan"), "samples": opt.samples, "threshold": opt.threshold,
                   "triangles": scene.nf, "query_s": query_s}
@@ -511,7 +444,7 @@ def main_distance(opt):
         dist, tri, point = dist.cpu().numpy(), tri.cpu().numpy(), point.cpu().numpy()
         query_s = time.perf_counter() - t0
         n = dist.shape[0]
-        _savez(path, dist=dist, tri=tri, point=point)
+        run_io.replace_file(path, lambda tmp: np.savez(tmp, dist=dist, tri=tri, point=point))
         report = {"path": path, "points": n, "acc": float(dist.mean()) if n else float("nan"), "median": float(np.median(dist)) if n else float("nan"),
                   "prec": float((dist < opt.threshold).mean()) if n else float("nan"), "threshold": opt.threshold, "triangles": scene.nf,
                   "query_s": query_s}

@@ -33,7 +33,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, run_io
+from . import _lib, ops, run_io
 from ._lib import ptr as _p, stream as _stream
 
 MAPS = ("rgb", "normal", "depth")
@@ -50,10 +50,7 @@ def _f32(t, what):
     return t.detach().to(torch.float32).contiguous()
 
 
-def pixel_grid(H, W, device=None):
-    """uv [H*W, 2] float32 in the datasets' order: x fastest, integer pixel coordinates."""
-    ys, xs = torch.meshgrid(torch.arange(H, device=device), torch.arange(W, device=device), indexing="ij")
-    return torch.stack([xs, ys], -1).reshape(-1, 2).float()
+pixel_grid, write_png = ops.pixel_grid, run_io.write_png              # their homes are neat_amd.ops and neat_amd.run_io
 
 
 def frame_put(rgb, normal, depth, gt, p0, P, rgb8=None, normal8=None, depth_out=None, err=None):
@@ -215,26 +212,14 @@ def dataset_view(dataset, idx, device):
 
 def camera_view(w2c, width, height, fov, device):
     """A world-to-camera matrix [4,4] with show.intrinsics(width, height, fov) -> (uv, pose = inverse(w2c), intrinsics [1,4,4]) on the device."""
-    from .show import intrinsics as show_intrinsics
     K = np.eye(4)
-    K[:3, :3] = show_intrinsics(width, height, fov)
+    K[:3, :3] = run_io.fov_intrinsics(width, height, fov)
     pose = np.linalg.inv(np.asarray(w2c, dtype=np.float64).reshape(4, 4))
     as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)[None]
     return pixel_grid(height, width, device)[None], as_dev(pose), as_dev(K)
 
 
 # ------------------------------------------------------------------ files
-def write_png(path, image, overwrite=True):
-    """uint8 [H,W,3] or [H,W] (tensor or array) -> a PNG; an existing file is kept unless `overwrite`.  -> True if written."""
-    if os.path.exists(path) and not overwrite:
-        return False
-    from PIL import Image
-    arr = image.cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    Image.fromarray(np.ascontiguousarray(arr)).save(path)
-    return True
-
-
 def psnr_rows(psnrs):
     """The per-view values, then their mean and their standard deviation (ddof 0), float64 (eval.py:129-131)."""
     p = np.asarray(psnrs, dtype=np.float64).reshape(-1)

@@ -4,8 +4,10 @@
     <run>/checkpoints/ModelParameters/<checkpoint>.pth       {"epoch", "model_state_dict"}, written by neat_amd.runner
     <run>/wireframes/{checkpoint}-{h}-{all,wfi,wfi_checked}.npz, -neat.pth      written by neat_amd.parse
 
-The trainer and every tool (parse, mesh, render, trace, raycast, post, show, evaluate) stand on this module and on neat_amd.ply; none of
-them reaches into another tool for its files.
+A scan directory's ground truth (lines.json, offset_scale.txt), the dataset's cameras, --views, and how every tool writes a file
+(replace_file, write_png, skip_existing) are here too.  The trainer and the twelve tools (parse, mesh, render, trace, raycast, post, show,
+evaluate, detect, triangulate, scenegen, creases) stand on this module and on neat_amd.ply; none of them reaches into another tool for
+its files, cameras or command line (neat_amd.visibility holds what trace check and raycast check share).
 """
 import json
 import os
@@ -120,15 +122,103 @@ def scene_images(instance_dir):
     raise FileNotFoundError(f"{instance_dir}: neither images/ nor image/")
 
 
+def replace_file(path, write):
+    """Every tool's way to write a file: the parent directory is made, write(tmp) fills a temporary file beside `path` (its name ends as
+    `path` does, so np.savez adds nothing to it), and the finished file is moved into place.  If `write` raises, `path` is as it was and
+    the temporary file is gone."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + ".tmp" + os.path.splitext(path)[1]
+    try:
+        write(tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def write_json(path, doc):
+    """`doc` as JSON through replace_file (json writes a float with float.__repr__, so it reads back to the same float64)."""
+    def write(tmp):
+        with open(tmp, "w") as fh:
+            json.dump(doc, fh)
+    replace_file(path, write)
+
+
+def skip_existing(path, overwrite):
+    """True, and the line that says so, when `path` is on disk and --overwrite was not given."""
+    skip = os.path.exists(path) and not overwrite
+    if skip:
+        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+    return skip
+
+
+def write_png(path, image, overwrite=True):
+    """uint8 [H,W,3] or [H,W] (tensor or array) -> a PNG; an existing file is kept unless `overwrite`.  -> True if written."""
+    if os.path.exists(path) and not overwrite:
+        return False
+    from PIL import Image
+    arr = image.cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    replace_file(path, lambda tmp: Image.fromarray(np.ascontiguousarray(arr)).save(tmp, format="PNG"))
+    return True
+
+
 def write_wireframe_json(path, wireframe, extra=None):
     """A WireframeGraph as the <scene>/<line_detector>/<image>.json the dataset classes read (`extra`: further keys, which load_json ignores)."""
     d = wireframe.jsonize()
     d.update(extra or {})
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = path + ".tmp"
-    with open(tmp, "w") as fh:
-        json.dump(d, fh)
-    os.replace(tmp, path)
+    write_json(path, d)
+
+
+def read_lines_json(path):
+    """A scan's lines.json -> (junctions float64 [J,3], edges int64 [E,2]: the junctions each straight edge joins)."""
+    with open(path) as fh:
+        gt = json.load(fh)
+    return np.asarray(gt["junctions"], dtype=np.float64).reshape(-1, 3), np.asarray(gt["lines"], dtype=np.int64).reshape(-1, 2)
+
+
+def read_offset_scale(path):
+    """A scan's offset_scale.txt -> its four numbers, float64: the offset, then the scale (model frame = (mesh frame + offset) * scale)."""
+    with open(path) as fh:
+        return np.array([float(v) for v in fh.read().split()], dtype=np.float64)
+
+
+def dataset_cams(dataset):
+    """The world-to-camera matrices float64 [F,4,4] of a dataset (the datasets hold camera-to-world)."""
+    return np.linalg.inv(np.stack([np.asarray(torch.as_tensor(dataset.pose_all[i]).numpy(), dtype=np.float64) for i in range(len(dataset))]))
+
+
+def read_cams(path):
+    """World-to-camera matrices float64 [F,4,4] of a cameras.npz (`extrinsics`: camera-to-world poses, as the datasets') or of the
+    cam.json neat_amd.show writes (world-to-camera)."""
+    if path.lower().endswith(".json"):
+        return load_cam_json(path)
+    with np.load(path) as z:
+        return np.linalg.inv(np.asarray(z["extrinsics"], dtype=np.float64).reshape(-1, 4, 4))
+
+
+def fov_intrinsics(width, height, fov=60.0):
+    """-> K [3,3]: vertical field of view `fov` degrees, square pixels, principal point ((W - 1) / 2, (H - 1) / 2)."""
+    f = 0.5 * height / np.tan(0.5 * fov / 180.0 * np.pi)
+    return np.array([[f, 0.0, 0.5 * (width - 1)], [0.0, f, 0.5 * (height - 1)], [0.0, 0.0, 1.0]])
+
+
+def camera_centres(cams):
+    """4 x 4 world-to-camera matrices [F,4,4] (any array) -> the camera centres -R^T t, float64 [F,3] on the host."""
+    cams = np.asarray(torch.as_tensor(cams).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 4, 4)
+    return -np.einsum("fji,fj->fi", cams[:, :3, :3], cams[:, :3, 3])
+
+
+def parse_views(text, n, step=False):
+    """--views: 'a:b', with `step` also 'a:b:step' (any part may be empty) -> the range of views."""
+    if text is None:
+        return range(n)
+    parts = text.split(":")
+    if len(parts) not in ((2, 3) if step else (2,)):
+        raise ValueError(f"--views {text}: expected a:b" + (" or a:b:step" if step else ""))
+    a, b, c = ([int(p) if p.strip() else None for p in parts] + [None])[:3]
+    if c is not None and c < 1:
+        raise ValueError(f"--views {text}: the step must be positive")
+    return range(n)[slice(a, b, c)]
 
 
 def load_cam_json(path):
@@ -150,6 +240,4 @@ def write_occl(path, lines3d, views, kept):
     seeing views per input line), kept bool [N]."""
     lines3d = np.asarray(lines3d).reshape(-1, 2, 3)
     kept = np.asarray(kept, dtype=bool)
-    tmp = path + ".tmp.npz"
-    np.savez(tmp, lines3d=lines3d[kept], views=np.asarray(views, dtype=np.int32), kept=kept)
-    os.replace(tmp, path)
+    replace_file(path, lambda tmp: np.savez(tmp, lines3d=lines3d[kept], views=np.asarray(views, dtype=np.int32), kept=kept))

@@ -22,7 +22,6 @@ tests/scenegen_f64.py restates it in float64 numpy, which the device equals byte
 import argparse
 import collections
 import ctypes
-import json
 import math
 import os
 import sys
@@ -30,7 +29,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, raycast, run_io
+from . import _lib, ply, raycast, run_io
 from .synth import look_at_pose
 from .wireframe import WireframeGraph
 
@@ -224,53 +223,27 @@ def scene_paths(out, views, name="gt"):
             "offset_scale": os.path.join(out, "offset_scale.txt")}
 
 
-def _replace(path, write):
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = path + ".tmp"
-    write(tmp)
-    os.replace(tmp, path)
-
-
-def write_obj(path, verts, faces):
-    """A Wavefront OBJ that ply.read_obj reads back to the same float64 values."""
-    def write(tmp):
-        with open(tmp, "w") as fh:
-            fh.write("# neat_amd.scenegen\n")
-            fh.writelines("v %r %r %r\n" % tuple(float(x) for x in v) for v in np.asarray(verts, dtype=np.float64).reshape(-1, 3))
-            fh.writelines("f %d %d %d\n" % tuple(int(i) + 1 for i in f) for f in np.asarray(faces).reshape(-1, 3))
-    _replace(path, write)
+write_obj = ply.write_obj              # its home is neat_amd.ply
 
 
 def write_static(paths, verts, faces, junctions, edges, K, poses):
     """cameras.npz, mesh.obj, lines.json and offset_scale.txt (`0 0 0 1`: everything is in the one normalised frame)."""
-    def npz(tmp):
-        with open(tmp, "wb") as fh:
-            np.savez(fh, intrinsics=np.asarray(K, dtype=np.float64), extrinsics=np.asarray(poses, dtype=np.float64))
-    _replace(paths["cameras"], npz)
+    run_io.replace_file(paths["cameras"], lambda tmp: np.savez(tmp, intrinsics=np.asarray(K, dtype=np.float64),
+                                                               extrinsics=np.asarray(poses, dtype=np.float64)))
     write_obj(paths["mesh"], verts, faces)
-
-    def lines(tmp):
-        with open(tmp, "w") as fh:
-            json.dump({"junctions": np.asarray(junctions, dtype=np.float64).reshape(-1, 3).tolist(),
-                       "lines": np.asarray(edges).reshape(-1, 2).astype(int).tolist()}, fh)
-    _replace(paths["lines"], lines)
+    run_io.write_json(paths["lines"], {"junctions": np.asarray(junctions, dtype=np.float64).reshape(-1, 3).tolist(),
+                                       "lines": np.asarray(edges).reshape(-1, 2).astype(int).tolist()})
 
     def offset(tmp):
         with open(tmp, "w") as fh:
             fh.write("0 0 0 1\n")
-    _replace(paths["offset_scale"], offset)
-
-
-def write_png(path, image):
-    from PIL import Image
-    _replace(path, lambda tmp: Image.fromarray(np.ascontiguousarray(image)).save(tmp, format="PNG"))
+    run_io.replace_file(paths["offset_scale"], offset)
 
 
 def read_lines(path):
     """lines.json -> (junctions float64 [J,3], edges int32 [E,2])."""
-    with open(path) as fh:
-        gt = json.load(fh)
-    return np.asarray(gt["junctions"], dtype=np.float64).reshape(-1, 3), np.asarray(gt["lines"], dtype=np.int32).reshape(-1, 2)
+    junctions, edges = run_io.read_lines_json(path)
+    return junctions, edges.astype(np.int32)
 
 
 # ------------------------------------------------------------------ command line
@@ -314,13 +287,12 @@ def main(argv=None):
     opt = parse_args(argv)
     _lib.lib()
     paths = scene_paths(opt.out, opt.views, opt.name)
-    if os.path.exists(paths["cameras"]) and not opt.overwrite:
-        print("exists: {} (--overwrite to replace it)".format(paths["cameras"]), flush=True)
+    if run_io.skip_existing(paths["cameras"], opt.overwrite):
         return 0
     if opt.shape is not None:
         verts, faces, junctions, edges = shapes[opt.shape]
     else:
-        verts, faces = raycast.read_mesh(opt.mesh)
+        verts, faces = ply.read_mesh(opt.mesh)
         junctions, edges = read_lines(opt.lines)
     if edges.size and (edges.min() < 0 or edges.max() >= junctions.shape[0]):
         raise ValueError("lines.json: a line names a junction outside the list")
@@ -338,8 +310,8 @@ def main(argv=None):
     rgb, mask = rgb.cpu().numpy(), mask.cpu().numpy()
     write_static(paths, verts, faces, junctions, edges, K, poses)
     for i in range(opt.views):
-        write_png(paths["images"][i], rgb[i])
-        write_png(paths["masks"][i], mask[i])
+        run_io.write_png(paths["images"][i], rgb[i])
+        run_io.write_png(paths["masks"][i], mask[i])
         run_io.write_wireframe_json(paths["wireframes"][i], graphs[i])
     print("{}: {} views of {} x {}, {} triangles, {} edges, {} visible runs".format(opt.out, opt.views, opt.res, opt.res, scene.nf,
                                                                                       int(edges.shape[0]), int(runs.idx.shape[0])), flush=True)

@@ -70,10 +70,7 @@ def orbit(rx=0.0, ry=0.0, rz=0.0, t=3.0, frames=72, step=5.0):
     return np.stack([CAMERA_AXES @ np.linalg.inv(camera_to_world(rx, (ry + k * step) % 360, rz, t)) for k in range(int(frames))])
 
 
-def intrinsics(width, height, fov=60.0):
-    """-> K [3,3]: vertical field of view `fov` degrees, square pixels, principal point ((W - 1) / 2, (H - 1) / 2)."""
-    f = 0.5 * height / np.tan(0.5 * fov / 180.0 * np.pi)
-    return np.array([[f, 0.0, 0.5 * (width - 1)], [0.0, f, 0.5 * (height - 1)], [0.0, 0.0, 1.0]])
+intrinsics = run_io.fov_intrinsics              # its home is neat_amd.run_io
 
 
 def pack_cameras(cameras, K):

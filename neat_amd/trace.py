@@ -23,15 +23,13 @@ evaluate dtu-lines read them), views int32 [N] (the seeing views per input line)
 stays the 2-D check of neat_amd.parse (--ckdist --ckview).  A -neat.pth contributes its `lines3d_wfi`.
 """
 import argparse
-import json
 import os
 import sys
 import time
 
-import numpy as np
 import torch
 
-from . import _lib, run_io
+from . import _lib, run_io, visibility
 
 MISS, HIT, INSIDE, UNCONVERGED = 0, 1, 2, 3
 DEFAULTS = dict(eps=1e-4, relax=1.0, max_steps=64, refine_steps=8, near=0.0)
@@ -107,7 +105,6 @@ def view(model, pose, intrinsics, H, W, *, radius=None, timings=None, **march):
     radius defaults to the model's bounding sphere; **march: eps, relax, max_steps, refine_steps, near, chunk.
     timings = a dict receives trace_s (device-synchronised wall time), evals and rays."""
     from . import ops
-    from .render import pixel_grid
     net = _sdf_network(model)
     if net is None:
         raise TypeError("trace.view: a model")
@@ -119,7 +116,7 @@ def view(model, pose, intrinsics, H, W, *, radius=None, timings=None, **march):
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
     with torch.cuda.device(dev):
-        dirs, _, origins = ops.camera_rays(pixel_grid(H, W, dev)[None], pose, K, with_origins=True)
+        dirs, _, origins = ops.camera_rays(ops.pixel_grid(H, W, dev)[None], pose, K, with_origins=True)
         depth, state, _, points, evals = rays(model, origins, dirs.reshape(-1, 3), radius=_radius_of(model, radius), **march)
         normal = torch.zeros(H * W, 3, device=dev)
         hit = torch.nonzero(state == HIT).flatten()
@@ -134,27 +131,15 @@ def view(model, pose, intrinsics, H, W, *, radius=None, timings=None, **march):
     return depth.view(H, W), normal.view(H, W, 3), state.view(H, W)
 
 
-def camera_centres(cams):
-    """4 x 4 world-to-camera matrices [F,4,4] (any array) -> the camera centres -R^T t, float64 [F,3] on the host."""
-    cams = np.asarray(torch.as_tensor(cams).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 4, 4)
-    return -np.einsum("fji,fj->fi", cams[:, :3, :3], cams[:, :3, 3])
+camera_centres, keep_rule, write_occl = run_io.camera_centres, run_io.keep_rule, run_io.write_occl      # their home is neat_amd.run_io
 
 
 def _visible(model, rows, cams, samples, bias, radius, march):
-    from . import ops
     net = _sdf_network(model)
     dev = next(net.parameters()).device if net is not None else rows.device
     radius = _radius_of(model, radius)
-    near = march.get("near", DEFAULTS["near"])
-    centres = torch.from_numpy(camera_centres(cams).astype(np.float32)).to(dev)
-    rows = torch.as_tensor(rows).detach().to(dev, torch.float32).reshape(-1, 3 if samples == 1 else 6).contiguous()
-    F, N = centres.shape[0], rows.shape[0]
-    if F * N == 0:
-        return torch.zeros(F, N, samples, device=dev, dtype=torch.bool)
-    with torch.cuda.device(dev):
-        o, d, t_end, ok = ops.trace_target_rays(centres, rows, samples, radius, near, bias)
-        _, state, _, _, _ = rays(model, o, d, radius=radius, t_end=t_end, **march)
-    return ((state == MISS) & (ok != 0)).view(F, N, samples)
+    return visibility.visible(dev, rows, cams, samples, bias, radius, march.get("near", DEFAULTS["near"]),
+                              lambda o, d, t_end: rays(model, o, d, radius=radius, t_end=t_end, **march)[1] == MISS)
 
 
 @torch.no_grad()
@@ -174,9 +159,6 @@ def visible_lines(model, lines3d, cams, *, samples=16, bias=0.01, radius=None, *
 
 
 # ------------------------------------------------------------------ command line
-keep_rule, write_occl = run_io.keep_rule, run_io.write_occl          # shared with neat_amd.raycast check
-
-
 def out_path(data):
     """`<data stem>_occl.npz` beside the input."""
     return os.path.splitext(data)[0] + "_occl.npz"
@@ -187,17 +169,12 @@ def build_parser():
     sub = ap.add_subparsers(dest="command", required=True)
     ck = sub.add_parser("check", help="keep the lines of a wireframe that enough cameras see past the learnt surface")
     ck.add_argument("--conf", type=str, required=True)
-    ck.add_argument("--data", type=str, required=True, help="the wireframe: an .npz with `lines3d`, or a -neat.pth (its lines3d_wfi)")
-    ck.add_argument("--min-views", default=5, type=int, help="views that must see a line")
-    ck.add_argument("--min-frac", default=0.5, type=float, help="fraction of a line's samples a view must see")
-    ck.add_argument("--bias", default=0.01, type=float, help="a ray stops this far in front of its target")
-    ck.add_argument("--samples", default=16, type=int, help="points per line")
+    visibility.add_check_flags(ck, "--data", "--min-views", "--min-frac", "--bias", "--samples")
     ck.add_argument("--checkpoint", default="latest", type=str)
     ck.add_argument("--expdir", default=None, help="run directory holding checkpoints/ (default: the conf's directory)")
-    ck.add_argument("--data_root", default="../data", help="root of the dataset's data_dir")
-    ck.add_argument("--gpu", default=0, type=int, help="device index")
+    visibility.add_check_flags(ck, "--data_root", "--gpu")
     ck.add_argument("--precision", choices=list(_lib.PRECISIONS), default=None)
-    ck.add_argument("--json", default=False, action="store_true", help="print one JSON object with the counts and the seconds")
+    visibility.add_check_flags(ck, "--json")
     ck.add_argument("--overwrite", default=False, action="store_true", help="rewrite an _occl.npz that is already on disk")
     return ap
 
@@ -205,36 +182,21 @@ def build_parser():
 def parse_args(argv=None):
     ap = build_parser()
     opt = ap.parse_args(argv)
-    if opt.samples < 2 or opt.min_views < 0 or not 0.0 <= opt.min_frac <= 1.0 or not opt.bias >= 0.0:
-        ap.error("--samples >= 2, --min-views >= 0, 0 <= --min-frac <= 1, --bias >= 0")
+    visibility.validate_check(ap, opt)
     return opt
 
 
 def main_check(opt):
     _lib.lib()
     path = out_path(opt.data)
-    if os.path.exists(path) and not opt.overwrite:
-        print("exists: {} (--overwrite to replace it)".format(path), flush=True)
+    if run_io.skip_existing(path, opt.overwrite):
         return 0
     torch.cuda.set_device(opt.gpu)
     device = torch.device("cuda", opt.gpu)
     model, epoch, _, conf = run_io.load_model(opt.conf, opt.checkpoint, device, opt.expdir, opt.precision)
-    dataset = run_io.build_dataset(conf, opt.data_root)
-    poses = np.stack([np.asarray(torch.as_tensor(dataset.pose_all[i]).numpy(), dtype=np.float64) for i in range(len(dataset))])
-    cams = np.linalg.inv(poses)                      # the datasets hold camera-to-world
-    lines3d = run_io.load_lines(opt.data, pth_key="lines3d_wfi")[0]          # of a -neat.pth: the lines before the 2-D visibility check
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    frac = visible_lines(model, torch.from_numpy(lines3d), cams, samples=opt.samples, bias=opt.bias).cpu().numpy()
-    trace_s = time.perf_counter() - t0
-    views, kept = keep_rule(frac, opt.min_views, opt.min_frac)
-    write_occl(path, lines3d, views, kept)
-    print("{}: kept {} / {} lines ({} views, {} samples per line), tracing {:.3f} s".format(path, int(kept.sum()), len(kept), len(cams),
-                                                                                         opt.samples, trace_s), flush=True)
-    if opt.json:
-        print(json.dumps({"epoch": int(epoch), "path": path, "kept": int(kept.sum()), "total": int(len(kept)), "views": int(len(cams)),
-                          "trace_s": trace_s}), flush=True)
-    return 0
+    cams = run_io.dataset_cams(run_io.build_dataset(conf, opt.data_root))
+    return visibility.run_check(opt, path, device, cams, lambda lines3d: (
+        visible_lines(model, lines3d, cams, samples=opt.samples, bias=opt.bias).cpu().numpy(), {}), "tracing", "trace_s", {"epoch": int(epoch)})
 
 
 def main(argv=None):

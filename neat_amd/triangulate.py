@@ -16,6 +16,7 @@ segments: one device tensor [n_v,4] = x1 y1 x2 y2 in pixels per view; Ks [V,3,3]
 csrc/kernels_triangulate.hpp implements it and tests/triangulate_f64.py restates it.  There is no CPU path: CPU tensors are refused.
 """
 import argparse
+import functools
 import math
 import os
 import sys
@@ -207,17 +208,7 @@ def build_parser():
     return ap
 
 
-def parse_views(text, n):
-    """'a:b' or 'a:b:step' (any part may be empty) -> the range of views."""
-    if text is None:
-        return range(n)
-    parts = text.split(":")
-    if len(parts) not in (2, 3):
-        raise ValueError(f"--views {text}: expected a:b or a:b:step")
-    a, b, step = ([int(p) if p.strip() else None for p in parts] + [None])[:3]
-    if step is not None and step < 1:
-        raise ValueError(f"--views {text}: the step must be positive")
-    return range(n)[slice(a, b, step)]
+parse_views = functools.partial(run_io.parse_views, step=True)              # 'a:b' or 'a:b:step'; its home is neat_amd.run_io
 
 
 def out_path(opt, instance_dir, line_detector):
@@ -227,11 +218,8 @@ def out_path(opt, instance_dir, line_detector):
 
 def write_lines(path, lines3d, views, support, cameras):
     """The tool's file, written through a temporary one."""
-    tmp = path + ".tmp.npz"
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    np.savez(tmp, lines3d=np.asarray(lines3d, np.float64).reshape(-1, 2, 3), views=np.asarray(views, np.int32),
-             support=np.asarray(support, np.float64), cameras=np.asarray(cameras, np.float64).reshape(-1, 4, 4))
-    os.replace(tmp, path)
+    run_io.replace_file(path, lambda tmp: np.savez(tmp, lines3d=np.asarray(lines3d, np.float64).reshape(-1, 2, 3), views=np.asarray(views, np.int32),
+                                                   support=np.asarray(support, np.float64), cameras=np.asarray(cameras, np.float64).reshape(-1, 4, 4)))
 
 
 def main(argv=None):

@@ -14,39 +14,15 @@ on 16 CPU processes.  One process, one warm-up, the median of `reps` repetitions
 from a run of its own: this script once more as a fresh process under `rocprofv3 --kernel-trace --stats` (--kernel-run).
 """
 import argparse
-import csv
-import glob
 import multiprocessing
 import os
 import statistics
-import subprocess
-import sys
-import tempfile
 import time
 from concurrent.futures import ProcessPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def kernel_table(opt, rows=8):
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "300", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run", "--level", str(opt.level), "--queries", str(opt.queries)]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: the build, then (a) and (b) once each through raycast.closest; %d kernels, %.3f s"
-           " of kernel time" % (len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (r["Name"].split("(")[0][-72:], int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    return out
+from timing import ROOT, kernel_table, sync_time
 
 
 def torch_brute_force(verts, faces, pts, chunk=128):
@@ -123,13 +99,6 @@ def main():
     sets = {"(a) within 0.05 of the surface": torch.from_numpy(near).to(dev), "(b) uniform in the box": torch.from_numpy(rng.uniform(-1.0, 1.0, (opt.queries, 3))).to(dev)}
     scene = raycast.build(torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev))
 
-    def sync_time(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
-
     if opt.kernel_run:
         for pts in sets.values():
             raycast.closest(scene, pts)
@@ -183,7 +152,8 @@ def main():
             % (int((tri_dev.cpu().numpy() == tri_cpu).sum()), n, int((tri_dev.long() == tri_t).sum()),
                int((d2_dev.cpu().numpy() == d2_cpu).sum()), int((d2_dev == d2_t).sum()))]
     print("\n".join(out[-5:]), flush=True)
-    out += kernel_table(opt)
+    out += kernel_table(__file__, ["--kernel-run", "--level", str(opt.level), "--queries", str(opt.queries)],
+                        "the build, then (a) and (b) once each through raycast.closest; %d kernels, %.3f s of kernel time", 8)
     with open(opt.out, "w") as fh:
         fh.write("\n".join(out) + "\n")
     print("wrote", opt.out)

@@ -11,37 +11,13 @@ wall time, the host's read-backs included).  The kernel table is from a run of i
 `rocprofv3 --kernel-trace --stats` (--kernel-run: creases.lines once per case).
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
-import sys
-import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def kernel_table(rows=14):
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "300", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run"]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: creases.lines once per case (the uploads included); %d kernels, %.4f s of kernel time"
-           % (len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (r["Name"].split("(")[0][-72:], int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    return out
+from timing import ROOT, kernel_table, sync_time
 
 
 def torch_rule(v, f, c, s2, length, boundary=True):
@@ -131,13 +107,6 @@ def main():
     cases = [("icosphere level %d" % opt.level,) + tuple(RC.icosphere(opt.level)), ("L block subdivided 5 times",) + tuple(scenegen.subdivide(lv, lf, 5)),
              ("L block subdivided 7 times",) + tuple(scenegen.subdivide(lv, lf, 7))]
 
-    def sync_time(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
-
     if opt.kernel_run:
         for _, verts, faces in cases:
             creases.lines(verts, faces, device=dev)
@@ -166,7 +135,7 @@ def main():
                 % (med(tc), faces.shape[0] / med(tc) * 1e-6, min(tc[1:]), max(tc[1:]), med(tt), med(tt) / med(tc), counts[0], counts[1], counts[2], cpu,
                    cpu / med(tc), same)]
         print("\n".join(out[-2:]), flush=True)
-    out += kernel_table()
+    out += kernel_table(__file__, ["--kernel-run"], "creases.lines once per case (the uploads included); %d kernels, %.4f s of kernel time", 14)
     with open(opt.out, "w") as fh:
         fh.write("\n".join(out) + "\n")
     print("wrote", opt.out)

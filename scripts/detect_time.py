@@ -11,19 +11,13 @@ with the segment counts of both.  The kernel table is from a run of its own: thi
 `rocprofv3 --kernel-trace --stats` (--kernel-run: eight pictures, both scales, twice).
 """
 import argparse
-import csv
-import glob
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT, kernel_table, timed
 FIXTURE = os.path.join(ROOT, "tests", "golden", "scene_abc_00075213_8views.npz")
 H, W = 1200, 1600
 
@@ -41,37 +35,6 @@ def pictures(views, seed=0):
         else:
             q = [big[(i + j) % len(big)] for j in range(4)]
             out[i] = np.concatenate([np.concatenate(q[:2], axis=1), np.concatenate(q[2:], axis=1)], axis=0)
-    return out
-
-
-def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        r = fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return statistics.median(ts), min(ts), max(ts), r
-
-
-def kernel_table(rows=14):
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "420", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run"]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: 8 pictures of 1200 x 1600 at scale 1 and at 0.8, twice; %d kernels, %.3f s of kernel"
-           " time" % (len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (r["Name"].split("(")[0][-72:], int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
     return out
 
 
@@ -118,7 +81,7 @@ def main():
         lines.append("tests/detect_f64.detect on the CPU, the same picture: %.2f s (%.0f x), %d segments, %d regions judged; equal to the device's: %s"
                      % (t1, t1 / med1, ref["lines"].shape[0], int(ref["cand_judge"].sum()), same))
     if not opt.no_trace:
-        lines += kernel_table()
+        lines += kernel_table(__file__, ["--kernel-run"], "8 pictures of 1200 x 1600 at scale 1 and at 0.8, twice; %d kernels, %.3f s of kernel time", 14, limit=420)
     text = "\n".join(lines) + "\n"
     print(text, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)

@@ -10,14 +10,12 @@ points of the same sphere; everything is observed.  One warm-up run, then the me
 import argparse
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT
 
 
 def sphere(radius, subdiv, seed=0):

@@ -9,13 +9,11 @@ itself when it is given a timings dict, so the stages are wall-clock seconds bet
 """
 import argparse
 import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT
 STAGES = ("coarse_s", "frame_s", "grid_s", "extract_s", "cut_s", "components_s")
 
 

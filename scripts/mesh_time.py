@@ -11,12 +11,10 @@ faces written) against the 6.29 TB/s float4 copy rate of the MI355X.  The extrac
 import argparse
 import json
 import os
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT
 COPY_RATE = 6.29e12      # bytes/s, float4 copy measured on MI355X
 
 

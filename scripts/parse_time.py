@@ -5,8 +5,6 @@
 1. toy scene (the runner test's 64 x 64 scene, 6 views, untrained abc-neat-a model): wireframe_recon, forward vs post-processing;
 2. a DTU-sized synthetic view set (49 views, 60 000 masked rays and 400 ground-truth lines per view, J = 1024): distil alone on
    recorded-like outputs (rows near the ground-truth lines, outliers), median of 5 runs after a warm-up."""
-import os
-import sys
 import tempfile
 import time
 from pathlib import Path
@@ -14,8 +12,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing  # noqa: F401 (puts the repository root on sys.path)
 
 
 def toy():

@@ -9,20 +9,14 @@ of each call included).  The CPU form runs once (it takes seconds).  The kernel 
 fresh process under `rocprofv3 --kernel-trace --stats` (--kernel-run: one warm-up and one call of each subcommand).
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
-import sys
-import tempfile
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT, kernel_table
 W, H, FOCAL = 640, 480, 600.0
 
 
@@ -50,25 +44,6 @@ def scene(n, V, m, seed=0):
         det[:, 4] = np.where(rng.random(m) < 0.3, rng.uniform(0.05, 0.4, m), rng.uniform(0.6, 0.99, m))
         views.append({"K": K, "pose": pose, "det": det[rng.permutation(m)]})
     return lines.astype(np.float32), views
-
-
-def kernel_table(opt, rows=16):
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "420", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run", "--lines", str(opt.lines), "--views", str(opt.views), "--dets", str(opt.dets),
-               "--grid", str(opt.grid)]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: one warm-up and one call of fuse, refine and snap; %d kernels, %.3f s of kernel time"
-           % (len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (r["Name"].split("(")[0][-72:], int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    return out
 
 
 def timed(fn, reps, sync):
@@ -120,7 +95,8 @@ def main():
         t_cpu, rc = timed(lambda: forms[name](torch.tensor(lines), tviews[torch.device("cpu")]), 0, lambda: None)
         out.append("%-8s %17.4f %26.4f %30.3f     %d / %d / %d" % (name, t_post, t_dev, t_cpu, r.shape[0], rd.shape[0], rc.shape[0]))
         print(out[-1], flush=True)
-    out += kernel_table(opt)
+    out += kernel_table(__file__, ["--kernel-run", "--lines", str(opt.lines), "--views", str(opt.views), "--dets", str(opt.dets), "--grid", str(opt.grid)],
+                        "one warm-up and one call of fuse, refine and snap; %d kernels, %.3f s of kernel time", 16, limit=420)
     with open(opt.out, "w") as fh:
         fh.write("\n".join(out) + "\n")
     print("wrote", opt.out)

@@ -12,40 +12,15 @@ its own: this script once more as a fresh process under `rocprofv3 --kernel-trac
 sixteenth of workload (b)).
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
-import sys
-import tempfile
 import time
 from concurrent.futures import ProcessPoolExecutor
 import multiprocessing
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def kernel_table(opt, rows=12):
-    import torch  # noqa: F401
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "420", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run", "--level", str(opt.level)]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: the build and the view twice, 3 125 lines x 16 samples x 64 views; %d kernels, %.3f s"
-           " of kernel time" % (len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (r["Name"].split("(")[0][-72:], int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    return out
+from timing import ROOT, kernel_table, sync_time
 
 
 def torch_brute_force(verts, faces, o, d, chunk=256):
@@ -121,13 +96,6 @@ def main():
     cams = np.stack([np.linalg.inv(synth.look_at_pose(tuple(x)).astype(np.float64)) for x in c])
     v_dev, f_dev = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
 
-    def sync_time(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
-
     if opt.kernel_run:
         for _ in range(2):
             scene = raycast.build(v_dev, f_dev)
@@ -185,7 +153,8 @@ def main():
             % (same_t, opt.sub_rays, int((tri_dev.long() == tri_t).sum()), opt.sub_rays and float(np.nanmax(np.abs(np.where(
                 tri_cpu >= 0, t_dev.cpu().numpy().astype(np.float64) - t_cpu64, 0.0)))))]
     print("\n".join(out[-5:]), flush=True)
-    out += kernel_table(opt)
+    out += kernel_table(__file__, ["--kernel-run", "--level", str(opt.level)],
+                        "the build and the view twice, 3 125 lines x 16 samples x 64 views; %d kernels, %.3f s of kernel time", 12, limit=420)
     with open(opt.out, "w") as fh:
         fh.write("\n".join(out) + "\n")
     print("wrote", opt.out)

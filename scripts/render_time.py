@@ -13,20 +13,15 @@ host route    what eval.py does: model(s) per chunk (the eval forward with its j
 The kernel table is from a run of its own: this script under `rocprofv3 --kernel-trace --stats` for one frame at the middle chunk size.
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
-import sys
 import tempfile
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT, kernel_table
 
 
 def setup(width, height, dev):
@@ -71,29 +66,6 @@ def host_frame(model, uv, pose, K, gt, wf, H, W, chunk):
     return time.perf_counter() - t0, img, psnr
 
 
-def kernel_table(opt, chunk, rows=14):
-    """This script once more under rocprofv3 --kernel-trace --stats (a process of its own, one frame) -> the top rows of its kernel table."""
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "420", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--traced", "--width", str(opt.width), "--height", str(opt.height), "--chunks", str(chunk)]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: one warm-up and one timed frame at chunk %d; %d kernels, %.3f s of kernel time"
-           % (chunk, len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        name = r["Name"].split("(")[0][-72:]
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (name, int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    frame = [r for r in table if "frame_" in r["Name"]]
-    out.append("# the frame kernels (frame_*): %d launches, %.3f ms in all" % (sum(int(r["Calls"]) for r in frame),
-                                                                              sum(float(r["TotalDurationNs"]) for r in frame) * 1e-6))
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1600)
@@ -130,7 +102,10 @@ def main():
                            % (chunk, -(-H * W // chunk), statistics.median(runs)))
                 print(out[-1], flush=True)
     if not opt.no_trace:
-        out += kernel_table(opt, chunks[len(chunks) // 2])
+        chunk = str(chunks[len(chunks) // 2])
+        out += kernel_table(__file__, ["--traced", "--width", str(opt.width), "--height", str(opt.height), "--chunks", chunk],
+                            "one warm-up and one timed frame at chunk " + chunk + "; %d kernels, %.3f s of kernel time", 14, limit=420,
+                            family=("frame", "frame_"))
         print("\n".join(out[-18:]), flush=True)
     with open(opt.out, "w") as fh:
         fh.write("\n".join(out) + "\n")

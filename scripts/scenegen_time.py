@@ -12,37 +12,12 @@ One process, one warm-up, the median of `reps` repetitions (device-synchronised 
 own: this script once more as a fresh process under `rocprofv3 --kernel-trace --stats` (--kernel-run: both workloads once).
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
-import sys
-import tempfile
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def kernel_table(opt, rows=10):
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "300", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run", "--level", str(opt.level), "--views", str(opt.views), "--res", str(opt.res)]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: the build, the pictures and the edges once; %d kernels, %.3f s of kernel time"
-           % (len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (r["Name"].split("(")[0][-72:], int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    return out
+from timing import ROOT, kernel_table, sync_time
 
 
 def parent_pictures(scene, K, poses, H, W, ss, albedo=0.7, ambient=0.25, background=1.0):
@@ -101,13 +76,6 @@ def main():
     w2c = np.linalg.inv(poses)
     segs = torch.from_numpy(J[E]).float().to(dev)
 
-    def sync_time(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
-
     scene = raycast.build(v_dev, f_dev)
     if opt.kernel_run:
         scenegen.pictures(scene, K, poses, H, W, ss=opt.ss)
@@ -139,7 +107,8 @@ def main():
             "raycast.visible_lines, 16 samples an edge (%d rays) %.4f s, mean visible fraction %.3f"
             % (E.shape[0], opt.views, med(te), runs.idx.shape[0], samples, E.shape[0] * opt.views * 16, med(tl), frac.mean().item())]
     print("\n".join(out[1:]), flush=True)
-    out += kernel_table(opt)
+    out += kernel_table(__file__, ["--kernel-run", "--level", str(opt.level), "--views", str(opt.views), "--res", str(opt.res)],
+                        "the build, the pictures and the edges once; %d kernels, %.3f s of kernel time", 10)
     with open(opt.out, "w") as fh:
         fh.write("\n".join(out) + "\n")
     print("wrote", opt.out)

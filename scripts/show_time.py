@@ -12,15 +12,13 @@ other extreme of the mesh pass.  The host baseline draws what the reference's lo
 import argparse
 import os
 import statistics
-import sys
 import tempfile
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT
 
 
 def wireframe(n, seed=0):

@@ -9,43 +9,14 @@ count back once per iteration, so host time is part of what a user waits for).  
 once more as a fresh process under `rocprofv3 --kernel-trace --stats` (--kernel-run: one warm-up and one traced view in the default build).
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
-import sys
-import tempfile
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def kernel_table(opt, rows=14):
-    """This script once more under rocprofv3 --kernel-trace --stats (a process of its own) -> the top rows of its kernel table."""
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "420", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run", "--width", str(opt.width), "--height", str(opt.height), "--fov", str(opt.fov)]
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: one warm-up and one traced view, default build; %d kernels, %.3f s of kernel time"
-           % (len(table), total * 1e-9), "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        name = r["Name"].split("(")[0][-72:]
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (name, int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    own = [r for r in table if "trace_" in r["Name"]]
-    out.append("# the trace kernels (trace_*): %d launches, %.3f ms in all" % (sum(int(r["Calls"]) for r in own),
-                                                                              sum(float(r["TotalDurationNs"]) for r in own) * 1e-6))
-    return out
+from timing import ROOT, kernel_table
 
 
 def main():
@@ -98,7 +69,8 @@ def main():
         lines.append("%-7s %9.4f %10.2f %11d %9d %15d %16.4f %26.1f" % (prec, t_s, tm["evals"] / (H * W), len(rec), counts[trace.HIT],
                                                                        counts[trace.UNCONVERGED], r_s, r_s / t_s))
         print(lines[-1], flush=True)
-    lines += kernel_table(opt)
+    lines += kernel_table(__file__, ["--kernel-run", "--width", str(opt.width), "--height", str(opt.height), "--fov", str(opt.fov)],
+                          "one warm-up and one traced view, default build; %d kernels, %.3f s of kernel time", 14, limit=420, family=("trace", "trace_"))
     with open(opt.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     print("wrote", opt.out)

@@ -13,33 +13,14 @@ a size the CPU finishes, with the device's time for that size.  The kernel table
 a fresh process under `rocprofv3 --kernel-trace --stats` (--kernel-run: the workload twice).  None of these times is a pass condition.
 """
 import argparse
-import csv
-import glob
 import math
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        r = fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return statistics.median(ts), min(ts), max(ts), r
+from timing import ROOT, kernel_table, timed
 
 
 def torch_pair_count(consts, cam, nb, cos_min, overlap_min):
@@ -72,24 +53,6 @@ def torch_pair_count(consts, cam, nb, cos_min, overlap_min):
             uni = hi.clamp(min=1.0) - lo.clamp(max=0.0)
             total += (ok & (inter >= overlap_min * uni)).sum()
     return int(total.item())
-
-
-def kernel_table(args, rows=12):
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["timeout", "-k", "10", "300", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable,
-               os.path.abspath(__file__), "--kernel-run"] + args
-        p = subprocess.run(cmd, capture_output=True, text=True)
-        found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
-        if p.returncode != 0 or not found:
-            return ["# no kernel table: rocprofv3 exit %s, %d stats files" % (p.returncode, len(found))]
-        table = list(csv.DictReader(open(found[0])))
-    total = sum(float(r["TotalDurationNs"]) for r in table)
-    out = ["# rocprofv3 --kernel-trace --stats, a run of its own: the workload twice; %d kernels, %.3f s of kernel time" % (len(table), total * 1e-9),
-           "# %-72s %8s %12s %10s %7s" % ("kernel", "calls", "total ms", "avg us", "%")]
-    for r in sorted(table, key=lambda r: -float(r["TotalDurationNs"]))[:rows]:
-        out.append("  %-72s %8d %12.3f %10.2f %7.2f" % (r["Name"].split("(")[0][-72:], int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
-                                                       float(r["TotalDurationNs"]) / int(r["Calls"]) * 1e-3, 100.0 * float(r["TotalDurationNs"]) / total))
-    return out
 
 
 def main():
@@ -152,7 +115,8 @@ def main():
                      "%d hypotheses, %d lines; equal to the device's: %s"
                      % (opt.host_views, opt.host_segments, t1, med1 * 1e3, lo1 * 1e3, hi1 * 1e3, t1 / med1, ref["rows"].shape[0], ref["lines3d"].shape[0], same))
     if not opt.no_trace:
-        lines += kernel_table(["--views", str(opt.views), "--segments", str(opt.segments), "--neighbours", str(M)])
+        lines += kernel_table(__file__, ["--kernel-run", "--views", str(opt.views), "--segments", str(opt.segments), "--neighbours", str(M)],
+                              "the workload twice; %d kernels, %.3f s of kernel time", 12)
     text = "\n".join(lines) + "\n"
     print(text, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
