@@ -8,7 +8,6 @@ runs in neat_amd/csrc; what stays in torch here is the R-sized glue of the attra
 import math
 
 import numpy as np
-import os
 
 import torch
 from torch import nn
@@ -363,8 +362,6 @@ class VolSDFNetwork(_HipModule):
         for head in (self.rendering_network, self.attraction_network, self.implicit_network):
             head.__dict__["_neat_owner"] = weakref.ref(self)
         self.static_randoms = None        # see _cpu_random
-        self.use_side_stream = int(os.environ.get("NEAT_SIDE_STREAMS", "0"))   # forward(): bit 0: ffn(latents), bit 1: get_outputs(points3d) on a second stream
-        self._side = {}
         self.z_vals_override = None       # bench/tests: given depth samples [R,S] bypass the sampler
         # new optional key.  Default = the parity-grade build a maintainer should get from changing `train.model_class` alone: fp16x3
         # passes every reference golden at the fp32 bars (outputs 1e-4, gradients 2e-3) at 8x the speed of the exact-f32 build
@@ -390,8 +387,14 @@ class VolSDFNetwork(_HipModule):
     def _sphere(self):
         return 0.0 if self.white_bkgd else self.scene_bounding_sphere
 
+    @staticmethod
+    def _require_cuda(uv):
+        """The model has no CPU path (ops._f32c refuses host tensors further down): say so before any work is queued."""
+        if not uv.is_cuda:
+            raise RuntimeError("neat_amd.VolSDFNetwork needs CUDA inputs (no CPU path): got uv on %s" % uv.device)
+
     def _render(self, cam_loc, ray_dirs, z_vals, want_normal_map, eik_points=None, with_eik=False):
-        if z_vals.is_cuda and type(self.density) is LaplaceDensity:
+        if type(self.density) is LaplaceDensity:
             # the raw parameter and beta_min: |beta| + beta_min (density.py:29-30) is formed inside the compositing kernels and its
             # backward (sum over the rays, sign) inside neat_render_backward -- five elementwise launches less per step
             beta, beta_min = self.density.beta, self.density.beta_min
@@ -424,7 +427,7 @@ class VolSDFNetwork(_HipModule):
         return ops.volume_weights(z_vals, sdf, self.density.get_beta())
 
     def _rays(self, input, key="uv"):
-        if input[key].is_cuda and input["pose"].shape[1:] == (4, 4):      # directions and the per-ray camera centre in one launch
+        if input["pose"].shape[1:] == (4, 4):      # directions and the per-ray camera centre in one launch
             dirs, _, origins = ops.camera_rays(input[key], input["pose"], input["intrinsics"], with_origins=True)
             return dirs.reshape(-1, 3), origins
         dirs, cam = rend_util.get_camera_params(input[key], input["pose"], input["intrinsics"])
@@ -435,13 +438,14 @@ class VolSDFNetwork(_HipModule):
         if self.z_vals_override is not None:
             z = self.z_vals_override
             idx = self._cpu_random("eik_idx", lambda: torch.randint(z.shape[-1], (z.shape[0],)), z.device)
-            if z.is_cuda and self.training and not self.junction_eikonal:
+            if self.training and not self.junction_eikonal:
                 return z, (z, idx)          # the eikonal-point launch picks z[r, idx[r]] itself (ops.eik_points)
             return z, z.gather(1, idx.unsqueeze(-1))
         return self.ray_sampler.get_z_vals(ray_dirs, cam_loc, self)
 
     def render_rgb(self, input):
         assert not self.training
+        self._require_cuda(input["uv"])
         ray_dirs, cam_loc = self._rays(input)
         z_vals, _ = self._z_vals(ray_dirs, cam_loc)
         return self._render(cam_loc, ray_dirs, z_vals, False)[0]
@@ -450,11 +454,21 @@ class VolSDFNetwork(_HipModule):
         """-> (setup, ray_dirs [R,3], cam_loc [R,3]): the rays through `uv`.  setup = ops.camera_setup's tuple if the caller allows its one
         launch and it applies (it then carries the rays through uv_proj as well, if given), else None and the rays come from _rays."""
         intrinsics, uv, pose = input["intrinsics"], input["uv"], input["pose"]
-        if (one_launch and uv.is_cuda and pose.shape == (1, 4, 4) and intrinsics.dtype == torch.float32 and intrinsics.stride(-1) == 1
+        if (one_launch and pose.shape == (1, 4, 4) and intrinsics.dtype == torch.float32 and intrinsics.stride(-1) == 1
                 and intrinsics.shape[0] == 1):
             setup = ops.camera_setup(uv, uv_proj, pose, intrinsics)
             return setup, setup[0], setup[1]
         return (None,) + tuple(self._rays(input))
+
+    def _world_to_camera(self, input, setup):
+        """-> (w2c [3,4] = [R | T] of pose^-1, K3 [3,3]), both contiguous (rend_a :424-431, :440): from the camera_setup launch if it ran,
+        else one camera_mats launch, else (a pose or intrinsics that launch does not take) inv_small; no host sync either way."""
+        intrinsics, pose = input["intrinsics"], input["pose"]
+        if setup is not None:
+            return setup[3], setup[4]
+        if pose.shape[1:] == (4, 4) and intrinsics.dtype == torch.float32 and intrinsics.stride(-1) == 1:
+            return ops.camera_mats(pose[0], intrinsics[0])
+        return ops.inv_small(pose[0])[:3].contiguous(), intrinsics[0, :3, :3].contiguous()
 
     @torch.no_grad()
     def render_pixels(self, uv, pose, intrinsics):
@@ -462,13 +476,16 @@ class VolSDFNetwork(_HipModule):
         forward -- camera rays, the sampler and the main pass, without the junction and line block -- bit for bit what forward returns
         as rgb_values, normal_map and depth on the same pixels (neat_amd.render walks a view with it)."""
         assert not self.training
+        self._require_cuda(uv)
         _, ray_dirs, cam_loc = self._camera({"uv": uv, "pose": pose, "intrinsics": intrinsics}, True)
         z_vals, _ = self._z_vals(ray_dirs, cam_loc)
         rgb, _, depth, _, _, _, _, nmap = self._render(cam_loc, ray_dirs, z_vals, True)
         return rgb, nmap, depth
 
     def forward(self, input):
-        intrinsics, uv, pose = input["intrinsics"], input["uv"], input["pose"]
+        """The reference's forward (rend_a :392-527) step by step; every step runs on the current stream."""
+        uv = input["uv"]
+        self._require_cuda(uv)
         # camera-only work of the whole forward in one launch: rays through uv and through uv_proj, [R | T] of pose^-1, the contiguous
         # intrinsics (round 6; before: camera_rays twice + camera_mats)
         with_proj = "uv_proj" in input and input["uv_proj"].shape == uv.shape
@@ -487,175 +504,114 @@ class VolSDFNetwork(_HipModule):
             rgb, lines3d, depth, xyz, weights, sdf_s, points, nmap = self._render(cam_loc, ray_dirs, z_vals, not self.training)
         output = {"points": points, "rgb_values": rgb, "sdf": sdf_s, "depth": depth, "xyz": xyz}
 
-        # ---- attraction field / junctions (rend_a :424-513); R-sized, stays in torch -------------------
-        # Two pieces of this block do not feed the matching below and run on a side stream, concurrently with it: the
-        # global junctions ffn(latents) (depends on parameters only; autograd runs its backward on that stream too, next
-        # to the render backward) and get_outputs(points3d) with the l3d geometry (latency-bound R-point launches).
-        points3d = xyz
-        main = torch.cuda.current_stream() if xyz.is_cuda else None
-        side = self._side_stream(xyz.device) if (main is not None and self.use_side_stream) else None
-        if setup is not None:
-            w2c, K3 = setup[3], setup[4]
-        elif xyz.is_cuda and pose.shape[1:] == (4, 4) and intrinsics.dtype == torch.float32 and intrinsics.stride(-1) == 1:
-            w2c, K3 = ops.camera_mats(pose[0], intrinsics[0])     # [R | T] of pose^-1 and the contiguous 3x3 intrinsics: one launch, no sync
-        else:
-            w2c = ops.inv_small(pose[0])[:3]                 # one launch, no host-side singularity check, no sync
-            K3 = intrinsics[0, :3, :3]
-        Rm, T = w2c[:, :3], w2c[:, 3:]
-        eye = _eye3(K3.device)
-
-        def l3d_block():
-            if points3d.is_cuda:          # get_outputs(points3d) (rend_a :441-443) without the row-major copies of lin8's output (one
-                # launch): the junction block reads the sdf and the normal only; both keep their graph to the parameters
-                net = self.implicit_network
-                p3_sdf, p3_grad = ops.sdf_point_normals(net.handle(), points3d, net.sdf_bounding_sphere, net.sphere_scale)
-            else:
-                p3_sdf, _, p3_grad = self.implicit_network.get_outputs(points3d)
-            l_dirs, l_orig = (setup[2], cam_loc) if setup is not None else self._rays(input, "uv_proj")
-            if points3d.is_cuda:          # plane intersection per ray: one launch
-                l3d = ops.l3d_points(points3d, l_orig, l_dirs, p3_grad)
-            else:
-                den = (l_dirs * p3_grad).sum(-1)
-                den = den + torch.where(den >= 0, torch.full_like(den, 1e-6), torch.full_like(den, -1e-6))
-                t = (((points3d - l_orig) * p3_grad).sum(-1) / den).detach()
-                l3d = l_orig + l_dirs * t.unsqueeze(-1)
-            l3d_score = None
-            if self.training and self.use_l3d:      # only the l3d candidate filter reads the score (rend_a :455-468)
-                with torch.no_grad():
-                    a, b = l3d - lines3d[:, 0], l3d - lines3d[:, 1]
-                    l3d_score = torch.linalg.cross(a, b).norm(dim=-1) / (lines3d[:, 0] - lines3d[:, 1]).norm(dim=-1)
-            return p3_sdf, l3d, l3d_score
-
-        j3d_global = None
-        if side is not None:
-            side_b = self._side_stream(xyz.device, 1)
-            side.wait_stream(main)
-            side_b.wait_stream(main)
-            if self.training:
-                if self.use_side_stream & 1:
-                    with torch.cuda.stream(side):
-                        j3d_global = self._global_junctions()
-                    j3d_global.record_stream(main)
-                else:
-                    j3d_global = self._global_junctions()
-            if self.use_side_stream & 2:
-                with torch.cuda.stream(side_b):
-                    p3_sdf, l3d, l3d_score = l3d_block()
-                for tns in (p3_sdf, l3d, l3d_score):
-                    if tns is not None:
-                        tns.record_stream(main)
-            else:
-                p3_sdf, l3d, l3d_score = l3d_block()
-                side_b = None
-            if self.training and self.use_l3d and side_b is not None:
-                main.wait_stream(side_b)
-                side_b = None
-        else:
-            side_b = None
-            if self.training:
-                j3d_global = self._global_junctions()
-            p3_sdf, l3d, l3d_score = l3d_block()
-        if xyz.is_cuda:        # one launch per projection (forward / backward) instead of ~16 R-sized torch kernels
-            K3c, w2c3 = K3.contiguous(), w2c.contiguous()
-            K3 = K3c           # the loss inverts output["K"]: hand it the contiguous copy
-            proj = lambda Kc, X: ops.project2d(Kc, w2c3, X)
-            # the same points with K (pixels) and with the identity (calibrated): one launch for both (round 6)
-            proj_pair = lambda X: ops.project2d_pair(K3c, eye, w2c3, X)
-        else:
-            K3c = K3
-            proj = lambda Kc, X: self.project2D(Kc, Rm, T, X)
-            proj_pair = lambda X: (proj(K3c, X), proj(eye, X))
-        if xyz.is_cuda:
-            lines2d, lines2d_calib = proj_pair(lines3d)
-            lines2d = lines2d.detach()      # (rend_a :436: the pixel projection is taken of lines3d.detach())
-        else:
-            lines2d = proj(K3c, lines3d.detach())
-            lines2d_calib = proj(eye, lines3d)
+        # ---- attraction field / junctions (rend_a :424-513) ---------------------------------------------
+        w2c, K3 = self._world_to_camera(input, setup)
+        eye = _eye3(K3.device)          # every projection below is taken twice, with K3 (pixels) and with the identity (calibrated): one launch
+        j3d_global = self._global_junctions() if self.training else None
+        p3_sdf, l3d, l3d_score = self._surface_geometry(input, setup, cam_loc, xyz, lines3d)
+        lines2d, lines2d_calib = ops.project2d_pair(K3, eye, w2c, lines3d)
+        lines2d = lines2d.detach()      # (rend_a :436: the pixel projection is taken of lines3d.detach())
         if self.training:
-            cand_valid = None
-            if self.dbscan_enabled:
-                if lines3d.is_cuda and 2 <= 2 * n_rays <= ops.DBSCAN_MAX_POINTS:
-                    # DBSCAN(eps = 0.01, min_samples = 2) + cluster means on the device: padded centres + validity mask,
-                    # no host round trip (reference: sklearn on the host, :328-339, :460)
-                    cand3d, cand_valid, _ = ops.dbscan_means(lines3d.detach().reshape(-1, 3), 0.01)
-                else:
-                    cand3d = self.cluster_dbscan(lines3d.detach().cpu().numpy().reshape(-1, 3), eps=0.01, min_samples=2)
-            elif self.use_l3d:
-                thr = l3d_score.median().clamp_min(0.01)
-                keep = l3d_score < thr          # data-dependent shape: one host sync, as the reference (:465-468)
-                cand3d = torch.cat([lines3d[keep].detach().reshape(-1, 3), l3d[keep]], 0)
-            else:
-                cand3d = lines3d.detach().reshape(-1, 3)
-            if self.dbscan_enabled or self.use_l3d:
-                cand2d, cand2d_calib = proj_pair(cand3d)
-            else:      # the candidates ARE the line end points: their projections were just computed (same arithmetic, same values)
-                cand2d = lines2d.reshape(-1, 2)
-                cand2d_calib = lines2d_calib.detach().reshape(-1, 2)
+            cand3d, cand_valid, cand2d, cand2d_calib = self._junction_candidates(lines3d, lines2d, lines2d_calib, l3d, l3d_score, K3, eye, w2c)
             gt2d = _device_copy(input["wireframe"][0], "vertices", cand2d.device)
-            fused_gate = cand2d.is_cuda and min(gt2d.shape[0], cand2d.shape[0]) <= 2048
-            cost = ops.junction_cost(cand2d, gt2d) if fused_gate else ((cand2d[None] - gt2d[:, None]) ** 2).sum(-1).sqrt()
-            # Hungarian matching on the device (reference: scipy on the host, :473).  Without a candidate mask every gt
-            # junction / candidate of the smaller side is matched, so the pair count min(V, C) is static; with the padded
-            # DBSCAN centres the pairs beyond the device-side count come back as -1 and are masked out
-            rows, cols, _ = ops.linear_sum_assignment(cost, None, cand_valid)
-            if fused_gate:
-                # matched costs, median / 10 px gate and the gathered matched candidates: one launch (:474-489)
-                median, good, j3_pad, j2_pad, j2c_pad = ops.junction_gate(rows, cols, cost, cand3d, cand2d, cand2d_calib, self.use_median)
-                if self.use_median:
-                    output["median"] = median
-            else:
-                if cand_valid is None:
-                    matched = cost[rows, cols]
-                    pair_ok = None
-                else:
-                    pair_ok = rows >= 0
-                    rows, cols = rows.clamp_min(0), cols.clamp_min(0)
-                    matched = torch.where(pair_ok, cost[rows, cols], torch.full_like(cost[rows, cols], float("nan")))
-                if self.use_median:
-                    if matched.numel() == 0:
-                        median = matched.new_tensor(10.0)
-                    elif pair_ok is None:
-                        median = matched.detach().median()
-                    else:
-                        median = torch.nanmedian(matched.detach())
-                        median = torch.where(torch.isnan(median), torch.full_like(median, 10.0), median)
-                    good = matched < median
-                    output["median"] = median
-                else:
-                    good = matched < 10
-                if pair_ok is not None:
-                    good = good & pair_ok
-                j2_pad, j3_pad, j2c_pad = cand2d[cols], cand3d[cols], cand2d_calib[cols]
-            if side is not None:
-                main.wait_stream(side)          # join: the global junctions are needed from here on
+            median, good, padded = self._match_junctions(gt2d, cand3d, cand2d, cand2d_calib, cand_valid)
+            if self.use_median:
+                output["median"] = median
             # the reference compacts with `[good]` (:478-489), a data-dependent shape; here the matched candidates stay
             # padded + mask (what neat_amd.loss reads) and the compact tensors are built only if somebody asks for them
-            output = JunctionOutputs(output, good, {"j2d_local": j2_pad, "j3d_local": j3_pad, "j2d_local_calib": j2c_pad})
+            output = JunctionOutputs(output, good, padded)
             output["j3d_global"] = j3d_global
-            output["j2d_global"], output["j2d_global_calib"] = proj_pair(j3d_global)
-            if xyz.is_cuda:
-                output.calib_proj = {"w2c": w2c3, "lines3d": lines3d, "lines2d_calib": lines2d_calib, "j3d_global": j3d_global,
-                                     "j2d_global_calib": output["j2d_global_calib"]}
-        if side_b is not None:
-            main.wait_stream(side_b)            # join: get_outputs(points3d) / l3d ran next to the matching above
-        elif side is not None and not self.training:
-            main.wait_stream(side)
+            output["j2d_global"], output["j2d_global_calib"] = ops.project2d_pair(K3, eye, w2c, j3d_global)
+            output.calib_proj = {"w2c": w2c, "lines3d": lines3d, "lines2d_calib": lines2d_calib, "j3d_global": j3d_global,
+                                 "j2d_global_calib": output["j2d_global_calib"]}
         output["l3d"] = l3d
-        output["points3d"] = points3d
+        output["points3d"] = xyz
         output["lines3d"] = lines3d
         output["lines2d_calib"] = lines2d_calib
         output["lines2d"] = lines2d
         output["sdf"] = p3_sdf.flatten()
         output["wireframe-gt"] = input["wireframe"]
-        output["K"] = K3
+        output["K"] = K3                # contiguous: the loss inverts it
 
         if self.training:
             if grad_theta is None:
-                grad_theta = self._eikonal(n_rays, cam_loc, ray_dirs, z_eik, output["j3d_global"].detach())
+                grad_theta = self._eikonal(n_rays, cam_loc, ray_dirs, z_eik, j3d_global.detach())
             output["grad_theta"] = grad_theta
         else:
             output["normal_map"] = nmap
         return output
+
+    def _surface_geometry(self, input, setup, cam_loc, points3d, lines3d):
+        """The surface at the rendered points (rend_a :441-447) -> (sdf [R,1], l3d [R,3], l3d_score [R] or None).  l3d: where the ray
+        through the projected pixel `uv_proj` meets the tangent plane at points3d."""
+        # get_outputs(points3d) without the row-major copies of lin8's output (one launch): the junction block reads the sdf and the
+        # normal only; both keep their graph to the parameters
+        net = self.implicit_network
+        p3_sdf, p3_grad = ops.sdf_point_normals(net.handle(), points3d, net.sdf_bounding_sphere, net.sphere_scale)
+        l_dirs, l_orig = (setup[2], cam_loc) if setup is not None else self._rays(input, "uv_proj")
+        l3d = ops.l3d_points(points3d, l_orig, l_dirs, p3_grad)
+        l3d_score = None
+        if self.training and self.use_l3d:      # only the l3d candidate filter reads the score (rend_a :455-468)
+            with torch.no_grad():
+                a, b = l3d - lines3d[:, 0], l3d - lines3d[:, 1]
+                l3d_score = torch.linalg.cross(a, b).norm(dim=-1) / (lines3d[:, 0] - lines3d[:, 1]).norm(dim=-1)
+        return p3_sdf, l3d, l3d_score
+
+    def _junction_candidates(self, lines3d, lines2d, lines2d_calib, l3d, l3d_score, K3, eye, w2c):
+        """Local junction candidates (rend_a :455-471) -> (cand3d [C,3], cand_valid [C] or None, cand2d [C,2], cand2d_calib [C,2])."""
+        if not (self.dbscan_enabled or self.use_l3d):
+            # the candidates ARE the line end points: their projections are computed already (same arithmetic, same values)
+            return lines3d.detach().reshape(-1, 3), None, lines2d.reshape(-1, 2), lines2d_calib.detach().reshape(-1, 2)
+        cand_valid = None
+        if self.dbscan_enabled:
+            if 2 <= 2 * lines3d.shape[0] <= ops.DBSCAN_MAX_POINTS:
+                # DBSCAN(eps = 0.01, min_samples = 2) + cluster means on the device: padded centres + validity mask,
+                # no host round trip (reference: sklearn on the host, :328-339, :460)
+                cand3d, cand_valid, _ = ops.dbscan_means(lines3d.detach().reshape(-1, 3), 0.01)
+            else:
+                cand3d = self.cluster_dbscan(lines3d.detach().cpu().numpy().reshape(-1, 3), eps=0.01, min_samples=2)
+        else:
+            thr = l3d_score.median().clamp_min(0.01)
+            keep = l3d_score < thr          # data-dependent shape: one host sync, as the reference (:465-468)
+            cand3d = torch.cat([lines3d[keep].detach().reshape(-1, 3), l3d[keep]], 0)
+        return (cand3d, cand_valid) + tuple(ops.project2d_pair(K3, eye, w2c, cand3d))
+
+    def _match_junctions(self, gt2d, cand3d, cand2d, cand2d_calib, cand_valid):
+        """Hungarian matching of the candidates to the view's junctions and the distance gate (rend_a :472-489)
+        -> (median or None, good [K] bool, {"j2d_local", "j3d_local", "j2d_local_calib"}: the matched candidates, padded [K, .])."""
+        fused_gate = min(gt2d.shape[0], cand2d.shape[0]) <= ops.JUNCTION_GATE_MAX
+        cost = ops.junction_cost(cand2d, gt2d) if fused_gate else ((cand2d[None] - gt2d[:, None]) ** 2).sum(-1).sqrt()
+        # Hungarian matching on the device (reference: scipy on the host, :473).  Without a candidate mask every gt
+        # junction / candidate of the smaller side is matched, so the pair count min(V, C) is static; with the padded
+        # DBSCAN centres the pairs beyond the device-side count come back as -1 and are masked out
+        rows, cols, _ = ops.linear_sum_assignment(cost, None, cand_valid)
+        if fused_gate:
+            # matched costs, median / 10 px gate and the gathered matched candidates: one launch (:474-489)
+            median, good, j3_pad, j2_pad, j2c_pad = ops.junction_gate(rows, cols, cost, cand3d, cand2d, cand2d_calib, self.use_median)
+        else:
+            median = None
+            if cand_valid is None:
+                matched = cost[rows, cols]
+                pair_ok = None
+            else:
+                pair_ok = rows >= 0
+                rows, cols = rows.clamp_min(0), cols.clamp_min(0)
+                matched = torch.where(pair_ok, cost[rows, cols], torch.full_like(cost[rows, cols], float("nan")))
+            if self.use_median:
+                if matched.numel() == 0:
+                    median = matched.new_tensor(10.0)
+                elif pair_ok is None:
+                    median = matched.detach().median()
+                else:
+                    median = torch.nanmedian(matched.detach())
+                    median = torch.where(torch.isnan(median), torch.full_like(median, 10.0), median)
+                good = matched < median
+            else:
+                good = matched < 10
+            if pair_ok is not None:
+                good = good & pair_ok
+            j2_pad, j3_pad, j2c_pad = cand2d[cols], cand3d[cols], cand2d_calib[cols]
+        return median, good, {"j2d_local": j2_pad, "j3d_local": j3_pad, "j2d_local_calib": j2c_pad}
 
     def _global_junctions(self):
         """ffn(latents) (rend_a :491).  The shipped architecture (Linear-ReLU-Linear-ReLU-Linear, 256 wide) on CUDA goes
@@ -666,12 +622,6 @@ class VolSDFNetwork(_HipModule):
                 and tuple(lin[2].weight.shape) == (3, 256)):
             return ops.ffn_junctions(self.latents, lin)
         return self.ffn(self.latents)
-
-    def _side_stream(self, device, idx=0):
-        key = (str(device), idx)
-        if key not in self._side:
-            self._side[key] = torch.cuda.Stream(device=device)
-        return self._side[key]
 
     def _cpu_random(self, name, draw, device):
         """Randoms are drawn on the CPU (the reference's RNG stream).  Normally: draw + asynchronous pinned copy.  With
@@ -687,19 +637,13 @@ class VolSDFNetwork(_HipModule):
         return slot["dev"]
 
     def _eikonal_points(self, n_rays, cam_loc, ray_dirs, z_eik, junctions):
-        """Eikonal points: uniform in the bounding cube + one near-surface sample per ray (rend_a :515-527)."""
+        """Eikonal points: uniform in the bounding cube + one near-surface sample per ray (rend_a :515-527):
+        [uniform | o + z d | junctions] in one launch."""
         r = self.scene_bounding_sphere
         eik = self._cpu_random("eik_uniform", lambda: torch.empty(n_rays, 3).uniform_(-r, r), ray_dirs.device)
         if isinstance(z_eik, tuple):          # (depths [R,S], drawn index per ray): given depth samples (_z_vals)
-            if eik.is_cuda:
-                return ops.eik_points(eik, cam_loc, ray_dirs, None, junctions, z=z_eik[0], idx=z_eik[1])
-            z_eik = z_eik[0].gather(1, z_eik[1].unsqueeze(-1))
-        if eik.is_cuda:
-            return ops.eik_points(eik, cam_loc, ray_dirs, z_eik, junctions)       # [uniform | o + z d | junctions]: one launch
-        eik = torch.cat([eik, torch.addcmul(cam_loc, z_eik, ray_dirs)], 0)
-        if junctions is not None:
-            eik = torch.cat([eik, junctions], 0)
-        return eik
+            return ops.eik_points(eik, cam_loc, ray_dirs, None, junctions, z=z_eik[0], idx=z_eik[1])
+        return ops.eik_points(eik, cam_loc, ray_dirs, z_eik, junctions)
 
     def _eikonal(self, n_rays, cam_loc, ray_dirs, z_eik, junctions):
         return self.implicit_network.gradient(self._eikonal_points(n_rays, cam_loc, ray_dirs, z_eik, junctions))

@@ -794,6 +794,7 @@ def ffn_junctions(x, linears):
 
 
 DBSCAN_MAX_POINTS = 8192
+JUNCTION_GATE_MAX = 2048      # neat_junction_gate refuses K = min(V, C) pairs above it (its matched costs live in LDS): the model gates in torch then
 
 
 def dbscan_means(points, eps):

@@ -272,6 +272,26 @@ def test_ops_refuse_cpu_tensors():
         m.implicit_network.get_sdf_vals(torch.zeros(4, 3))      # no CPU fallback: must fail loudly
 
 
+def test_model_refuses_cpu_inputs():
+    """The model's three entry points refuse host tensors up front, with the exception type and phrase of ops._f32c."""
+    import torch
+    from neat_amd import networks, synth
+    from neat_amd.wireframe import WireframeGraph
+    sc = synth.synth_scene(seed=9, n_rays=8)
+    inp = {k: torch.tensor(sc[k]) for k in ("intrinsics", "pose", "uv", "uv_proj")}
+    inp["wireframe"] = [WireframeGraph(*(torch.tensor(sc[k]) for k in ("wf_vertices", "wf_vconf", "wf_edges", "wf_weights")), 512, 512)]
+    m = networks.VolSDFNetwork(synth.ABC_NEAT_A_MODEL_CONF)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m(inp)
+    m.eval()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m(inp)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m.render_rgb(inp)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m.render_pixels(inp["uv"], inp["pose"], inp["intrinsics"])
+
+
 def test_torch_ops_are_registered_for_the_gpu_only():
     """torch.ops.neat_hip.* (neat_amd/torch_ops.py) exist with tensor/scalar schemas and have no CPU kernel: the dispatcher refuses."""
     import torch

@@ -1996,6 +1996,77 @@ def test_device_dbscan_path_equals_host_path(dev):
     close(wa, wb, tol=1e-5, what="lin3 grad")
 
 
+@pytest.mark.parametrize("use_median", [True, False])
+def test_torch_gate_equals_fused_gate(dev, use_median):
+    """The model's matching and gate with the one-launch gate (ops.junction_cost + ops.junction_gate) against its torch formulation, the
+    branch taken when both sides of the matching exceed ops.JUNCTION_GATE_MAX (forced here by setting the limit to 0): same mask, same
+    matched junctions, same median, same loss and gradients.  Scene 9 (seed 9) with 96 rays: 8 pairs.
+    The two cost formulas may differ in the last place, so the test first requires that no matched cost of the fused run lies within
+    1e-3 of its threshold.  With the median gate the threshold IS one of the matched costs (the lower median, an element): that
+    element is compared with itself in either formulation and fails `<` exactly; every other cost must keep the distance."""
+    import copy
+    from neat_amd import networks, ops
+    from neat_amd.loss import VolSDFLoss
+    from tests.util_replay import RngReplay
+    conf = copy.deepcopy(synth.ABC_NEAT_A_MODEL_CONF)
+    conf["use_median"] = use_median
+    sd = {k: T(v) for k, v in synth.synth_state_dict(9, "rough").items()}
+    R, S = 96, 40
+    sc = synth.synth_scene(seed=9, n_rays=R)
+    z = T(synth.synth_z_vals(9, R, S)).to(dev)
+    gen = torch.Generator().manual_seed(9)
+    eik_idx = torch.randint(S, (R,), generator=gen)
+    eik_uniform = torch.empty(R, 3).uniform_(-3, 3, generator=gen)
+    gt = {"rgb": T(sc["gt_rgb"]).to(dev), "lines2d": T(sc["gt_lines2d"]).to(dev)}
+    res, seen = [], []
+    fused_gate = ops.junction_gate
+
+    def recording_gate(rows, cols, cost, *rest):
+        seen.append(cost[rows, cols])
+        return fused_gate(rows, cols, cost, *rest)
+
+    for fused in (True, False):
+        m = networks.VolSDFNetwork(conf)
+        m.load_state_dict(sd)
+        m.to(dev).train()
+        m.z_vals_override = z
+        limit = ops.JUNCTION_GATE_MAX
+        try:
+            ops.junction_gate = recording_gate
+            if not fused:
+                ops.JUNCTION_GATE_MAX = 0            # forces the torch gate
+            with RngReplay([("randint", eik_idx), ("uniform_", eik_uniform)]):
+                out = m(scene_inputs(sc, dev))
+        finally:
+            ops.JUNCTION_GATE_MAX = limit
+            ops.junction_gate = fused_gate
+        lo = VolSDFLoss(**synth.ABC_NEAT_A_LOSS_CONF)(out, gt)
+        lo["loss"].backward()
+        res.append((out.good.clone(), {k: v.detach() for k, v in out.padded.items()}, out["median"].detach() if use_median else None,
+                    float(lo["loss"].detach()), float(lo["j3d_loss"].detach()),
+                    m.latents.grad.detach().clone(), m.implicit_network.lin3.weight_v.grad.detach().clone()))
+    (good_a, pad_a, med_a, la, j3a, ga, wa), (good_b, pad_b, med_b, lb, j3b, gb, wb) = res
+    assert len(seen) == 1, "the fused gate ran in exactly one of the two forwards"
+    matched = seen[0].cpu()
+    assert matched.shape == (8,)
+    dist = (matched - (float(med_a) if use_median else 10.0)).abs()
+    print("matched costs", matched.tolist(), "median", None if med_a is None else float(med_a), "good", good_a.tolist())
+    if use_median:
+        assert int((dist == 0).sum()) == 1 and int((dist > 1e-3).sum()) == matched.numel() - 1, dist
+    else:
+        assert bool((dist > 1e-3).all()), dist
+    assert bool(good_a.any()) and not bool(good_a.all())
+    assert torch.equal(good_a, good_b)
+    for k in ("j3d_local", "j2d_local", "j2d_local_calib"):
+        assert pad_a[k].shape == pad_b[k].shape
+        close(pad_a[k][good_a], pad_b[k][good_a], tol=1e-5, what=k)
+    if use_median:
+        close(med_a, med_b, tol=1e-5, what="median")
+    assert abs(la - lb) <= 1e-6 * max(1.0, abs(lb)) and abs(j3a - j3b) <= 1e-6 * max(1.0, abs(j3b))
+    close(ga, gb, tol=1e-5, what="latents grad")
+    close(wa, wb, tol=1e-5, what="lin3 grad")
+
+
 @pytest.mark.parametrize("use_median,R", [(True, 96), (False, 33)])
 def test_fused_loss_tail_vs_torch_formulation(dev, use_median, R):
     """VolSDFLoss with the fused tail (neat_loss_terms / neat_loss_pairs) against the torch formulation of the same
