@@ -833,6 +833,30 @@ int neat_crease_chains(const double* verts, int nv, int nf, int E, double sin2_t
 int neat_crease_fill(const double* verts, int nv, int nf, int E, void* ws, int n_lines, int n_junc, double* junctions, int* vertex, int* lines,
                      unsigned char* kind, unsigned char* curved, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): 2-D wireframes with shared junctions from the views' detected
+ * segments (neat_amd/detect.py junctions): ends that meet near the crossing of their lines become one junction, a lone end that stops
+ * at another segment's inside becomes a T, duplicate and collapsed segments are dropped.  The rule: DESIGN 3o and
+ * neat_amd/csrc/kernels_wireframe2d.hpp, restated in float64 by tests/junctions2d_f64.py, which the device equals byte for byte.
+ * Float64 without contraction, no transcendental function; a union-find whose roots are the smallest member, counted, scanned and
+ * filled lists: two runs give the same bytes.  All views in one set of nine launches whose count does not depend on the data;
+ * asynchronous on the stream, no allocation, no read-back.  Bad arguments return -1 before any launch.
+ *
+ * neat_wf2d_scratch_bytes : the workspace (256-byte aligned, caller-owned); 0 when refused: a negative count, V > 65535, nmax > S,
+ *   segments without a view or with nmax = 0, 10 S or V ceil(nmax / 256) beyond 2^31 - 1.
+ * neat_wf2d_build : segments float64 [S,4] = x1 y1 x2 y2 in (view, index) order, segoff int32 [V+1] ascending from 0 to S, weight
+ *   float64 [S] (finite).  nmax: no view holds more segments (any upper bound up to S; it sizes the grids).  gap > 0 pixels,
+ *   0 < frac < 0.5, 0 < sin_min <= 1 the sine of the least angle between two lines that may cross, t_junctions 0 / 1.
+ *   Per vertex, capacity 2 S, the views one after the other, each in ascending order of the vertex's lowest endpoint (end k of segment i
+ *   is endpoint 2 i + k): vertices float64 [.,2], degree int32 (ends joined), kind int32 (0 a free end, 1 a junction, 2 a T), score
+ *   float64 (the largest weight of its segments), spread float64 (the largest distance from the vertex to an end it replaces), t_edge
+ *   int32 (kind 2: the segment it stands on, numbered in its view; else -1); voff int32 [V+1] the views' first vertices, voff[V] the count.
+ *   ends int32 [S,2]: the vertex of each end, numbered in its view.  Per edge, capacity S, in segment order: edges int32 [.,2] (vertices
+ *   numbered in the view), eweight float64, esrc int32 (the segment, numbered in its view); eoff int32 [V+1]. */
+size_t neat_wf2d_scratch_bytes(int V, int S, int nmax);
+int neat_wf2d_build(const double* segments, const int* segoff, const double* weight, int V, int S, int nmax, double gap, double frac, double sin_min,
+                    int t_junctions, void* ws, double* vertices, int* degree, int* kind, double* score, double* spread, int* t_edge, int* voff,
+                    int* ends, int* edges, double* eweight, int* esrc, int* eoff, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

@@ -20,6 +20,7 @@
 #include "kernels_detect.hpp"
 #include "kernels_triangulate.hpp"
 #include "kernels_crease.hpp"
+#include "kernels_wireframe2d.hpp"
 #include "ws_layout.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
@@ -1579,6 +1580,46 @@ int neat_crease_fill(const double* verts, int nv, int nf, int E, void* ws, int n
                      (const int*)w.ltag, (const int*)w.jmap, lines, kind, curved);
   hipLaunchKernelGGL(crease_junction_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, verts, nv, (const int*)w.jflag, (const int*)w.jmap, n_junc, junctions,
                      vertex);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: 2-D wireframes with shared junctions from the views' segments (kernels_wireframe2d.hpp) -------------------------------
+size_t neat_wf2d_scratch_bytes(int V, int S, int nmax) {
+  Wf2dWs w;
+  return wf2d_layout(nullptr, V, S, nmax, WF_WG, &w) ? w.total : 0;
+}
+
+int neat_wf2d_build(const double* segments, const int* segoff, const double* weight, int V, int S, int nmax, double gap, double frac, double sin_min,
+                    int t_junctions, void* ws, double* vertices, int* degree, int* kind, double* score, double* spread, int* t_edge, int* voff,
+                    int* ends, int* edges, double* eweight, int* esrc, int* eoff, void* stream) {
+  Wf2dWs w;
+  if (!(gap > 0.0) || !std::isfinite(gap) || !(frac > 0.0 && frac < 0.5) || !(sin_min > 0.0 && sin_min <= 1.0) || !voff || !eoff ||
+      !wf2d_layout(ws, V, S, nmax, WF_WG, &w))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (S == 0) {
+    NEAT_CHECK(hipMemsetAsync(voff, 0, ((size_t)V + 1) * sizeof(int), st));
+    return (int)hipMemsetAsync(eoff, 0, ((size_t)V + 1) * sizeof(int), st);
+  }
+  if (!segments || !segoff || !weight || !ws || ((uintptr_t)ws & 255) || !vertices || !degree || !kind || !score || !spread || !t_edge || !ends ||
+      !edges || !eweight || !esrc)
+    return -1;
+  const dim3 per_seg(grid1(S, WF_WG)), per_end(grid1(2 * S, WF_WG)), per_wave(grid1(2 * S, WF_WAVES)), pairs((unsigned)((long long)V * w.tiles));
+  hipLaunchKernelGGL(wf_segment_kernel, per_seg, dim3(WF_WG), 0, st, segments, segoff, V, S, gap, frac, w.rec, w.view, w.parent, w.last);
+  hipLaunchKernelGGL(wf_meet_kernel, pairs, dim3(WF_WG), 0, st, segoff, S, w.tiles, (const double*)w.rec, sin_min, w.parent);
+  hipLaunchKernelGGL(wf_flatten_kernel, per_end, dim3(WF_WG), 0, st, 2 * S, w.parent, w.last);
+  NEAT_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(wf_vertex_scan_kernel, dim3(1), dim3(1024), 0, st, S, V, segoff, (const int*)w.parent, w.vidx, voff);
+  hipLaunchKernelGGL(wf_junction_kernel, per_wave, dim3(WF_WG), 0, st, 2 * S, (const int*)w.parent, (const int*)w.last, (const int*)w.vidx,
+                     (const double*)w.rec, weight, vertices, degree, kind, score, spread, t_edge);
+  hipLaunchKernelGGL(wf_tee_kernel, pairs, dim3(WF_WG), 0, st, segoff, S, w.tiles, (const double*)w.rec, weight, sin_min, t_junctions ? 1 : 0,
+                     (const int*)w.parent, (const int*)w.last, (const int*)w.vidx, (const int*)voff, vertices, degree, kind, score, spread, t_edge,
+                     ends);
+  NEAT_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(wf_duplicate_kernel, pairs, dim3(WF_WG), 0, st, segoff, S, w.tiles, (const int*)ends, weight, w.keep);
+  hipLaunchKernelGGL(wf_edge_scan_kernel, dim3(1), dim3(1024), 0, st, S, V, segoff, (const int*)w.keep, w.eidx, eoff);
+  hipLaunchKernelGGL(wf_edge_fill_kernel, per_seg, dim3(WF_WG), 0, st, S, segoff, (const int*)w.view, (const int*)w.keep, (const int*)w.eidx,
+                     (const int*)ends, weight, edges, eweight, esrc);
   return (int)hipGetLastError();
 }
 

@@ -460,4 +460,32 @@ inline bool crease_layout(void* ws, int nv, int nf, int scan_tile, CreaseWs* w) 
   return true;
 }
 
+// ---- 2-D wireframes with shared junctions (kernels_wireframe2d.hpp) over V views, S segments in all, nmax in one view at most (an upper
+// bound will do: it sizes the pair launches' grid).  Every region is bounded by S.  rec [8 S] (p, q, u, L, g) | view [S] | per endpoint:
+// parent (then the label), last (a root's highest member), vidx (a root's place in the vertex list) [2 S] each | keep, eidx [S] (a
+// segment is an edge; the edges before it)
+constexpr int WF_MAX_VIEWS = 65535;
+inline bool wf2d_counts_ok(long long V, long long S, long long nmax, int tile) {
+  if (V < 0 || S < 0 || nmax < 0 || V > WF_MAX_VIEWS || nmax > S || S > 0x7fffffffLL / 10 || (S > 0 && (V == 0 || nmax == 0))) return false;
+  return V * ((nmax + tile - 1) / tile) <= 0x7fffffffLL;
+}
+struct Wf2dWs {
+  int tiles;                // tiles of one view in the pair launches: ceil(nmax / tile)
+  double* rec; int *view, *parent, *last, *vidx, *keep, *eidx;
+  size_t total;
+};
+inline bool wf2d_layout(void* ws, int V, int S, int nmax, int tile, Wf2dWs* w) {
+  if (!wf2d_counts_ok(V, S, nmax, tile)) return false;
+  w->tiles = (nmax + tile - 1) / tile;
+  const size_t s = (size_t)S;
+  WsCarver c(ws);
+  w->rec = c.take<double>(8 * s);
+  w->view = c.take<int>(s);
+  for (int** p : {&w->parent, &w->last, &w->vidx}) *p = c.take<int>(2 * s);
+  w->keep = c.take<int>(s);
+  w->eidx = c.take<int>(s);
+  w->total = c.end();
+  return true;
+}
+
 }  // namespace neat

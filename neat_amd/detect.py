@@ -8,7 +8,14 @@ then says `dataset.line_detector = lsd`.  One summary line: vie
 
     lines, width, nfa, n, k, offsets = detect.lines(images, scale=1.0)      # images: uint8 device tensor [V,H,W,3] or [V,H,W]
     detect.labels(codes)                                                     # uint8 [V,h,w], 255 = unused -> int32 labels, -1 = unused
-    detect.to_wireframe(lines, nfa, H, W)                                    # -> WireframeGraph
+    detect.to_wireframe(lines, nfa, H, W)                                    # -> WireframeGraph, two vertices of its own a segment
+
+With `--junctions [--gap 4] [--gap-frac 0.4] [--angle 10] [--no-t]` the segments' ends are joined into shared junctions (DESIGN 3o,
+csrc/kernels_wireframe2d.hpp, restated by tests/junctions2d_f64.py); `--from NAME` then reads the segments of `<scan>/<NAME>/*.json`
+instead of detecting.  The summary line adds the vertices and edges built.
+
+    res = detect.junctions(lines, weight, offsets, gap=4.0, frac=0.4, angle=10.0, t_junctions=True)      # dict of device tensors
+    wfs = detect.wireframes(lines, nfa, offsets, H, W)                                                   # one WireframeGraph per view
 
 The detector is an a-contrario one of the LSD family (Grompone von Gioi et al.) over the line-support regions of Burns, Hanson and
 Riseman: connected components of the quantised gradient orientation in two overlapping partitions, validated by LSD's rectangle and
@@ -127,11 +134,118 @@ def to_wireframe(lines, nfa, H, W):
     """The lines [N,4] of one view and their -log10 NFA -> a WireframeGraph of 2 N vertices and N edges.  The edge weight (and the score of
     its two vertices) is 1 - 10^(-nfa), so the datasets' `> 0.05` threshold keeps what the NFA test kept (all but NFA values above 0.95)."""
     lines = torch.as_tensor(lines).detach().cpu().to(torch.float64).reshape(-1, 4)
-    nfa = torch.as_tensor(nfa).detach().cpu().to(torch.float64).reshape(-1)
     N = lines.shape[0]
-    weight = (1.0 - torch.pow(10.0, -nfa)).float()
+    weight = nfa_weight(nfa)
     edges = torch.arange(2 * N, dtype=torch.long).reshape(N, 2)
     return WireframeGraph(lines.reshape(2 * N, 2).float(), weight.repeat_interleave(2), edges, weight, frame_width=int(W), frame_height=int(H))
+
+
+def nfa_weight(nfa):
+    """-log10 NFA -> the edge weight 1 - 10^(-nfa) as the files hold it: float32, formed in float64 on the host."""
+    nfa = torch.as_tensor(nfa).detach().cpu().to(torch.float64).reshape(-1)
+    return (1.0 - torch.pow(10.0, -nfa)).float()
+
+
+# ---- shared junctions (DESIGN 3o) ------------------------------------------------------------------------------------------------------------
+JUNCTION_DEFAULTS = {"gap": 4.0, "frac": 0.4, "angle": 10.0, "t_junctions": True}
+JUNCTION_KEYS = ("vertices", "degree", "kind", "score", "spread", "t_edge", "voff", "ends", "edges", "eweight", "esrc", "eoff")
+
+
+def check_junction_options(gap, frac, angle):
+    if not (gap > 0.0 and math.isfinite(gap) and 0.0 < frac < 0.5 and 0.0 < angle <= 90.0):
+        raise ValueError(f"detect.junctions: gap {gap} must be positive, frac {frac} lie in (0, 0.5) and angle {angle} in (0, 90]")
+
+
+def junctions(lines, weight, offsets, gap=JUNCTION_DEFAULTS["gap"], frac=JUNCTION_DEFAULTS["frac"], angle=JUNCTION_DEFAULTS["angle"],
+              t_junctions=JUNCTION_DEFAULTS["t_junctions"]):
+    """The segments of V views -> their wireframes with shared junctions, on the device (the rule: DESIGN 3o, tests/junctions2d_f64.py).
+
+    lines [S,4] = x1 y1 x2 y2 and weight [S] on the device, in (view, index) order; offsets [V+1]: the views' first segments, as
+    detect.lines returns them (a device tensor: the launches are then sized for S segments a view) or on the host (a sequence or a CPU
+    tensor: sized for the largest view).  gap in pixels, frac of a segment's length, angle in degrees.
+
+    -> dict of device tensors, the views one after the other and every index a view's own.  Per vertex: vertices float64 [N,2], degree
+    int32 [N], kind int32 [N] (0 a free end, 1 a junction, 2 a T), score float64 [N], spread float64 [N], t_edge int32 [N]; voff int32
+    [V+1].  ends int32 [S,2]: the vertex of each end.  Per edge: edges int32 [E,2], eweight float64 [E], esrc int32 [E] (its segment);
+    eoff int32 [V+1].  One synchronisation, at the end, to slice the outputs."""
+    if not (torch.is_tensor(lines) and lines.is_cuda and torch.is_tensor(weight) and weight.is_cuda):
+        raise RuntimeError("neat_amd.detect needs CUDA tensors (there is no CPU path)")
+    if lines.dim() != 2 or lines.shape[1] != 4 or weight.numel() != lines.shape[0]:
+        raise RuntimeError(f"detect.junctions: lines [S,4] and weight [S], got {tuple(lines.shape)} and {tuple(weight.shape)}")
+    gap, frac, angle = float(gap), float(frac), float(angle)
+    check_junction_options(gap, frac, angle)
+    dev = lines.device
+    S = int(lines.shape[0])
+    with torch.cuda.device(dev):
+        seg = lines.detach().to(torch.float64).contiguous()
+        w = weight.detach().to(torch.float64).reshape(-1).contiguous()
+        if torch.is_tensor(offsets) and offsets.is_cuda:
+            if offsets.dim() != 1 or offsets.numel() < 1:
+                raise RuntimeError(f"detect.junctions: offsets [V+1], got {tuple(offsets.shape)}")
+            segoff, nmax = offsets.to(device=dev, dtype=torch.int32).contiguous(), S
+        else:
+            host = np.asarray(offsets.numpy() if torch.is_tensor(offsets) else offsets, dtype=np.int64).reshape(-1)
+            if host.size < 1 or host[0] != 0 or host[-1] != S or (np.diff(host) < 0).any():
+                raise ValueError(f"detect.junctions: offsets must ascend from 0 to the {S} segments")
+            segoff, nmax = torch.from_numpy(host.astype(np.int32)).to(dev), int(np.diff(host).max()) if host.size > 1 else 0
+        V = int(segoff.numel()) - 1
+        lib = _lib.lib()
+        nbytes = lib.neat_wf2d_scratch_bytes(V, S, nmax) if S < 2 ** 31 else 0
+        if nbytes == 0 and S > 0:
+            raise RuntimeError(f"detect.junctions: {V} views of {S} segments are beyond what one call indexes; pass fewer views")
+        f64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float64)
+        i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        out = {"vertices": f64(2 * S, 2), "degree": i32(2 * S), "kind": i32(2 * S), "score": f64(2 * S), "spread": f64(2 * S), "t_edge": i32(2 * S),
+               "voff": i32(V + 1), "ends": i32(S, 2), "edges": i32(S, 2), "eweight": f64(S), "esrc": i32(S), "eoff": i32(V + 1)}
+        _lib.check(lib.neat_wf2d_build(_lib.ptr(seg), _lib.ptr(segoff), _lib.ptr(w), V, S, nmax, gap, frac, math.sin(angle * math.pi / 180.0),
+                                       1 if t_junctions else 0, _lib.ptr(ws), *(_lib.ptr(out[k]) for k in JUNCTION_KEYS), _lib.stream()),
+                   "neat_wf2d_build")
+        N, E = torch.stack([out["voff"][-1], out["eoff"][-1]]).tolist()
+        for k in ("vertices", "degree", "kind", "score", "spread", "t_edge"):
+            out[k] = out[k][:N].clone()
+        for k in ("edges", "eweight", "esrc"):
+            out[k] = out[k][:E].clone()
+    return out
+
+
+def wireframes(lines, nfa, offsets, H, W, **kw):
+    """The detector's output (lines [S,4], nfa [S], offsets [V+1], on the device) -> one WireframeGraph per view with shared junctions.
+    The builder sees the segments and weights as a file of to_wireframe holds them (float32), so building from such a file gives the
+    same graphs.  Each graph carries `degree` and `kind` of its vertices as extra attributes."""
+    if not (torch.is_tensor(lines) and lines.is_cuda):
+        raise RuntimeError("neat_amd.detect needs CUDA tensors (there is no CPU path)")
+    weight = nfa_weight(nfa).to(lines.device)
+    return graphs(junctions(lines.float(), weight, offsets, **kw), H, W)
+
+
+def graphs(res, H, W):
+    """detect.junctions' result -> one WireframeGraph per view (float32 on the host), with `degree` and `kind` [N] beside the vertices.
+    H, W: one size for all views, or a sequence of them."""
+    host = {k: v.cpu() for k, v in res.items()}
+    voff, eoff = host["voff"].tolist(), host["eoff"].tolist()
+    out = []
+    for v in range(len(voff) - 1):
+        a, b, c, d = voff[v], voff[v + 1], eoff[v], eoff[v + 1]
+        h, w = (H[v], W[v]) if isinstance(H, (list, tuple)) else (H, W)
+        wf = WireframeGraph(host["vertices"][a:b].float(), host["score"][a:b].float(), host["edges"][c:d].long(), host["eweight"][c:d].float(),
+                            frame_width=int(w), frame_height=int(h))
+        wf.degree, wf.kind = host["degree"][a:b].tolist(), host["kind"][a:b].tolist()
+        out.append(wf)
+    return out
+
+
+def write_graphs(folder, stems, wfs):
+    """The graphs of detect.wireframes / detect.graphs as <folder>/<stem>.json, `vertices-degree` and `vertices-kind` beside the usual keys."""
+    for stem, wf in zip(stems, wfs):
+        run_io.write_wireframe_json(os.path.join(folder, stem + ".json"), wf, {"vertices-degree": wf.degree, "vertices-kind": wf.kind})
+
+
+def read_soup(path):
+    """A <scene>/<line_detector>/<image>.json of any detector -> (segments float32 [n,4] = its edges' end points, weights float32 [n], H, W)."""
+    wf = WireframeGraph.load_json(path)
+    seg = torch.cat([wf.vertices[wf.edges[:, 0]], wf.vertices[wf.edges[:, 1]]], dim=1).reshape(-1, 4)
+    return seg, wf.weights.reshape(-1), int(wf.frame_height), int(wf.frame_width)
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------------------------
@@ -143,6 +257,13 @@ def build_parser():
     ap.add_argument("--views", type=str, default=None, help="a:b, a slice of the sorted views")
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--batch", type=int, default=16, help="views of equal size per call")
+    ap.add_argument("--junctions", action="store_true", help="join the segments' ends into shared junctions (DESIGN 3o) instead of two vertices a segment")
+    ap.add_argument("--gap", type=float, default=JUNCTION_DEFAULTS["gap"], help="--junctions: how far from its end a segment may meet another, pixels")
+    ap.add_argument("--gap-frac", dest="gap_frac", type=float, default=JUNCTION_DEFAULTS["frac"], help="--junctions: and as a share of its length, in (0, 0.5)")
+    ap.add_argument("--angle", type=float, default=JUNCTION_DEFAULTS["angle"], help="--junctions: the least angle between two segments that meet, degrees")
+    ap.add_argument("--no-t", dest="no_t", action="store_true", help="--junctions: leave an end that stops at another segment's inside where it is")
+    ap.add_argument("--from", dest="source", type=str, default=None, metavar="NAME",
+                    help="--junctions: read the segments of <scan>/<NAME>/*.json (any detector's) instead of detecting")
     return ap
 
 
@@ -164,14 +285,46 @@ def main(argv=None):
     if not 0.0 < opt.scale <= 1.0 or opt.batch < 1:
         print(f"--scale {opt.scale} must lie in (0, 1] and --batch {opt.batch} be positive", file=sys.stderr, flush=True)
         return 2
-    paths = run_io.scene_images(opt.scan)
+    kw = {"gap": opt.gap, "frac": opt.gap_frac, "angle": opt.angle, "t_junctions": not opt.no_t}
     try:
+        if opt.source is not None and not opt.junctions:
+            raise ValueError("--from reads a detector's files to join their segments: it needs --junctions")
+        if opt.source is not None and os.path.normpath(opt.source) == os.path.normpath(opt.name):
+            raise ValueError(f"--from {opt.source} and --name {opt.name} are one folder")
+        check_junction_options(opt.gap, opt.gap_frac, opt.angle)
+        if opt.source is not None:
+            folder = os.path.join(opt.scan, opt.source)
+            paths = sorted(os.path.join(folder, n) for n in os.listdir(folder) if n.endswith(".json"))
+        else:
+            paths = run_io.scene_images(opt.scan)
         paths = [paths[i] for i in parse_views(opt.views, len(paths))]
-    except ValueError as err:
+    except (ValueError, FileNotFoundError) as err:
         print(err, file=sys.stderr, flush=True)
         return 2
     t0 = time.perf_counter()
-    total = 0
+    total = built_v = built_e = 0
+    stem_of = lambda path: os.path.splitext(os.path.basename(path))[0]
+
+    def summary():
+        built = f"{built_v} vertices, {built_e} edges, " if opt.junctions else ""
+        print(f"{len(paths)} views, {total} segments, {built}{time.perf_counter() - t0:.3f} s -> {os.path.join(opt.scan, opt.name)}", flush=True)
+        return 0
+
+    def write_built(stems, wfs):
+        nonlocal built_v, built_e
+        write_graphs(os.path.join(opt.scan, opt.name), stems, wfs)
+        built_v += sum(wf.vertices.shape[0] for wf in wfs)
+        built_e += sum(wf.edges.shape[0] for wf in wfs)
+
+    if opt.source is not None:                   # the segments of files: --batch views a call, of any sizes
+        for b0 in range(0, len(paths), opt.batch):
+            soups = [read_soup(p) for p in paths[b0:b0 + opt.batch]]
+            off = np.concatenate([[0], np.cumsum([s[0].shape[0] for s in soups])])
+            res = junctions(torch.cat([s[0] for s in soups]).to(device), torch.cat([s[1] for s in soups]).to(device), off, **kw)
+            write_built([stem_of(p) for p in paths[b0:b0 + opt.batch]], graphs(res, [s[2] for s in soups], [s[3] for s in soups]))
+            total += int(off[-1])
+        torch.cuda.synchronize(device)
+        return summary()
     group = []                                   # consecutive views of equal size go into one call
 
     def flush():
@@ -180,6 +333,11 @@ def main(argv=None):
             return
         batch = torch.from_numpy(np.stack([img for _, img in group])).to(device)
         seg, _, nfa, _, _, off = lines(batch, scale=opt.scale)
+        if opt.junctions:
+            write_built([stem_of(path) for path, _ in group], wireframes(seg, nfa, off.cpu().tolist(), batch.shape[1], batch.shape[2], **kw))
+            total += int(seg.shape[0])
+            group.clear()
+            return
         seg, nfa, off = seg.cpu(), nfa.cpu(), off.cpu().tolist()
         for j, (path, img) in enumerate(group):
             a, b = off[j], off[j + 1]
@@ -196,8 +354,7 @@ def main(argv=None):
         group.append((path, img))
     flush()
     torch.cuda.synchronize(device)
-    print(f"{len(paths)} views, {total} segments, {time.perf_counter() - t0:.3f} s -> {os.path.join(opt.scan, opt.name)}", flush=True)
-    return 0
+    return summary()
 
 
 if __name__ == "__main__":

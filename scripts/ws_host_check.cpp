@@ -19,6 +19,7 @@
 #include "kernels_show.hpp"
 #include "kernels_trace.hpp"
 #include "kernels_triangulate.hpp"
+#include "kernels_wireframe2d.hpp"
 #include "ws_layout.hpp"
 
 using namespace neat;
@@ -305,6 +306,25 @@ int main() {
     CHECK(TRI_WG * TRI_SEGB * 8 <= 64 * 1024);                             // the pair kernel's tile of partners in LDS
   }
 
+  // ---- 2-D wireframes: views, segments in all, the largest view (or a bound on it); segment counts around the pair kernels' tile
+  {
+    const int shapes[][3] = {{0, 0, 0}, {1, 1, 1}, {3, 3, 2}, {1, 255, 255}, {1, 256, 256}, {2, 257, 257}, {5, 600, 600}, {64, 128000, 2000}, {64, 128000, 128000}};
+    for (const auto& sh : shapes) {
+      CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+        Wf2dWs w;
+        if (!wf2d_layout(b, sh[0], sh[1], sh[2], WF_WG, &w)) return false;
+        const size_t s = (size_t)sh[1];
+        if ((long long)w.tiles * WF_WG < sh[2] || (w.tiles > 0 && (long long)(w.tiles - 1) * WF_WG >= sh[2])) return false;
+        r = {{w.rec, s * WF_REC * 8, 256}, {w.view, s * 4, 256}, {w.parent, s * 8, 256}, {w.last, s * 8, 256}, {w.vidx, s * 8, 256},
+             {w.keep, s * 4, 256}, {w.eidx, s * 4, 256}};
+        t = w.total;
+        return true;
+      }));
+    }
+    CHECK(wf2d_counts_ok(64, 128000, 2000, WF_WG) && wf2d_counts_ok(0, 0, 0, WF_WG) && wf2d_counts_ok(WF_MAX_VIEWS, 0x7fffffff / 10, 8000, WF_WG));
+    CHECK(WF_WG * WF_REC * 8 <= 64 * 1024);                                // the pair kernels' tile of partners in LDS
+  }
+
   // ---- scene generation: views and edges; the edge list, then the runs per (view, edge) and their offsets
   {
     const int shapes[][2] = {{0, 0}, {0, 18}, {3, 0}, {1, 1}, {3, 12}, {100, 18}, {7, 257}, {SG_MAX_VIEWS, 4096}};
@@ -444,6 +464,11 @@ int main() {
         !tri_layout(nullptr, 2, 4, 2, 4, TRI_WG, &wtri) && !tri_layout(nullptr, 2, 4, 1, 5, TRI_WG, &wtri) &&
         !tri_layout(nullptr, TRI_MAX_VIEWS + 1, 4, 1, 4, TRI_WG, &wtri) && !tri_layout(nullptr, 2, 0x7fffffff / 10 + 1, 1, 10, TRI_WG, &wtri) &&
         !tri_layout(nullptr, 20, 1 << 27, 17, 10, TRI_WG, &wtri) && !tri_layout(nullptr, TRI_MAX_VIEWS, 1 << 24, 64, 1 << 24, TRI_WG, &wtri));
+  Wf2dWs wwf;
+  CHECK(!wf2d_layout(nullptr, -1, 0, 0, WF_WG, &wwf) && !wf2d_layout(nullptr, 1, -1, 0, WF_WG, &wwf) && !wf2d_layout(nullptr, 1, 4, -1, WF_WG, &wwf) &&
+        !wf2d_layout(nullptr, 1, 4, 5, WF_WG, &wwf) && !wf2d_layout(nullptr, 0, 4, 4, WF_WG, &wwf) && !wf2d_layout(nullptr, 1, 4, 0, WF_WG, &wwf) &&
+        !wf2d_layout(nullptr, WF_MAX_VIEWS + 1, 4, 4, WF_WG, &wwf) && !wf2d_layout(nullptr, 1, 0x7fffffff / 10 + 1, 1, WF_WG, &wwf) &&
+        !wf2d_layout(nullptr, WF_MAX_VIEWS, 0x7fffffff / 10, 0x7fffffff / 10, WF_WG, &wwf));
   ScenegenWs wsg;
   CHECK(!scenegen_layout(nullptr, -1, 1, &wsg) && !scenegen_layout(nullptr, 1, -1, &wsg) && !scenegen_layout(nullptr, SG_MAX_VIEWS + 1, 1, &wsg) &&
         !scenegen_layout(nullptr, 1, 0x7fffffff / 8 + 1, &wsg) && !scenegen_layout(nullptr, 1000, 0x7fffffff / 4000 + 1, &wsg));
