@@ -857,6 +857,33 @@ int neat_wf2d_build(const double* segments, const int* segoff, const double* wei
                     int t_junctions, void* ws, double* vertices, int* degree, int* kind, double* score, double* spread, int* t_edge, int* voff,
                     int* ends, int* edges, double* eweight, int* esrc, int* eoff, void* stream);
 
+/* ---- added to ABI v15 (new symbols only, so the version number stays): 3-D wireframes with shared junctions from the triangulated
+ * lines and the views' 2-D graphs (neat_amd/triangulate.py wireframe): a 3-D line end inherits the 2-D vertices of its member segments'
+ * ends; ends of different lines that share a 2-D vertex in min_votes views and whose lines nearly cross there become one junction at
+ * the least-squares point of their lines; collapsed and duplicate lines are dropped.  The rule: DESIGN 3p and
+ * neat_amd/csrc/kernels_wireframe3d.hpp, restated in float64 by tests/wireframe3d_f64.py, which the device equals byte for byte.
+ * Float64 without contraction, no transcendental function; sorted keys that are counted, scanned and filled, a union-find whose roots
+ * are the smallest member: two runs give the same bytes.  Asynchronous on the stream, no allocation, no read-back.  Bad arguments
+ * return -1 before any launch; -2: a sort wants more temporary storage than the workspace holds (before any launch too).
+ *
+ * neat_wf3d_scratch_bytes : the workspace (256-byte aligned, caller-owned) with room for pairs_max votes; 0 when refused: a negative
+ *   count, V > 65535, 2 N >= 2^24, 6 S, NV or pairs_max beyond 2^31 - 1, segments without a view or a 2-D vertex.
+ * neat_wf3d_build : lines3d float64 [N,2,3], support float64 [N] (finite), members int32 [S] (the line of each 2-D segment, -1 for
+ *   none), estimate float64 [S,2,3] (the 3-D point of each segment end), as neat_tri_lines gives them; endv int32 [S,2] the 2-D vertex
+ *   of each segment end, numbered over all views in [0, NV), a vertex in one view only; view int32 [S].  0 < end_frac < 0.5: how far
+ *   from a line's end, as a share of its length, a segment end may lie and still be that end; 0 < reach <= 1: how far from its end,
+ *   likewise, a line may cross another, and how far apart the two may pass; 0 < sin_min <= 1 the sine of the least angle between two
+ *   lines that may cross; min_votes >= 1.  An entry of members, endv or view outside its range carries nothing.
+ *   Per vertex, capacity 2 N, in ascending order of the vertex's lowest end id (end e of line L is 2 L + e): vertices float64 [.,3],
+ *   degree int32 (ends joined), kind int32 (0 a free end, at the line's own end point; 1 a junction), votes int32 (the most views that
+ *   voted for one of its links), spread float64 (the largest distance from the vertex to an end it replaces); n_vertices int32 [1].
+ *   Per edge, capacity N, in line order: edges int32 [.,2] (the vertices of the line's ends 0 and 1), esrc int32 (the line);
+ *   n_edges int32 [1].  When the views cast more votes than pairs_max, n_vertices is -1 and n_edges the room to ask for. */
+size_t neat_wf3d_scratch_bytes(int V, int S, int N, int NV, long long pairs_max);
+int neat_wf3d_build(const double* lines3d, const double* support, int N, const int* members, const double* estimate, const int* endv, const int* view,
+                    int V, int S, int NV, long long pairs_max, double end_frac, double reach, double sin_min, int min_votes, void* ws, double* vertices,
+                    int* degree, int* kind, int* votes, double* spread, int* n_vertices, int* edges, int* esrc, int* n_edges, void* stream);
+
 /* ---- a9 alone: volume_rendering :540-554 given sdf [R,S] -> weights [R,S] (used by tests) -------- */
 int neat_volume_weights(const float* z, const float* sdf, int R, int S, const float* beta, float* weights, void* stream);
 

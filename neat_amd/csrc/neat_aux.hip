@@ -21,6 +21,7 @@
 #include "kernels_triangulate.hpp"
 #include "kernels_crease.hpp"
 #include "kernels_wireframe2d.hpp"
+#include "kernels_wireframe3d.hpp"
 #include "ws_layout.hpp"
 #include "../../include/neat_hip.h"
 #include <algorithm>
@@ -1620,6 +1621,73 @@ int neat_wf2d_build(const double* segments, const int* segoff, const double* wei
   hipLaunchKernelGGL(wf_edge_scan_kernel, dim3(1), dim3(1024), 0, st, S, V, segoff, (const int*)w.keep, w.eidx, eoff);
   hipLaunchKernelGGL(wf_edge_fill_kernel, per_seg, dim3(WF_WG), 0, st, S, segoff, (const int*)w.view, (const int*)w.keep, (const int*)w.eidx,
                      (const int*)ends, weight, edges, eweight, esrc);
+  return (int)hipGetLastError();
+}
+
+// ---- added to ABI v15: 3-D wireframes with shared junctions from the lines and the views' 2-D graphs (kernels_wireframe3d.hpp) ---------------
+size_t neat_wf3d_scratch_bytes(int V, int S, int N, int NV, long long pairs_max) {
+  Wf3dWs w;
+  return wf3d_layout(nullptr, V, S, N, NV, pairs_max, &w) ? w.total_bytes : 0;
+}
+
+int neat_wf3d_build(const double* lines3d, const double* support, int N, const int* members, const double* estimate, const int* endv, const int* view,
+                    int V, int S, int NV, long long pairs_max, double end_frac, double reach, double sin_min, int min_votes, void* ws, double* vertices,
+                    int* degree, int* kind, int* votes, double* spread, int* n_vertices, int* edges, int* esrc, int* n_edges, void* stream) {
+  Wf3dWs w;
+  if (!(end_frac > 0.0 && end_frac < 0.5) || !(reach > 0.0 && reach <= 1.0) || !(sin_min > 0.0 && sin_min <= 1.0) || min_votes < 1 || !n_vertices ||
+      !n_edges || !wf3d_layout(ws, V, S, N, NV, pairs_max, &w))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (N == 0) {
+    NEAT_CHECK(hipMemsetAsync(n_vertices, 0, sizeof(int), st));
+    return (int)hipMemsetAsync(n_edges, 0, sizeof(int), st);
+  }
+  if (!lines3d || !support || !ws || ((uintptr_t)ws & 255) || !vertices || !degree || !kind || !votes || !spread || !edges || !esrc ||
+      (S > 0 && (!members || !estimate || !endv || !view)))
+    return -1;
+  const size_t n_rec = 2 * (size_t)S, n_pair = (size_t)pairs_max;
+  size_t need[3] = {0, 0, 0};                                            // what the three sorts want, asked before anything is launched
+  if (n_rec > 0) NEAT_CHECK(rocprim::radix_sort_keys(nullptr, need[0], w.rkey, w.rskey, n_rec, 0u, 64u, st));
+  if (n_rec > 0 && n_pair > 0) NEAT_CHECK(rocprim::radix_sort_keys(nullptr, need[1], w.pkey, w.pskey, n_pair, 0u, 64u, st));
+  NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, need[2], w.ekey, w.eskey, w.eline, w.esline, (size_t)N, 0u, 64u, st));
+  if (std::max(need[0], std::max(need[1], need[2])) > w.sort_bytes) return -2;
+  const int n2 = 2 * N;
+  NEAT_CHECK(hipMemsetAsync(w.total, 0, sizeof(long long), st));
+  hipLaunchKernelGGL(wf3_init_kernel, grid1(n2, WF3_WG), dim3(WF3_WG), 0, st, n2, w.parent, w.last, w.lvotes);
+  if (n_rec > 0) {
+    NEAT_CHECK(hipMemsetAsync(w.vview, 0, (size_t)NV * sizeof(int), st));
+    hipLaunchKernelGGL(wf3_ends_kernel, grid1(S, WF3_WG), dim3(WF3_WG), 0, st, lines3d, N, members, estimate, endv, view, V, S, NV, end_frac, w.rkey,
+                       w.vview);
+    NEAT_CHECK(hipGetLastError());
+    size_t tb = need[0];
+    NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.rkey, w.rskey, n_rec, 0u, 64u, st));
+    hipLaunchKernelGGL(wf3_pair_count_kernel, grid1(2 * S, WF3_WG), dim3(WF3_WG), 0, st, (const wf3_key*)w.rskey, 2 * S, w.rcnt);
+    hipLaunchKernelGGL(wf3_pair_scan_kernel, dim3(1), dim3(1024), 0, st, 2 * S, (const int*)w.rcnt, w.roff, w.total);
+    if (n_pair > 0) {
+      NEAT_CHECK(hipMemsetAsync(w.pkey, 0xff, n_pair * sizeof(wf3_key), st));
+      hipLaunchKernelGGL(wf3_pair_fill_kernel, grid1(2 * S, WF3_WG), dim3(WF3_WG), 0, st, (const wf3_key*)w.rskey, 2 * S, (const long long*)w.roff,
+                         (const int*)w.vview, NV, pairs_max, w.pkey);
+      NEAT_CHECK(hipGetLastError());
+      tb = need[1];
+      NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.pkey, w.pskey, n_pair, 0u, 64u, st));
+      hipLaunchKernelGGL(wf3_link_kernel, dim3((unsigned)((pairs_max + WF3_WG - 1) / WF3_WG)), dim3(WF3_WG), 0, st, (const wf3_key*)w.pskey, pairs_max, lines3d, N, min_votes, reach,
+                         sin_min, w.parent, w.lvotes);
+    }
+  }
+  hipLaunchKernelGGL(wf_flatten_kernel, grid1(n2, WF_WG), dim3(WF_WG), 0, st, n2, w.parent, w.last);
+  NEAT_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(wf3_vertex_scan_kernel, dim3(1), dim3(1024), 0, st, n2, (const int*)w.parent, w.vidx, n_vertices);
+  hipLaunchKernelGGL(wf3_vertex_kernel, grid1(n2, WF3_WAVES), dim3(WF3_WG), 0, st, n2, (const int*)w.parent, (const int*)w.last, (const int*)w.vidx,
+                     (const int*)w.lvotes, lines3d, vertices, degree, kind, votes, spread);
+  hipLaunchKernelGGL(wf3_edge_key_kernel, grid1(N, WF3_WG), dim3(WF3_WG), 0, st, N, (const int*)w.parent, (const int*)w.vidx, w.ekey, w.eline, w.keep);
+  NEAT_CHECK(hipGetLastError());
+  size_t tb = need[2];
+  NEAT_CHECK(rocprim::radix_sort_pairs(w.sort, tb, w.ekey, w.eskey, w.eline, w.esline, (size_t)N, 0u, 64u, st));
+  hipLaunchKernelGGL(wf3_edge_pick_kernel, grid1(N, WF3_WG), dim3(WF3_WG), 0, st, N, (const wf3_key*)w.eskey, (const int*)w.esline, support, w.keep);
+  hipLaunchKernelGGL(wf3_edge_scan_kernel, dim3(1), dim3(1024), 0, st, N, (const int*)w.keep, w.eidx, (const long long*)w.total, pairs_max, n_vertices,
+                     n_edges);
+  hipLaunchKernelGGL(wf3_edge_fill_kernel, grid1(N, WF3_WG), dim3(WF3_WG), 0, st, N, (const int*)w.keep, (const int*)w.eidx, (const int*)w.parent,
+                     (const int*)w.vidx, edges, esrc);
   return (int)hipGetLastError();
 }
 

@@ -488,4 +488,45 @@ inline bool wf2d_layout(void* ws, int V, int S, int nmax, int tile, Wf2dWs* w) {
   return true;
 }
 
+// ---- 3-D wireframes with shared junctions (kernels_wireframe3d.hpp) over V views, S 2-D segments, N 3-D lines, NV 2-D vertices and room
+// for pairs_max pair keys.  An end id is below 2 N < 2^24 and a view below 2^16, so a pair key (24 + 24 + 16 bits) fits 64 bits.
+// total: the pairs there are | rkey, rskey [2 S] the records and their sort | rcnt [2 S], roff [2 S] the pairs a record starts and
+// those before it | vview [NV] | pkey, pskey [pairs_max] | per end id: parent (then the label), last, vidx, lvotes [2 N] each | per line:
+// ekey, eskey, eline, esline (the edge keys and their sort), keep, eidx [N] | the radix sort's temporary storage, fixed as crease_layout
+// fixes it; a call asks rocprim and refuses if it wants more
+constexpr int WF3_MAX_ENDS = 1 << 24;
+inline bool wf3d_counts_ok(long long V, long long S, long long N, long long NV, long long pairs_max) {
+  if (V < 0 || S < 0 || N < 0 || NV < 0 || pairs_max < 0 || V > WF_MAX_VIEWS || 2 * N >= WF3_MAX_ENDS) return false;
+  return 6 * S <= 0x7fffffffLL && NV <= 0x7fffffffLL && pairs_max <= 0x7fffffffLL && (S == 0 || (V > 0 && NV > 0));
+}
+struct Wf3dWs {
+  size_t n_sort;            // the largest list a sort sees
+  long long* total; unsigned long long *rkey, *rskey; int* rcnt; long long* roff; int* vview;
+  unsigned long long *pkey, *pskey; int *parent, *last, *vidx, *lvotes;
+  unsigned long long *ekey, *eskey; int *eline, *esline, *keep, *eidx;
+  void* sort; size_t sort_bytes, total_bytes;
+};
+inline bool wf3d_layout(void* ws, int V, int S, int N, int NV, long long pairs_max, Wf3dWs* w) {
+  if (!wf3d_counts_ok(V, S, N, NV, pairs_max)) return false;
+  const size_t s2 = 2 * (size_t)S, n = (size_t)N, p = (size_t)pairs_max;
+  w->n_sort = s2 > p ? (s2 > n ? s2 : n) : (p > n ? p : n);
+  w->sort_bytes = (size_t)32 * w->n_sort + ((size_t)4 << 20);
+  WsCarver c(ws);
+  w->total = c.take<long long>(32);
+  w->rkey = c.take<unsigned long long>(s2);
+  w->rskey = c.take<unsigned long long>(s2);
+  w->rcnt = c.take<int>(s2);
+  w->roff = c.take<long long>(s2);
+  w->vview = c.take<int>((size_t)NV);
+  w->pkey = c.take<unsigned long long>(p);
+  w->pskey = c.take<unsigned long long>(p);
+  for (int** q : {&w->parent, &w->last, &w->vidx, &w->lvotes}) *q = c.take<int>(2 * n);
+  w->ekey = c.take<unsigned long long>(n);
+  w->eskey = c.take<unsigned long long>(n);
+  for (int** q : {&w->eline, &w->esline, &w->keep, &w->eidx}) *q = c.take<int>(n);
+  w->sort = c.take<char>(w->sort_bytes);
+  w->total_bytes = c.end();
+  return true;
+}
+
 }  // namespace neat

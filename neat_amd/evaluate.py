@@ -4,7 +4,7 @@ eval-wfr-dtu.py and eval-abc.py; those need open3d, sklearn, GPUtil and trimesh,
     python -m neat_amd.evaluate dtu-mesh      --data surface_2000.ply --scan 24 --dataset_dir <DTU> [--mode mesh|pcd] [--vis_out_dir DIR]
     python -m neat_amd.evaluate dtu-lines     --data <name>-wfi_checked.npz --scan 24 --cam cameras.npz --dataset_dir <DTU> [--score S]
     python -m neat_amd.evaluate dtu-junctions --data <name>-neat.pth --scan 24 --cam cameras.npz --dataset_dir <DTU>
-    python -m neat_amd.evaluate abc           --data <name>-neat.pth --scan <scan dir with lines.json and offset_scale.txt>
+    python -m neat_amd.evaluate abc           --data <name>-neat.pth | <name>-wf3d.npz --scan <scan dir with lines.json and offset_scale.txt>
 
 Flags and defaults are the reference's; every sub-command also takes --seed (the permutation of the shuffle that precedes the thinning;
 the reference draws an unseeded one), --gpu (a device index), --obs (an .npz with ObsMask, BB, Res, P instead of the two .mat files),
@@ -509,7 +509,12 @@ def run_dtu_junctions(opt, dev):
 
 
 def run_abc(opt, dev):
-    data = torch.load(opt.data, map_location="cpu")
+    if opt.data.lower().endswith(".npz"):           # triangulate --wireframe: the junctions and the edges' segments of a checkpoint-free wireframe
+        with np.load(opt.data) as z:
+            data = {"junctions3d_initial": np.asarray(z["junctions3d"], dtype=np.float64).reshape(-1, 3),
+                    "lines3d_wfi_checked": np.asarray(z["lines3d"], dtype=np.float64).reshape(-1, 2, 3)}
+    else:
+        data = torch.load(opt.data, map_location="cpu")
     junctions, edges = run_io.read_lines_json(os.path.join(opt.scan, "lines.json"))
     offset_scale = run_io.read_offset_scale(os.path.join(opt.scan, "offset_scale.txt"))
     t0 = time.perf_counter()

@@ -111,6 +111,20 @@ def dataset_views(dataset):
     return segments, Ks, poses
 
 
+def dataset_graphs(dataset):
+    """Every view of a dataset as a graph -> (vertices [n,2], edges [e,2] into them, intrinsics [3,3], camera-to-world poses [4,4]): four
+    lists.  The edges are those scoring above 0.05, in order, so vertices[edges] are the rows of dataset_views' segments."""
+    vertices, edges, Ks, poses = [], [], [], []
+    for i in range(len(dataset)):
+        _, sample, _ = dataset[i]
+        wf = sample["wireframe"]
+        vertices.append(wf.vertices)
+        edges.append(wf.edges[wf.weights > 0.05])
+        Ks.append(sample["intrinsics"][:3, :3])
+        poses.append(sample["pose"])
+    return vertices, edges, Ks, poses
+
+
 def scene_images(instance_dir):
     """The views of a scene directory as the dataset classes list them: `images/` (BlenderDataset) or `image/` (SceneDataset), the
     sorted *.png / *.jpg / *.JPEG / *.JPG files without "mask" in their path."""

@@ -9,8 +9,17 @@ builds the conf's dataset and writes `<instance dir>/<line_detector>-l3d.npz` wi
 line), support [N] (the consensus score of its axis member; not `scores`, which evaluate --score reads as lower-is-better) and cameras
 [V,4,4] (the camera-to-world poses used).  One summary line: views, segments, hypotheses, estimates, lines, seconds.
 
+    ... --wireframe [--end-frac 0.2] [--reach 0.25] [--min-votes 2] [--junction-angle 10]
+
+reads the views as graphs (their 2-D junctions are shared: detect --junctions) and writes `<instance dir>/<line_detector>-wf3d.npz`
+instead: the 3-D wireframe whose line ends that share a 2-D vertex in enough views are one junction.  lines3d [E,2,3] holds
+the edges' segments, so every tool that reads the line soup reads this file, and its unique end points are the junctions; beside it
+junctions3d [J,3], edges [E,2], degree, kind, votes [J], src [E] (the triangulated line of an edge), views, support [E], cameras.
+
     triangulate.lines(segments, Ks, poses, **thresholds)         # -> dict of device tensors
     triangulate.hypotheses(segments, Ks, poses, neighbours=6, angle_min=5.0, overlap_min=0.25)      # the pair test alone
+    triangulate.wireframe(vertices, edges, Ks, poses, **thresholds, end_frac=0.2, reach=0.25, min_votes=2, angle=10.0)
+    triangulate.junctions3d(lines3d, support, members, estimate, endv, view, V, NV, ...)            # the junction rule alone, on lines' arrays
 
 segments: one device tensor [n_v,4] = x1 y1 x2 y2 in pixels per view; Ks [V,3,3]; poses [V,4,4] camera-to-world.  The rule is DESIGN 3k;
 csrc/kernels_triangulate.hpp implements it and tests/triangulate_f64.py restates it.  There is no CPU path: CPU tensors are refused.
@@ -30,6 +39,8 @@ from . import _lib, run_io
 DEFAULTS = {"neighbours": 6, "angle_min": 5.0, "overlap_min": 0.25, "sigma_px": 2.5, "min_score": 1.5, "min_views": 3}
 CAM = 48                     # doubles per view in the camera block
 MAX_HYPOTHESES = (2 ** 31 - 1) // 2
+WIREFRAME_DEFAULTS = {"end_frac": 0.2, "reach": 0.25, "min_votes": 2, "angle": 10.0}
+WIREFRAME_KEYS = ("junctions3d", "degree", "kind", "votes", "spread", "edges3d", "esrc", "lines3d_wf")
 
 
 def _np64(x):
@@ -189,6 +200,86 @@ def lines(segments, Ks, poses, neighbours=DEFAULTS["neighbours"], angle_min=DEFA
             "neighbours": mt.nb}
 
 
+def check_wireframe_options(end_frac, reach, min_votes, angle):
+    if not (0.0 < end_frac < 0.5 and 0.0 < reach <= 1.0 and 0.0 < angle <= 90.0 and int(min_votes) >= 1):
+        raise ValueError(f"triangulate: end_frac {end_frac} in (0, 0.5), reach {reach} in (0, 1], angle {angle} in (0, 90] degrees, "
+                         f"min_votes {min_votes} >= 1")
+
+
+def junctions3d(lines3d, support, members, estimate, endv, view, V, NV, end_frac=WIREFRAME_DEFAULTS["end_frac"],
+                reach=WIREFRAME_DEFAULTS["reach"], min_votes=WIREFRAME_DEFAULTS["min_votes"], angle=WIREFRAME_DEFAULTS["angle"], pairs_max=None):
+    """The rule of DESIGN 3p on the arrays of lines(): lines3d [N,2,3], support [N], members int32 [S], estimate [S,2,3], with endv int32
+    [S,2] the 2-D vertex of each segment end, numbered over all V views in [0, NV), and view int32 [S] -> dict of device tensors:
+    junctions3d float64 [J,3], degree, kind, votes int32 [J], spread float64 [J], edges3d int32 [E,2], esrc int32 [E].
+    pairs_max: the votes the workspace has room for (default: 8 per segment, what 2-D vertices of nine ends cast, and 4096 at least; a
+    scene that casts more is run again with the room it asks for).  One synchronisation: the read of the two counts."""
+    check_wireframe_options(end_frac, reach, min_votes, angle)
+    tensors = (lines3d, support, members, estimate, endv, view)
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise RuntimeError("neat_amd.triangulate needs CUDA tensors (there is no CPU path)")
+    dev = lines3d.device
+    lines3d, support, estimate = (t.to(torch.float64).contiguous() for t in (lines3d, support, estimate))
+    members, endv, view = (t.to(torch.int32).contiguous() for t in (members, endv, view))
+    N, S = int(support.shape[0]), int(members.shape[0])
+    if tuple(lines3d.shape) != (N, 2, 3) or tuple(estimate.shape) != (S, 2, 3) or tuple(endv.shape) != (S, 2) or tuple(view.shape) != (S,):
+        raise RuntimeError(f"triangulate: lines3d [N,2,3], support [N], members [S], estimate [S,2,3], endv [S,2], view [S]; got {[tuple(t.shape) for t in tensors]}")
+    lib = _lib.lib()
+    f64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float64)
+    i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        out = {"junctions3d": f64(2 * N, 3), "degree": i32(2 * N), "kind": i32(2 * N), "votes": i32(2 * N), "spread": f64(2 * N),
+               "edges3d": i32(N, 2), "esrc": i32(N)}
+        counts = i32(2)
+        room = max(8 * S, 4096) if pairs_max is None else int(pairs_max)
+        while True:
+            nbytes = lib.neat_wf3d_scratch_bytes(int(V), S, N, int(NV), room)
+            if nbytes == 0:
+                raise RuntimeError(f"triangulate: {V} views, {S} segments, {N} lines, {NV} vertices and {room} votes are beyond what one call indexes")
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            _lib.check(lib.neat_wf3d_build(_lib.ptr(lines3d), _lib.ptr(support), N, _lib.ptr(members), _lib.ptr(estimate), _lib.ptr(endv), _lib.ptr(view),
+                                           int(V), S, int(NV), room, float(end_frac), float(reach), math.sin(float(angle) * math.pi / 180.0),
+                                           int(min_votes), _lib.ptr(ws), _lib.ptr(out["junctions3d"]), _lib.ptr(out["degree"]), _lib.ptr(out["kind"]),
+                                           _lib.ptr(out["votes"]), _lib.ptr(out["spread"]), _lib.ptr(counts[0:1]), _lib.ptr(out["edges3d"]),
+                                           _lib.ptr(out["esrc"]), _lib.ptr(counts[1:2]), _lib.stream()), "neat_wf3d_build")
+            J, E = counts.tolist()                      # the one read-back: the two counts
+            if J >= 0:
+                break
+            if E <= room:
+                raise RuntimeError(f"triangulate: the views cast more votes than one call indexes ({E})")
+            room = E                                    # more votes than there was room for: once more, with the room they need
+    return {k: v[:E if k in ("edges3d", "esrc") else J].clone() for k, v in out.items()}
+
+
+def wireframe(vertices, edges, Ks, poses, end_frac=WIREFRAME_DEFAULTS["end_frac"], reach=WIREFRAME_DEFAULTS["reach"],
+              min_votes=WIREFRAME_DEFAULTS["min_votes"], angle=WIREFRAME_DEFAULTS["angle"], pairs_max=None, device=None, **thresholds):
+    """The views as graphs -> the dict of lines(vertices[edges], ...), plus the 3-D wireframe (the rule: DESIGN 3p,
+    tests/wireframe3d_f64.py): junctions3d float64 [J,3], degree, kind, votes int32 [J], spread float64 [J] per vertex; edges3d int32
+    [E,2], esrc int32 [E] (the line of an edge), lines3d_wf float64 [E,2,3] = junctions3d[edges3d].
+
+    vertices: one device tensor [n_v,2] per view; edges: one device integer tensor [e_v,2] per view, into the view's vertices.
+    pairs_max: see junctions3d.  One synchronisation beyond lines': the read of the two counts."""
+    check_wireframe_options(end_frac, reach, min_votes, angle)
+    vertices, edges = list(vertices), list(edges)
+    if len(vertices) != len(edges):
+        raise ValueError(f"triangulate: {len(vertices)} views of vertices for {len(edges)} views of edges")
+    for v, e in zip(vertices, edges):
+        if not (torch.is_tensor(v) and torch.is_tensor(e) and v.is_cuda and e.is_cuda):
+            raise RuntimeError("neat_amd.triangulate needs CUDA tensors (there is no CPU path)")
+        if v.dim() != 2 or v.shape[1] != 2 or e.dim() != 2 or e.shape[1] != 2 or e.dtype.is_floating_point:
+            raise RuntimeError(f"triangulate: vertices [n,2] and integer edges [e,2] per view, got {tuple(v.shape)} and {tuple(e.shape)}")
+    segments = [torch.cat([v[e[:, 0].long()], v[e[:, 1].long()]], dim=1) for v, e in zip(vertices, edges)]
+    res = lines(segments, Ks, poses, device=device, **thresholds)
+    dev = res["estimate"].device
+    voff = np.concatenate([[0], np.cumsum([int(v.shape[0]) for v in vertices])]).astype(np.int64)      # shapes: no read-back
+    with torch.cuda.device(dev):
+        endv = torch.cat([e.to(torch.int32) + int(voff[v]) for v, e in enumerate(edges)] + [torch.empty(0, 2, device=dev, dtype=torch.int32)])
+        view = torch.from_numpy(np.repeat(np.arange(len(edges), dtype=np.int32), [int(e.shape[0]) for e in edges])).to(dev)
+    res.update(junctions3d(res["lines3d"], res["support"], res["members"], res["estimate"], endv, view, len(vertices), int(voff[-1]), end_frac, reach,
+                           min_votes, angle, pairs_max))
+    res["lines3d_wf"] = res["junctions3d"][res["edges3d"].long()].reshape(-1, 2, 3)
+    return res
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m neat_amd.triangulate",
@@ -204,6 +295,13 @@ def build_parser():
     ap.add_argument("--overlap", type=float, default=DEFAULTS["overlap_min"], help="least overlap of a pair along the partner")
     ap.add_argument("--angle", type=float, default=DEFAULTS["angle_min"], help="least angle between the two planes, degrees")
     ap.add_argument("--out", type=str, default=None, help="output file (default: <instance dir>/<line_detector>-l3d.npz)")
+    ap.add_argument("--wireframe", action="store_true", help="read the views as graphs and write the 3-D wireframe with shared junctions (-wf3d.npz)")
+    ap.add_argument("--end-frac", dest="end_frac", type=float, default=WIREFRAME_DEFAULTS["end_frac"],
+                    help="--wireframe: how far from a line's end, as a share of its length, a segment end still is that end, in (0, 0.5)")
+    ap.add_argument("--reach", type=float, default=WIREFRAME_DEFAULTS["reach"], help="--wireframe: how far beyond its end, likewise, a line may cross another")
+    ap.add_argument("--min-votes", dest="min_votes", type=int, default=WIREFRAME_DEFAULTS["min_votes"], help="--wireframe: views that must share the 2-D vertex")
+    ap.add_argument("--junction-angle", dest="junction_angle", type=float, default=WIREFRAME_DEFAULTS["angle"],
+                    help="--wireframe: the least angle between two lines that meet, degrees")
     ap.add_argument("--gpu", type=int, default=0, help="device index")
     return ap
 
@@ -213,7 +311,7 @@ parse_views = functools.partial(run_io.parse_views, step=True)              # 'a
 
 def out_path(opt, instance_dir, line_detector):
     """The output file of a parsed command line."""
-    return opt.out or os.path.join(instance_dir, f"{line_detector}-l3d.npz")
+    return opt.out or os.path.join(instance_dir, f"{line_detector}-{'wf3d' if getattr(opt, 'wireframe', False) else 'l3d'}.npz")
 
 
 def write_lines(path, lines3d, views, support, cameras):
@@ -222,10 +320,49 @@ def write_lines(path, lines3d, views, support, cameras):
                                                    support=np.asarray(support, np.float64), cameras=np.asarray(cameras, np.float64).reshape(-1, 4, 4)))
 
 
+def write_wireframe(path, res, cameras):
+    """The file of --wireframe, written through a temporary one: lines3d are the edges' segments."""
+    host = {k: res[k].cpu().numpy() for k in WIREFRAME_KEYS + ("views", "support")}
+    src = host["esrc"].astype(np.int64)
+    run_io.replace_file(path, lambda tmp: np.savez(
+        tmp, lines3d=np.asarray(host["lines3d_wf"], np.float64).reshape(-1, 2, 3), junctions3d=np.asarray(host["junctions3d"], np.float64).reshape(-1, 3),
+        edges=np.asarray(host["edges3d"], np.int32).reshape(-1, 2), degree=host["degree"], kind=host["kind"], votes=host["votes"],
+        src=host["esrc"], views=np.asarray(host["views"][src], np.int32), support=np.asarray(host["support"][src], np.float64),
+        cameras=np.asarray(cameras, np.float64).reshape(-1, 4, 4)))
+
+
+def main_wireframe(opt, conf, dataset):
+    """--wireframe: the views as graphs -> the -wf3d.npz."""
+    try:
+        check_wireframe_options(opt.end_frac, opt.reach, opt.min_votes, opt.junction_angle)
+        vertices, edges, Ks, poses = run_io.dataset_graphs(dataset)
+        picked = list(parse_views(opt.views, len(vertices)))
+    except ValueError as err:
+        print(err, file=sys.stderr, flush=True)
+        return 2
+    torch.cuda.set_device(opt.gpu)
+    device = torch.device("cuda", opt.gpu)
+    t0 = time.perf_counter()
+    Ks, poses = _np64([Ks[v] for v in picked]).reshape(-1, 3, 3), _np64([poses[v] for v in picked]).reshape(-1, 4, 4)
+    res = wireframe([torch.as_tensor(vertices[v])[:, :2].to(device) for v in picked], [torch.as_tensor(edges[v]).to(device) for v in picked], Ks, poses,
+                    neighbours=opt.neighbours, angle_min=opt.angle, overlap_min=opt.overlap, sigma_px=opt.sigma, min_score=opt.min_score,
+                    min_views=opt.min_views, end_frac=opt.end_frac, reach=opt.reach, min_votes=opt.min_votes, angle=opt.junction_angle, device=device)
+    torch.cuda.synchronize(device)
+    seconds = time.perf_counter() - t0
+    path = out_path(opt, dataset.instance_dir, conf.get_config("dataset").get("line_detector", "hawp"))
+    write_wireframe(path, res, poses)
+    print(f"{len(picked)} views, {res['estimate'].shape[0]} segments, {res['rows'].shape[0]} hypotheses, {int(res['kept'].sum())} estimates, "
+          f"{res['lines3d'].shape[0]} lines, {res['junctions3d'].shape[0]} vertices, {int((res['kind'] == 1).sum())} junctions, "
+          f"{res['edges3d'].shape[0]} edges, {seconds:.3f} s -> {path}", flush=True)
+    return 0
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     conf = run_io.parse_conf(opt.conf)
     dataset = run_io.build_dataset(conf, opt.data_root, opt.scan_id)
+    if opt.wireframe:
+        return main_wireframe(opt, conf, dataset)
     segments, Ks, poses = run_io.dataset_views(dataset)
     try:
         picked = list(parse_views(opt.views, len(segments)))

@@ -325,6 +325,35 @@ int main() {
     CHECK(WF_WG * WF_REC * 8 <= 64 * 1024);                                // the pair kernels' tile of partners in LDS
   }
 
+  // ---- 3-D wireframes: views, 2-D segments, 3-D lines, 2-D vertices, room for pair keys; counts around the workgroup and empty parts
+  {
+    const long long shapes[][5] = {{0, 0, 0, 0, 0}, {1, 1, 1, 2, 1}, {0, 0, 20, 0, 0}, {4, 80, 0, 60, 16}, {3, 771, 257, 774, 100000},
+                                   {12, 150, 17, 140, 4096}, {4, 1024, 256, 400, 255}, {64, 128000, 40000, 90000, 512000}};
+    for (const auto& sh : shapes) {
+      CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
+        Wf3dWs w;
+        if (!wf3d_layout(b, (int)sh[0], (int)sh[1], (int)sh[2], (int)sh[3], sh[4], &w)) return false;
+        const size_t s2 = 2 * (size_t)sh[1], n = (size_t)sh[2], nv = (size_t)sh[3], p = (size_t)sh[4];
+        if (w.n_sort < s2 || w.n_sort < n || w.n_sort < p || w.sort_bytes < 32 * w.n_sort) return false;
+        r = {{w.total, 8, 256}, {w.rkey, s2 * 8, 256}, {w.rskey, s2 * 8, 256}, {w.rcnt, s2 * 4, 256}, {w.roff, s2 * 8, 256}, {w.vview, nv * 4, 256},
+             {w.pkey, p * 8, 256}, {w.pskey, p * 8, 256}};
+        for (int* q : {w.parent, w.last, w.vidx, w.lvotes}) r.push_back({q, 2 * n * 4, 256});
+        r.push_back({w.ekey, n * 8, 256});
+        r.push_back({w.eskey, n * 8, 256});
+        for (int* q : {w.eline, w.esline, w.keep, w.eidx}) r.push_back({q, n * 4, 256});
+        r.push_back({w.sort, w.sort_bytes, 256});
+        t = w.total_bytes;
+        return true;
+      }));
+    }
+    CHECK(wf3d_counts_ok(WF_MAX_VIEWS, 0x7fffffffLL / 6, WF3_MAX_ENDS / 2 - 1, 0x7fffffffLL, 0x7fffffffLL) && wf3d_counts_ok(0, 0, 0, 0, 0));
+    CHECK(!wf3d_counts_ok(-1, 0, 0, 0, 0) && !wf3d_counts_ok(1, -1, 0, 1, 0) && !wf3d_counts_ok(1, 1, -1, 1, 0) && !wf3d_counts_ok(1, 1, 1, -1, 0) &&
+          !wf3d_counts_ok(1, 1, 1, 1, -1) && !wf3d_counts_ok(WF_MAX_VIEWS + 1, 1, 1, 1, 1) && !wf3d_counts_ok(1, 1, WF3_MAX_ENDS / 2, 1, 1) &&
+          !wf3d_counts_ok(1, 0x7fffffffLL / 6 + 1, 1, 1, 1) && !wf3d_counts_ok(1, 1, 1, 0x80000000LL, 1) && !wf3d_counts_ok(1, 1, 1, 1, 0x80000000LL) &&
+          !wf3d_counts_ok(0, 1, 1, 1, 1) && !wf3d_counts_ok(1, 1, 1, 0, 1));
+    CHECK(2LL * (WF3_MAX_ENDS / 2 - 1) + 1 < (1LL << 24) && WF_MAX_VIEWS < (1 << 16));          // an end id in 24 bits, a view in 16: a pair key in 64
+  }
+
   // ---- scene generation: views and edges; the edge list, then the runs per (view, edge) and their offsets
   {
     const int shapes[][2] = {{0, 0}, {0, 18}, {3, 0}, {1, 1}, {3, 12}, {100, 18}, {7, 257}, {SG_MAX_VIEWS, 4096}};
