@@ -1,5 +1,6 @@
 // Workgroup-wide scans, reductions and compaction shared by the tool kernels (kernels_parse / mesh / evalmesh / eval / frame / trace / post /
-// raycast) and, for block_compact, by lsap_kernel.  As in device_util.hpp, the translation units share one namespace, so only templates and
+// raycast / detect / triangulate / wireframe2d / wireframe3d), by the scans of graph_util.hpp (which scenegen and crease use) and, for
+// block_compact, by lsap_kernel.  As in device_util.hpp, the translation units share one namespace, so only templates and
 // __forceinline__ functions belong here.  No atomics and a fixed order everywhere: a result is the same bits on every run.  Every
 // function ends with a barrier, so it may be called again at once with the same LDS.
 #pragma once

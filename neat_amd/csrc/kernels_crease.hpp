@@ -12,22 +12,20 @@
 //           passed-through vertex are united (the smaller root wins, so the label is the chain's lowest edge); edges sorted by label;
 //           one wavefront per chain decides whether it is one straight line; lines per chain and junction flags counted and scanned.
 //   fill    the lines written chain by chain, sorted by (kind, curved) and then stably by (a, b), re-indexed into the junction list.
-// The only atomic is the union-find's integer fetch-min (detect_union, kernels_detect.hpp); everything else is a plain vector store,
+// The only atomic is the union-find's integer fetch-min (uf_union, graph_util.hpp); everything else is a plain vector store,
 // and where several lanes store to one word they store the same value.  Two runs give the same bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
-#include "block_util.hpp"      // block_exscan, block_carry_scan
 #include "device_util.hpp"     // rounded
-#include "kernels_detect.hpp"  // detect_find, detect_union
+#include "graph_util.hpp"      // uf_find, uf_union; the tiled scan
 
 namespace neat {
 
 constexpr int CR_WG = 256;
 constexpr int CR_WAVES = CR_WG / 64;
-constexpr int CR_SCAN_WG = 1024;
 constexpr unsigned long long CR_KEY_NONE = ~0ull;      // the half-edges of a dropped face: they sort last
 
 __device__ __forceinline__ double cr_dot(double ax, double ay, double az, double bx, double by, double bz) {
@@ -45,34 +43,6 @@ __device__ __forceinline__ double cr_cross2(double ax, double ay, double az, dou
 __device__ __forceinline__ int cr_lo32(unsigned long long k) { return (int)(unsigned)(k & 0xffffffffull); }
 __device__ __forceinline__ int cr_hi32(unsigned long long k) { return (int)(unsigned)(k >> 32); }
 __device__ __forceinline__ unsigned long long cr_pack(int hi, int lo) { return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo; }
-
-// ---- scans of an int-valued function of the index: the sums of tiles of CR_SCAN_WG, one workgroup over the tile sums, then the tiles again
-struct CrNonzero { const int* p; __device__ int operator()(int i) const { return p[i] != 0; } };
-struct CrEquals { const int* p; int v; __device__ int operator()(int i) const { return p[i] == v; } };
-struct CrValue { const int* p; __device__ int operator()(int i) const { return p[i]; } };
-
-template <class F>
-__global__ __launch_bounds__(CR_SCAN_WG) void crease_scan_tile_kernel(int n, F f, int* __restrict__ tile) {
-  __shared__ int s_wave[16];
-  const int i = blockIdx.x * CR_SCAN_WG + threadIdx.x;
-  int tot;
-  block_exscan(i < n ? f(i) : 0, s_wave, &tot);
-  if (threadIdx.x == 0) tile[blockIdx.x] = tot;
-}
-// tile sums -> their exclusive offsets in place; *total = the sum (the host has bounded it below 2^31)
-__global__ __launch_bounds__(CR_SCAN_WG) void crease_scan_top_kernel(int tiles, int* __restrict__ tile, int* __restrict__ total) {
-  __shared__ int s_wave[16];
-  const long long tot = block_carry_scan(tiles, [&](int i) { return tile[i]; }, [&](int i, long long e) { tile[i] = (int)e; }, s_wave);
-  if (threadIdx.x == 0) *total = (int)tot;
-}
-template <class F>
-__global__ __launch_bounds__(CR_SCAN_WG) void crease_scan_apply_kernel(int n, F f, const int* __restrict__ tile, int* __restrict__ out) {
-  __shared__ int s_wave[16];
-  const int i = blockIdx.x * CR_SCAN_WG + threadIdx.x;
-  int tot;
-  const int e = block_exscan(i < n ? f(i) : 0, s_wave, &tot);
-  if (i < n) out[i] = tile[blockIdx.x] + e;
-}
 
 // ---- the refusals: status = 1 for a face index outside the vertices, 2 for a non-finite coordinate (every writer of one launch stores the same value)
 __global__ __launch_bounds__(CR_WG) void crease_check_kernel(const double* __restrict__ verts, int nv, const int* __restrict__ faces, int nf,
@@ -233,11 +203,11 @@ __global__ __launch_bounds__(CR_WG) void crease_vertex_kernel(const unsigned lon
     }
   }
   vstate[v] = pass ? 2 : 1;
-  if (pass) detect_union<__HIP_MEMORY_SCOPE_AGENT>(parent, e1, e2);
+  if (pass) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, e1, e2);
 }
 __global__ __launch_bounds__(CR_WG) void crease_label_kernel(int E, int* __restrict__ parent, unsigned long long* __restrict__ key) {
   const int e = blockIdx.x * CR_WG + threadIdx.x;
-  if (e < E) key[e] = cr_pack(detect_find<__HIP_MEMORY_SCOPE_AGENT>(parent, e), e);
+  if (e < E) key[e] = cr_pack(uf_find<__HIP_MEMORY_SCOPE_AGENT>(parent, e), e);
 }
 __global__ __launch_bounds__(CR_WG) void crease_chain_head_kernel(const unsigned long long* __restrict__ key, int E, int* __restrict__ head) {
   const int i = blockIdx.x * CR_WG + threadIdx.x;

@@ -17,6 +17,7 @@
 
 #include "block_util.hpp"           // block_sum, block_exscan, block_carry_scan, block_compact
 #include "device_util.hpp"
+#include "graph_util.hpp"           // uf_find, uf_union
 
 namespace neat {
 
@@ -91,27 +92,7 @@ __global__ __launch_bounds__(DET_WG) void detect_gradient_kernel(const double* _
   code[(2 * v + 1) * hw + i] = c1o;
 }
 
-// ---- connected components as a label-equivalence union-find: parent[n] <= n always, so a root is the smallest index of its tree.
-// SCOPE: workgroup for the tile in LDS, agent for the merge along the tile borders in global memory (atomics reach the other XCDs'
-// workgroups at agent scope; a stale parent read elsewhere is still an ancestor, so a find over it is still right)
-template <int SCOPE>
-__device__ __forceinline__ int detect_find(int* L, int n) {
-  int p = __hip_atomic_load(L + n, __ATOMIC_RELAXED, SCOPE);
-  while (p != n) { n = p; p = __hip_atomic_load(L + n, __ATOMIC_RELAXED, SCOPE); }
-  return n;
-}
-template <int SCOPE>
-__device__ __forceinline__ void detect_union(int* L, int a, int b) {
-  bool done;
-  do {
-    a = detect_find<SCOPE>(L, a);
-    b = detect_find<SCOPE>(L, b);
-    if (a < b) { const int old = __hip_atomic_fetch_min(L + b, a, __ATOMIC_RELAXED, SCOPE); done = old == b; b = old; }
-    else if (b < a) { const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE); done = old == a; a = old; }
-    else done = true;
-  } while (!done);
-}
-
+// ---- connected components: uf_union of graph_util.hpp, at workgroup scope in a tile's LDS and at agent scope along the tile borders
 __device__ __forceinline__ int detect_tiles(int n) { return (n + DET_TILE - 1) / DET_TILE; }
 
 // one workgroup per (map, tile): the tile's components in LDS, then label = the root's index in the map (-1: unused).  With `size`,
@@ -133,18 +114,18 @@ __global__ __launch_bounds__(DET_WG) void detect_label_tile_kernel(const unsigne
   s_lab[tid] = c != DET_UNUSED ? tid : -1;
   __syncthreads();
   if (c != DET_UNUSED) {          // the four neighbours before this pixel in raster order: every 8-adjacent pair is seen once
-    if (lx > 0 && s_code[tid - 1] == c) detect_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - 1);
+    if (lx > 0 && s_code[tid - 1] == c) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - 1);
     if (ly > 0) {
-      if (lx > 0 && s_code[tid - DET_TILE - 1] == c) detect_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - DET_TILE - 1);
-      if (s_code[tid - DET_TILE] == c) detect_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - DET_TILE);
-      if (lx < DET_TILE - 1 && s_code[tid - DET_TILE + 1] == c) detect_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - DET_TILE + 1);
+      if (lx > 0 && s_code[tid - DET_TILE - 1] == c) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - DET_TILE - 1);
+      if (s_code[tid - DET_TILE] == c) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - DET_TILE);
+      if (lx < DET_TILE - 1 && s_code[tid - DET_TILE + 1] == c) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid, tid - DET_TILE + 1);
     }
   }
   __syncthreads();
   if (!in) return;
   int r = -1;
   if (c != DET_UNUSED) {
-    const int lr = detect_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid);
+    const int lr = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, tid);
     r = (y0 + lr / DET_TILE) * w + x0 + (lr & (DET_TILE - 1));
   }
   label[e] = r;
@@ -164,11 +145,11 @@ __global__ __launch_bounds__(DET_WG) void detect_label_merge_kernel(const unsign
   const unsigned char c = cm[i];
   if (c == DET_UNUSED) return;
   int* L = label + m * hw;
-  if (left && x > 0 && cm[i - 1] == c) detect_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - 1);
+  if (left && x > 0 && cm[i - 1] == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - 1);
   if (y > 0) {
-    if ((left || top) && x > 0 && cm[i - w - 1] == c) detect_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - w - 1);
-    if (top && cm[i - w] == c) detect_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - w);
-    if ((top || right) && x + 1 < w && cm[i - w + 1] == c) detect_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - w + 1);
+    if ((left || top) && x > 0 && cm[i - w - 1] == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - w - 1);
+    if (top && cm[i - w] == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - w);
+    if ((top || right) && x + 1 < w && cm[i - w + 1] == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(L, i, i - w + 1);
   }
 }
 
@@ -181,7 +162,7 @@ __global__ __launch_bounds__(DET_WG) void detect_label_flatten_kernel(int maps, 
   const int i = (int)(idx % hw);
   int* L = label + m * hw;
   if (__hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0) return;
-  const int r = detect_find<__HIP_MEMORY_SCOPE_AGENT>(L, i);
+  const int r = uf_find<__HIP_MEMORY_SCOPE_AGENT>(L, i);
   __hip_atomic_store(L + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (size) {
     const size_t er = m * hw + r;

@@ -14,8 +14,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "block_util.hpp"      // block_carry_scan
 #include "device_util.hpp"
+#include "graph_util.hpp"      // count_scan_kernel: the runs before each (view, edge)
 #include "kernels_raycast.hpp"
 
 namespace neat {
@@ -286,14 +286,6 @@ __global__ __launch_bounds__(SG_WG) void scenegen_edge_kernel(const float* __res
     }
   }
   if (!FILL && lane == 0) cnt[pair] = runs;
-}
-
-// one workgroup: off = the exclusive scan of cnt [n] (clamped to an int), *total = the exact count
-__global__ __launch_bounds__(1024) void scenegen_scan_kernel(int n, const int* __restrict__ cnt, int* __restrict__ off, long long* __restrict__ total) {
-  __shared__ int s_wave[16];
-  const long long tot = block_carry_scan(n, [&](int i) { return cnt[i]; },
-                                         [&](int i, long long e) { off[i] = (int)(e < (long long)INT_MAX ? e : (long long)INT_MAX); }, s_wave);
-  if (threadIdx.x == 0) *total = tot;
 }
 
 }  // namespace neat

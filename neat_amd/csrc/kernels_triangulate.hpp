@@ -20,7 +20,7 @@
 #include <stddef.h>
 
 #include "block_util.hpp"           // block_carry_scan, block_compact
-#include "kernels_detect.hpp"       // detect_find, detect_union: the label-equivalence union-find
+#include "graph_util.hpp"           // uf_union, uf_flatten_kernel, wave_members_each
 
 namespace neat {
 
@@ -274,23 +274,14 @@ __global__ __launch_bounds__(TRI_WG) void tri_link_kernel(int S, int M, const in
   for (int h = lane; h < nh; h += 64) {
     const int p = segoff[nb[a * M + hyp_m[h0 + h]]] + hyp_j[h0 + h];
     if (kept[p] && tri_linked(estimate + 6 * (size_t)g, estimate + 6 * (size_t)p, radius[g], radius[p]))
-      detect_union<__HIP_MEMORY_SCOPE_AGENT>(parent, g, p);
+      uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, g, p);
   }
 }
 
-// label = the root = the component's lowest estimate; last[root] = its highest
-__global__ __launch_bounds__(TRI_WG) void tri_flatten_kernel(int S, int* parent, int* __restrict__ last) {
-  const int g = blockIdx.x * TRI_WG + threadIdx.x;
-  if (g >= S) return;
-  if (__hip_atomic_load(parent + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0) return;
-  const int r = detect_find<__HIP_MEMORY_SCOPE_AGENT>(parent, g);
-  __hip_atomic_store(parent + g, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  atomicMax(last + r, g);
-}
-
-// ---- one wavefront per component, at its root r: its members are the g in [r, last[r]] with label r, met in ascending order (which is
-// view order) 64 at a time.  Distinct views = the changes of view along them; the axis = the best score, lowest index on a tie; tau =
-// the extent of all members' end points along the axis
+// ---- one wavefront per component, at its root r (uf_flatten_kernel has made label = the root = the lowest estimate, last[root] = the
+// highest): its members are the g in [r, last[r]] with label r, met in ascending order (which is view order) 64 at a time.  Distinct
+// views = the changes of view along them; the axis = the best score, lowest index on a tie; tau = the extent of all members' end
+// points along the axis
 __global__ __launch_bounds__(TRI_WG) void tri_component_kernel(int S, const int* __restrict__ label, const int* __restrict__ last,
                                                                const int* __restrict__ view, const double* __restrict__ score,
                                                                const double* __restrict__ estimate, int* __restrict__ nviews,
@@ -324,17 +315,15 @@ __global__ __launch_bounds__(TRI_WG) void tri_component_kernel(int S, const int*
   const double b0 = A[3] - A[0], b1 = A[4] - A[1], b2 = A[5] - A[2], bn = tri_norm3(b0, b1, b2);
   const double u0 = b0 / bn, u1 = b1 / bn, u2 = b2 / bn;
   double lo = INFINITY, hi = -INFINITY;
-  for (int g0 = r; g0 <= end; g0 += 64) {
-    const int g = g0 + lane;
-    if (g <= end && label[g] == r) {
-      const double* E = estimate + 6 * (size_t)g;
+  wave_members_each(label, r, end, lane, [&](int g) {
+#pragma clang fp contract(off)
+    const double* E = estimate + 6 * (size_t)g;
 #pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const double t = ((E[3 * k] - A[0]) * u0 + (E[3 * k + 1] - A[1]) * u1) + (E[3 * k + 2] - A[2]) * u2;
-        lo = fmin(lo, t); hi = fmax(hi, t);
-      }
+    for (int k = 0; k < 2; ++k) {
+      const double t = ((E[3 * k] - A[0]) * u0 + (E[3 * k + 1] - A[1]) * u1) + (E[3 * k + 2] - A[2]) * u2;
+      lo = fmin(lo, t); hi = fmax(hi, t);
     }
-  }
+  });
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { lo = fmin(lo, __shfl_xor(lo, o)); hi = fmax(hi, __shfl_xor(hi, o)); }
   if (lane == 0) { nviews[r] = nv; axis[r] = ba; tau[2 * (size_t)r] = lo; tau[2 * (size_t)r + 1] = hi; }

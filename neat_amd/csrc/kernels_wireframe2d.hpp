@@ -21,7 +21,7 @@
 #include <stddef.h>
 
 #include "block_util.hpp"           // block_carry_scan
-#include "kernels_detect.hpp"       // detect_find, detect_union: the label-equivalence union-find
+#include "graph_util.hpp"           // uf_union, uf_flatten_kernel, wave_members
 
 namespace neat {
 
@@ -118,23 +118,15 @@ __global__ __launch_bounds__(WF_WG) void wf_meet_kernel(const int* __restrict__ 
 #pragma unroll
         for (int kj = 0; kj < 2; ++kj) {
           const double eb = wf_along(B, kj, X, Y);
-          if (eb >= -B[7] && eb <= B[7]) detect_union<__HIP_MEMORY_SCOPE_AGENT>(parent, 2 * (a0 + i) + ki, 2 * (a0 + j0 + jj) + kj);
+          if (eb >= -B[7] && eb <= B[7]) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, 2 * (a0 + i) + ki, 2 * (a0 + j0 + jj) + kj);
         }
       }
     }
   }
 }
 
-// label = the root = the component's lowest endpoint; last[root] = its highest
-__global__ __launch_bounds__(WF_WG) void wf_flatten_kernel(int n, int* parent, int* __restrict__ last) {
-  const int e = blockIdx.x * WF_WG + threadIdx.x;
-  if (e >= n) return;
-  const int r = detect_find<__HIP_MEMORY_SCOPE_AGENT>(parent, e);
-  __hip_atomic_store(parent + e, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  atomicMax(last + r, e);
-}
-
-// one workgroup: vidx [2 S] = the roots before each endpoint = a root's place in the vertex list; voff [V + 1] = the views' first vertices
+// one workgroup, after uf_flatten_kernel (label = the root = the component's lowest endpoint; last[root] = its highest): vidx [2 S] =
+// the roots before each endpoint = a root's place in the vertex list; voff [V + 1] = the views' first vertices
 __global__ __launch_bounds__(1024) void wf_vertex_scan_kernel(int S, int V, const int* __restrict__ segoff, const int* __restrict__ label,
                                                               int* __restrict__ vidx, int* __restrict__ voff) {
   __shared__ int s_wave[16];
@@ -146,8 +138,8 @@ __global__ __launch_bounds__(1024) void wf_vertex_scan_kernel(int S, int V, cons
   }
 }
 
-// ---- one wavefront per junction, at its root r: its members are the endpoints in [r, last[r]] with label r, met in ascending order 64 at
-// a time; every lane adds the five sums of all of them in that order, so all lanes hold the same bits
+// ---- one wavefront per junction, at its root r: its members are the endpoints in [r, last[r]] with label r (wave_members); every lane
+// adds the five sums of all of them in ascending order, so all lanes hold the same bits
 __global__ __launch_bounds__(WF_WG) void wf_junction_kernel(int n, const int* __restrict__ label, const int* __restrict__ last,
                                                             const int* __restrict__ vidx, const double* __restrict__ rec,
                                                             const double* __restrict__ weight, double* __restrict__ vertices,
@@ -159,33 +151,21 @@ __global__ __launch_bounds__(WF_WG) void wf_junction_kernel(int n, const int* __
   const int end = last[r];
   if (end == r) return;                          // a lone end: the T pass writes it
   double a11 = 0.0, a12 = 0.0, a22 = 0.0, b1 = 0.0, b2 = 0.0, sc = -INFINITY;
-  int m = 0;
-  for (int e0 = r; e0 <= end; e0 += 64) {
-    const int e = e0 + lane;
-    const bool mine = e <= end && label[e] == r;
-    unsigned long long bal = __ballot(mine);
-    m += __popcll(bal);
-    if (mine) sc = fmax(sc, weight[e >> 1]);
-    while (bal) {
-      const int b = __builtin_ctzll(bal);
-      bal &= bal - 1ull;
-      const double* R = rec + (size_t)WF_REC * ((e0 + b) >> 1);
-      const double nx = -R[5], ny = R[4];
-      const double c = nx * R[0] + ny * R[1];
-      a11 = a11 + nx * nx; a12 = a12 + nx * ny; a22 = a22 + ny * ny;
-      b1 = b1 + nx * c; b2 = b2 + ny * c;
-    }
-  }
+  const int m = wave_members(label, r, end, lane, [&](int e) { sc = fmax(sc, weight[e >> 1]); }, [&](int e) {
+#pragma clang fp contract(off)
+    const double* R = rec + (size_t)WF_REC * (e >> 1);
+    const double nx = -R[5], ny = R[4];
+    const double c = nx * R[0] + ny * R[1];
+    a11 = a11 + nx * nx; a12 = a12 + nx * ny; a22 = a22 + ny * ny;
+    b1 = b1 + nx * c; b2 = b2 + ny * c;
+  });
   const double det = a11 * a22 - a12 * a12;
   const double X = (a22 * b1 - a12 * b2) / det, Y = (a11 * b2 - a12 * b1) / det;
   double sp = 0.0;
-  for (int e0 = r; e0 <= end; e0 += 64) {
-    const int e = e0 + lane;
-    if (e <= end && label[e] == r) {
-      const double* R = rec + (size_t)WF_REC * (e >> 1);
-      sp = fmax(sp, wf_dist(X, Y, R[2 * (e & 1)], R[2 * (e & 1) + 1]));
-    }
-  }
+  wave_members_each(label, r, end, lane, [&](int e) {
+    const double* R = rec + (size_t)WF_REC * (e >> 1);
+    sp = fmax(sp, wf_dist(X, Y, R[2 * (e & 1)], R[2 * (e & 1) + 1]));
+  });
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { sc = fmax(sc, __shfl_xor(sc, o)); sp = fmax(sp, __shfl_xor(sp, o)); }
   if (lane != 0) return;

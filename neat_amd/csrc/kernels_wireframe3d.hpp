@@ -14,14 +14,14 @@
 // pair key is (q << 40) | (q' << 16) | view, q < q' of different lines, one per pair of distinct records of one 2-D vertex.  ~0 marks an
 // unused key of either list and sorts behind every used one.
 #pragma once
+#include <float.h>
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
 
 #include "block_util.hpp"           // block_carry_scan
-#include "kernels_detect.hpp"       // detect_find, detect_union: the label-equivalence union-find
-#include "kernels_wireframe2d.hpp"  // wf_flatten_kernel: label = the root, last[root] = the component's highest member
+#include "graph_util.hpp"           // uf_union, uf_flatten_kernel, wave_members, count_scan_kernel
 
 namespace neat {
 
@@ -96,14 +96,8 @@ __global__ __launch_bounds__(WF3_WG) void wf3_pair_count_kernel(const wf3_key* _
   rcnt[i] = wf3_walk_records(rs, n, i, [](unsigned, int) {});
 }
 
-// one workgroup: roff [n] = the pairs before each record, *total = all of them
-__global__ __launch_bounds__(1024) void wf3_pair_scan_kernel(int n, const int* __restrict__ rcnt, long long* __restrict__ roff, long long* __restrict__ total) {
-  __shared__ int s_wave[16];
-  const long long tot = block_carry_scan(n, [&](int i) { return rcnt[i]; }, [&](int i, long long x) { roff[i] = x; }, s_wave);
-  if (threadIdx.x == 0) *total = tot;
-}
-
-// the pair keys, at most pairs_max of them (the rest of pkey stays WF3_NONE; the total tells the host that some were left out)
+// the pair keys, once count_scan_kernel has made roff [n] = the pairs before each record and *total = all of them: at most pairs_max
+// keys (the rest of pkey stays WF3_NONE; the total tells the host that some were left out)
 __global__ __launch_bounds__(WF3_WG) void wf3_pair_fill_kernel(const wf3_key* __restrict__ rs, int n, const long long* __restrict__ roff,
                                                                const int* __restrict__ vview, int NV, long long pairs_max, wf3_key* __restrict__ pkey) {
   const int i = blockIdx.x * WF3_WG + threadIdx.x;
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(WF3_WG) void wf3_link_kernel(const wf3_key* __restr
   const double delta2 = wf3_dot(dx, dy, dz, dx, dy, dz);
   const double least = a < c ? a : c;
   if (!(fabs(s - (double)(q0 & 1)) <= reach && fabs(t - (double)(q1 & 1)) <= reach && delta2 <= (reach * reach) * least)) return;
-  detect_union<__HIP_MEMORY_SCOPE_AGENT>(parent, q0, q1);
+  uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, q0, q1);
   atomicMax(lvotes + q0, votes);
   atomicMax(lvotes + q1, votes);
 }
@@ -161,8 +155,9 @@ __global__ __launch_bounds__(1024) void wf3_vertex_scan_kernel(int n2, const int
   if (threadIdx.x == 0) *n_vertices = (int)tot;
 }
 
-// ---- one wavefront per vertex, at its root r: its members are the end ids in [r, last[r]] with label r, met in ascending order 64 at a
-// time; every lane adds the sums of all of them in that order, so all lanes hold the same bits
+// ---- one wavefront per vertex, at its root r (uf_flatten_kernel has made label = the root, last[root] = the highest member): its
+// members are the end ids in [r, last[r]] with label r (wave_members); every lane adds the sums of all of them in ascending order, so all
+// lanes hold the same bits
 __global__ __launch_bounds__(WF3_WG) void wf3_vertex_kernel(int n2, const int* __restrict__ label, const int* __restrict__ last,
                                                             const int* __restrict__ vidx, const int* __restrict__ lvotes,
                                                             const double* __restrict__ lines3d, double* __restrict__ vertices,
@@ -181,29 +176,21 @@ __global__ __launch_bounds__(WF3_WG) void wf3_vertex_kernel(int n2, const int* _
     return;
   }
   double m00 = 0.0, m01 = 0.0, m02 = 0.0, m11 = 0.0, m12 = 0.0, m22 = 0.0, y0 = 0.0, y1 = 0.0, y2 = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
-  int m = 0, vt = 0;
-  for (int e0 = r; e0 <= end; e0 += 64) {
-    const int e = e0 + lane;
-    const bool mine = e <= end && label[e] == r;
-    unsigned long long bal = __ballot(mine);
-    m += __popcll(bal);
-    if (mine) vt = max(vt, lvotes[e]);
-    while (bal) {
-      const int q = e0 + __builtin_ctzll(bal);
-      bal &= bal - 1ull;
-      const double* A = lines3d + 6 * (size_t)(q >> 1);
-      const double ux = A[3] - A[0], uy = A[4] - A[1], uz = A[5] - A[2];
-      const double uu = wf3_dot(ux, uy, uz, ux, uy, uz);
-      const double p00 = 1.0 - (ux * ux) / uu, p01 = -((ux * uy) / uu), p02 = -((ux * uz) / uu);
-      const double p11 = 1.0 - (uy * uy) / uu, p12 = -((uy * uz) / uu), p22 = 1.0 - (uz * uz) / uu;
-      m00 = m00 + p00; m01 = m01 + p01; m02 = m02 + p02; m11 = m11 + p11; m12 = m12 + p12; m22 = m22 + p22;
-      y0 = y0 + ((p00 * A[0] + p01 * A[1]) + p02 * A[2]);
-      y1 = y1 + ((p01 * A[0] + p11 * A[1]) + p12 * A[2]);
-      y2 = y2 + ((p02 * A[0] + p12 * A[1]) + p22 * A[2]);
-      const double* E = A + 3 * (q & 1);
-      sx = sx + E[0]; sy = sy + E[1]; sz = sz + E[2];
-    }
-  }
+  int vt = 0;
+  const int m = wave_members(label, r, end, lane, [&](int e) { vt = max(vt, lvotes[e]); }, [&](int q) {
+#pragma clang fp contract(off)
+    const double* A = lines3d + 6 * (size_t)(q >> 1);
+    const double ux = A[3] - A[0], uy = A[4] - A[1], uz = A[5] - A[2];
+    const double uu = wf3_dot(ux, uy, uz, ux, uy, uz);
+    const double p00 = 1.0 - (ux * ux) / uu, p01 = -((ux * uy) / uu), p02 = -((ux * uz) / uu);
+    const double p11 = 1.0 - (uy * uy) / uu, p12 = -((uy * uz) / uu), p22 = 1.0 - (uz * uz) / uu;
+    m00 = m00 + p00; m01 = m01 + p01; m02 = m02 + p02; m11 = m11 + p11; m12 = m12 + p12; m22 = m22 + p22;
+    y0 = y0 + ((p00 * A[0] + p01 * A[1]) + p02 * A[2]);
+    y1 = y1 + ((p01 * A[0] + p11 * A[1]) + p12 * A[2]);
+    y2 = y2 + ((p02 * A[0] + p12 * A[1]) + p22 * A[2]);
+    const double* E = A + 3 * (q & 1);
+    sx = sx + E[0]; sy = sy + E[1]; sz = sz + E[2];
+  });
   const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
   const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
   const double det = (m00 * c00 + m01 * c01) + m02 * c02;
@@ -215,14 +202,12 @@ __global__ __launch_bounds__(WF3_WG) void wf3_vertex_kernel(int n2, const int* _
     X = sx / n; Y = sy / n; Z = sz / n;
   }
   double sp = 0.0;
-  for (int e0 = r; e0 <= end; e0 += 64) {
-    const int e = e0 + lane;
-    if (e <= end && label[e] == r) {
-      const double* E = lines3d + 3 * (size_t)e;
-      const double dx = X - E[0], dy = Y - E[1], dz = Z - E[2];
-      sp = fmax(sp, sqrt(wf3_dot(dx, dy, dz, dx, dy, dz)));
-    }
-  }
+  wave_members_each(label, r, end, lane, [&](int e) {
+#pragma clang fp contract(off)
+    const double* E = lines3d + 3 * (size_t)e;
+    const double dx = X - E[0], dy = Y - E[1], dz = Z - E[2];
+    sp = fmax(sp, sqrt(wf3_dot(dx, dy, dz, dx, dy, dz)));
+  });
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { vt = max(vt, __shfl_xor(vt, o)); sp = fmax(sp, __shfl_xor(sp, o)); }
   if (lane != 0) return;

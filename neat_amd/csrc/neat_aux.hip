@@ -43,7 +43,36 @@ int g_ffn_mfma = 1;         // the 256 x 256 layers of the global-junction MLP (
 int g_sampler_ablate = 0;   // probes: sampler_round_kernel without its bisection (1) / refine (2) / final (4) part (tuning key 30)
 
 #define NEAT_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
+#define NEAT_PASS(expr) do { const int r_ = (expr); if (r_ != 0) return r_; } while (0)
 inline dim3 grid1(int n, int b = 256) { return dim3((n + b - 1) / b); }
+
+// rocprim's radix sort of bits [bit0, bit1) into a workspace's sort region of `room` bytes (sort_scratch_bytes, ws_layout.hpp): ask what
+// it wants, -2 if that is more than the room, then sort.  run = false is the question alone, for a caller that refuses before its
+// first launch
+template <class K>
+int sort_keys(void* tmp, size_t room, K* in, K* out, size_t n, unsigned bit0, unsigned bit1, hipStream_t st, bool run = true) {
+  size_t tb = 0;
+  NEAT_CHECK(rocprim::radix_sort_keys(nullptr, tb, in, out, n, bit0, bit1, st));
+  if (tb > room) return -2;
+  return run ? (int)rocprim::radix_sort_keys(tmp, tb, in, out, n, bit0, bit1, st) : 0;
+}
+template <class K, class V>
+int sort_pairs(void* tmp, size_t room, K* kin, K* kout, V* vin, V* vout, size_t n, unsigned bit0, unsigned bit1, hipStream_t st, bool run = true) {
+  size_t tb = 0;
+  NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, bit0, bit1, st));
+  if (tb > room) return -2;
+  return run ? (int)rocprim::radix_sort_pairs(tmp, tb, kin, kout, vin, vout, n, bit0, bit1, st) : 0;
+}
+
+// out [n] = the exclusive scan of f over [0, n) (null: the total alone), *total = its sum; tile: n / SCAN_WG + 1 ints.  Three launches over
+// tiles of SCAN_WG (graph_util.hpp), for lists of millions; a list that one workgroup walks in a few rounds takes count_scan_kernel
+template <class F>
+void tiled_scan(int n, F f, int* tile, int* out, int* total, hipStream_t st) {
+  const int tiles = (n + SCAN_WG - 1) / SCAN_WG;
+  if (tiles > 0) hipLaunchKernelGGL(scan_tile_kernel<F>, dim3(tiles), dim3(SCAN_WG), 0, st, n, f, tile);
+  hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_WG), 0, st, tiles, tile, total);
+  if (tiles > 0 && out) hipLaunchKernelGGL(scan_apply_kernel<F>, dim3(tiles), dim3(SCAN_WG), 0, st, n, f, (const int*)tile, out);
+}
 
 __global__ void volume_weights_kernel(const float* __restrict__ z, const float* __restrict__ sdf, int R, int S,
                                       const float* __restrict__ beta_ptr, float* __restrict__ weights) {
@@ -1125,15 +1154,7 @@ int neat_post_refine_view(const float* cur, const int* n_cur, int ncap, const fl
   return (int)hipGetLastError();
 }
 
-static size_t post_sort_bytes(int n) {
-  size_t a = 0, b = 0;
-  if (n <= 0) return 0;
-  if (rocprim::radix_sort_keys(nullptr, a, (int*)nullptr, (int*)nullptr, 2 * (size_t)n) != hipSuccess) return 0;
-  if (rocprim::radix_sort_keys(nullptr, b, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)n) != hipSuccess) return 0;
-  return std::max(a, b);
-}
-
-size_t neat_post_snap_ws_bytes(int n, int G) { PostSnapWs w; return post_snap_layout(nullptr, n, G, post_sort_bytes(n), &w) ? w.total : 0; }
+size_t neat_post_snap_ws_bytes(int n, int G) { PostSnapWs w; return post_snap_layout(nullptr, n, G, &w) ? w.total : 0; }
 
 int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique, float* junctions, int* pcount, int* edges, float* lines_out,
                    int* counts, void* ws, void* stream) {
@@ -1141,14 +1162,12 @@ int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique,
   if (n < 0 || !post_grid_ok(G) || !counts || (unique != 0 && unique != 1) || max_snap != max_snap) return -1;   // G > 1024: refused before any launch
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) return (int)hipMemsetAsync(counts, 0, 2 * sizeof(int), st);
-  const size_t sort_bytes = post_sort_bytes(n);
-  if (!post_snap_layout(ws, n, G, sort_bytes, &w) || !lines || !junctions || !pcount || !edges || !lines_out || !ws) return -1;
+  if (!post_snap_layout(ws, n, G, &w) || !lines || !junctions || !pcount || !edges || !lines_out || !ws) return -1;
   const int M = 2 * n;
   hipLaunchKernelGGL(post_snap_bbox_kernel, dim3(1), dim3(1024), 0, st, lines, M, G, w.box);
   hipLaunchKernelGGL(post_snap_key_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, lines, M, G, (const float*)w.box, w.key);
   NEAT_CHECK(hipGetLastError());
-  size_t tb = sort_bytes;
-  NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.key, w.skey, (size_t)M, 0u, 32u, st));
+  NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.key, w.skey, (size_t)M, 0u, 32u, st));
   hipLaunchKernelGGL(post_snap_cells_kernel, dim3(1), dim3(1024), 0, st, (const int*)w.skey, M, w.head, w.counts);
   hipLaunchKernelGGL(post_snap_peak_kernel, grid1(M, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)w.skey, (const int*)w.head, (const int*)w.counts, M, G,
                      w.flag, w.cnt);
@@ -1163,8 +1182,7 @@ int neat_post_snap(const float* lines, int n, int G, float max_snap, int unique,
   }
   hipLaunchKernelGGL(post_snap_pairkey_kernel, grid1(n, PARSE_WG), dim3(PARSE_WG), 0, st, (const int*)w.near, (const float*)w.dist2, n, max_snap, w.pkey);
   NEAT_CHECK(hipGetLastError());
-  tb = sort_bytes;
-  NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.pkey, w.spkey, (size_t)n, 0u, 64u, st));
+  NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.pkey, w.spkey, (size_t)n, 0u, 64u, st));
   hipLaunchKernelGGL(post_snap_unique_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long*)w.spkey, n, (const float*)junctions, w.idx, edges,
                      lines_out, counts + 1);
   return (int)hipGetLastError();
@@ -1182,14 +1200,12 @@ int neat_raycast_build(const double* verts, int nv, const int* faces, int nf, vo
   hipStream_t st = (hipStream_t)stream;
   NEAT_CHECK(hipMemsetAsync(w.status, 0, 256, st));
   if (nf > 0) {
-    size_t tb = 0;
-    NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, tb, w.key, w.skey, w.val, w.sval, (size_t)nf, 0u, 64u, st));
-    if (tb > w.sort_bytes) return -2;
+    NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.key, w.skey, w.val, w.sval, (size_t)nf, 0u, 64u, st, false));      // asked before anything is launched
     hipLaunchKernelGGL(raycast_prep_kernel, dim3(w.tiles), dim3(RC_WG), 0, st, verts, nv, faces, nf, w.status, w.partial);
     hipLaunchKernelGGL(raycast_scene_box_kernel, dim3(1), dim3(RC_WG), 0, st, (const double*)w.partial, w.tiles, w.box);
     hipLaunchKernelGGL(raycast_key_kernel, dim3(w.tiles), dim3(RC_WG), 0, st, verts, faces, nf, (const int*)w.status, (const double*)w.box, w.key, w.val);
     NEAT_CHECK(hipGetLastError());
-    NEAT_CHECK(rocprim::radix_sort_pairs(w.sort, tb, w.key, w.skey, w.val, w.sval, (size_t)nf, 0u, 64u, st));
+    NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.key, w.skey, w.val, w.sval, (size_t)nf, 0u, 64u, st));
   }
   hipLaunchKernelGGL(raycast_leaf_kernel, dim3(w.L / w.per), dim3(RC_WG), 0, st, verts, faces, nf, w.L, w.per, (const int*)w.status,
                        (const int*)(nf > 0 ? w.sval : nullptr),
@@ -1347,7 +1363,7 @@ int neat_tri_lines(const int* segoff, int V, int S, int nmax, const int* nb, int
   if (H > 0)
     hipLaunchKernelGGL(tri_link_kernel, per_wave, dim3(TRI_WG), 0, st, S, M, view, segoff, nb, hoff, hyp_m, hyp_j, (const int*)kept,
                        (const double*)estimate, (const double*)w.radius, label);
-  hipLaunchKernelGGL(tri_flatten_kernel, per_seg, dim3(TRI_WG), 0, st, S, label, w.last);
+  hipLaunchKernelGGL(uf_flatten_kernel, grid1(S, UF_WG), dim3(UF_WG), 0, st, S, label, w.last);
   hipLaunchKernelGGL(tri_component_kernel, per_wave, dim3(TRI_WG), 0, st, S, (const int*)label, (const int*)w.last, view, (const double*)score,
                      (const double*)estimate, w.nviews, w.axis, w.tau);
   hipLaunchKernelGGL(tri_output_kernel, dim3(1), dim3(1024), 0, st, S, min_views, (const int*)label, (const int*)w.nviews, (const int*)w.axis,
@@ -1404,7 +1420,7 @@ int neat_scenegen_edge_count(const void* bvh, int nf, const double* junctions, i
   hipLaunchKernelGGL(scenegen_edge_kernel<false>, grid1(pairs, SG_WAVES), dim3(SG_WG), 0, st, (const float*)t.nodes, (const double*)t.tris, nf, t.L,
                      junctions, (const int*)w.edges, E, K, pose, V, H, W, step, min_len, bias, near, w.cnt, (const int*)nullptr, 0, (int*)nullptr,
                      (double*)nullptr, (double*)nullptr, (unsigned char*)nullptr);
-  hipLaunchKernelGGL(scenegen_scan_kernel, dim3(1), dim3(1024), 0, st, pairs, (const int*)w.cnt, w.off, total);
+  hipLaunchKernelGGL(count_scan_kernel<int>, dim3(1), dim3(1024), 0, st, pairs, (const int*)w.cnt, w.off, total);
   return (int)hipGetLastError();
 }
 
@@ -1429,30 +1445,6 @@ int neat_scenegen_edge_fill(const void* bvh, int nf, const double* junctions, in
 // ---- added to ABI v15: the crease lines of a triangle mesh (kernels_crease.hpp) -----------------------------------------------------------
 namespace {
 
-// out [n] = the exclusive scan of f over [0, n) (null: the total alone), *total = its sum
-template <class F>
-void crease_scan(int n, F f, const CreaseWs& w, int* out, int* total, hipStream_t st) {
-  const int tiles = (n + CR_SCAN_WG - 1) / CR_SCAN_WG;
-  if (tiles > 0) hipLaunchKernelGGL(crease_scan_tile_kernel<F>, dim3(tiles), dim3(CR_SCAN_WG), 0, st, n, f, w.tile);
-  hipLaunchKernelGGL(crease_scan_top_kernel, dim3(1), dim3(CR_SCAN_WG), 0, st, tiles, w.tile, total);
-  if (tiles > 0 && out) hipLaunchKernelGGL(crease_scan_apply_kernel<F>, dim3(tiles), dim3(CR_SCAN_WG), 0, st, n, f, (const int*)w.tile, out);
-}
-
-int crease_sort_pairs(const CreaseWs& w, unsigned long long* kin, unsigned long long* kout, int* vin, int* vout, size_t n, unsigned bit0,
-                      unsigned bit1, hipStream_t st) {
-  size_t tb = 0;
-  NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, bit0, bit1, st));
-  if (tb > w.sort_bytes) return -2;
-  return (int)rocprim::radix_sort_pairs(w.sort, tb, kin, kout, vin, vout, n, bit0, bit1, st);
-}
-
-int crease_sort_keys(const CreaseWs& w, unsigned long long* kin, unsigned long long* kout, size_t n, hipStream_t st) {
-  size_t tb = 0;
-  NEAT_CHECK(rocprim::radix_sort_keys(nullptr, tb, kin, kout, n, 0u, 64u, st));
-  if (tb > w.sort_bytes) return -2;
-  return (int)rocprim::radix_sort_keys(w.sort, tb, kin, kout, n, 0u, 64u, st);
-}
-
 // the counts that an earlier call left in the workspace are the ones the host passes back
 int crease_state_is(const CreaseWs& w, int first, int n, const int* want, hipStream_t st) {
   int got[3] = {0, 0, 0};
@@ -1463,7 +1455,6 @@ int crease_state_is(const CreaseWs& w, int first, int n, const int* want, hipStr
   return 0;
 }
 
-#define NEAT_PASS(expr) do { const int r_ = (expr); if (r_ != 0) return r_; } while (0)
 constexpr int CR_ST_HALVES = 2, CR_ST_CHAINS = 3, CR_ST_EDGES = 4, CR_ST_LINES = 5, CR_ST_JUNCTIONS = 6;
 
 }  // namespace
@@ -1472,12 +1463,12 @@ extern "C" {
 
 size_t neat_crease_scratch_bytes(int nv, int nf) {
   CreaseWs w;
-  return crease_layout(nullptr, nv, nf, CR_SCAN_WG, &w) ? w.total : 0;
+  return crease_layout(nullptr, nv, nf, SCAN_WG, &w) ? w.total : 0;
 }
 
 int neat_crease_edges(const double* verts, int nv, const int* faces, int nf, double cos_angle, int boundary, void* ws, int* counts, void* stream) {
   CreaseWs w;
-  if (!crease_layout(ws, nv, nf, CR_SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || !counts || !(cos_angle > -1.0 && cos_angle < 1.0) ||
+  if (!crease_layout(ws, nv, nf, SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || !counts || !(cos_angle > -1.0 && cos_angle < 1.0) ||
       (boundary != 0 && boundary != 1) || (nv > 0 && !verts) || (nf > 0 && !faces))
     return -1;
   hipStream_t st = (hipStream_t)stream;
@@ -1500,10 +1491,10 @@ int neat_crease_edges(const double* verts, int nv, const int* faces, int nf, dou
     for (int axis = 2; axis >= 0; --axis) {
       hipLaunchKernelGGL(crease_vkey_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, verts, nv, axis, (const int*)(axis == 2 ? nullptr : w.vb), w.ka, w.va);
       NEAT_CHECK(hipGetLastError());
-      NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.va, w.vb, (size_t)nv, 0u, 64u, st));
+      NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.ka, w.kb, w.va, w.vb, (size_t)nv, 0u, 64u, st));
     }
     hipLaunchKernelGGL(crease_vhead_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, verts, nv, (const int*)w.vb, w.vhead);
-    crease_scan(nv, CrNonzero{w.vhead}, w, w.vslot, counts + 1, st);
+    tiled_scan(nv, IsNonzero{w.vhead}, w.tile, w.vslot, counts + 1, st);
     hipLaunchKernelGGL(crease_vrep_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, nv, (const int*)w.vb, (const int*)w.vhead, (const int*)w.vslot, w.rep);
     hipLaunchKernelGGL(crease_weld_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, nv, (const int*)w.vb, (const int*)w.vhead, (const int*)w.vslot,
                        (const int*)w.rep, w.weld);
@@ -1511,11 +1502,11 @@ int neat_crease_edges(const double* verts, int nv, const int* faces, int nf, dou
   if (nf > 0) {
     hipLaunchKernelGGL(crease_face_kernel, grid1(nf, CR_WG), dim3(CR_WG), 0, st, verts, faces, nf, (const int*)w.weld, w.fn, w.ka, w.va);
     NEAT_CHECK(hipGetLastError());
-    NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.va, w.vb, (size_t)w.M, 0u, 64u, st));
+    NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.ka, w.kb, w.va, w.vb, (size_t)w.M, 0u, 64u, st));
     hipLaunchKernelGGL(crease_kind_kernel, grid1(w.M, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.kb, (const int*)w.vb, w.M, faces,
                        (const int*)w.weld, (const double*)w.fn, cos_angle, boundary, w.mark, w.state + CR_ST_HALVES);
-    crease_scan(w.M, CrNonzero{w.mark}, w, w.slot, counts + 3, st);
-    for (int kind = 0; kind < 3; ++kind) crease_scan(w.M, CrEquals{w.mark, kind + 1}, w, nullptr, counts + 4 + kind, st);
+    tiled_scan(w.M, IsNonzero{w.mark}, w.tile, w.slot, counts + 3, st);
+    for (int kind = 0; kind < 3; ++kind) tiled_scan(w.M, IsEqual{w.mark, kind + 1}, w.tile, nullptr, counts + 4 + kind, st);
     hipLaunchKernelGGL(crease_edge_kernel, grid1(w.M, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.kb, w.M, (const int*)w.mark,
                        (const int*)w.slot, w.elo, w.ehi, w.ekind);
   }
@@ -1526,7 +1517,7 @@ int neat_crease_edges(const double* verts, int nv, const int* faces, int nf, dou
 
 int neat_crease_chains(const double* verts, int nv, int nf, int E, double sin2_turn, double dev, void* ws, int* counts, void* stream) {
   CreaseWs w;
-  if (!crease_layout(ws, nv, nf, CR_SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || !counts || E < 0 || E > w.M || !(sin2_turn >= 0.0 && sin2_turn <= 1.0) ||
+  if (!crease_layout(ws, nv, nf, SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || !counts || E < 0 || E > w.M || !(sin2_turn >= 0.0 && sin2_turn <= 1.0) ||
       !(dev >= 0.0) || !std::isfinite(dev) || (E > 0 && !verts))
     return -1;
   hipStream_t st = (hipStream_t)stream;
@@ -1538,20 +1529,20 @@ int neat_crease_chains(const double* verts, int nv, int nf, int E, double sin2_t
   NEAT_CHECK(hipMemsetAsync(w.jflag, 0, (size_t)nv * sizeof(int), st));
   hipLaunchKernelGGL(crease_incidence_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, E, (const int*)w.elo, (const int*)w.ehi, w.ka, w.parent);
   NEAT_CHECK(hipGetLastError());
-  NEAT_PASS(crease_sort_keys(w, w.ka, w.kb, 2 * (size_t)E, st));
+  NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.ka, w.kb, 2 * (size_t)E, 0u, 64u, st));
   hipLaunchKernelGGL(crease_vertex_kernel, grid1(2 * E, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.kb, 2 * E, verts, (const int*)w.elo,
                      (const int*)w.ehi, (const int*)w.ekind, sin2_turn, w.vstate, w.parent);
   hipLaunchKernelGGL(crease_label_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, E, w.parent, w.ka);
   NEAT_CHECK(hipGetLastError());
-  NEAT_PASS(crease_sort_keys(w, w.ka, w.ckey, (size_t)E, st));
+  NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.ka, w.ckey, (size_t)E, 0u, 64u, st));
   hipLaunchKernelGGL(crease_chain_head_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, (const unsigned long long*)w.ckey, E, w.mark);
-  crease_scan(E, CrNonzero{w.mark}, w, w.slot, w.state + CR_ST_CHAINS, st);
+  tiled_scan(E, IsNonzero{w.mark}, w.tile, w.slot, w.state + CR_ST_CHAINS, st);
   hipLaunchKernelGGL(crease_chain_start_kernel, grid1(E, CR_WG), dim3(CR_WG), 0, st, E, (const int*)w.mark, (const int*)w.slot, w.cstart);
   hipLaunchKernelGGL(crease_chain_kernel<false>, grid1(E, CR_WAVES), dim3(CR_WG), 0, st, (const unsigned long long*)w.ckey, E,
                      (const int*)(w.state + CR_ST_CHAINS), (const int*)w.cstart, verts, (const int*)w.elo, (const int*)w.ehi, (const int*)w.ekind,
                      (const int*)w.vstate, dev, w.cinfo, w.cnl, w.jflag, (const int*)nullptr, 0, (unsigned long long*)nullptr, (int*)nullptr);
-  crease_scan(E, CrValue{w.cnl}, w, w.coff, counts + 1, st);
-  crease_scan(nv, CrNonzero{w.jflag}, w, w.jmap, counts + 2, st);
+  tiled_scan(E, Value{w.cnl}, w.tile, w.coff, counts + 1, st);
+  tiled_scan(nv, IsNonzero{w.jflag}, w.tile, w.jmap, counts + 2, st);
   NEAT_CHECK(hipGetLastError());
   NEAT_CHECK(hipMemcpyAsync(counts, w.state + CR_ST_CHAINS, sizeof(int), hipMemcpyDeviceToDevice, st));
   return (int)hipMemcpyAsync(w.state + CR_ST_LINES, counts + 1, 2 * sizeof(int), hipMemcpyDeviceToDevice, st);
@@ -1560,7 +1551,7 @@ int neat_crease_chains(const double* verts, int nv, int nf, int E, double sin2_t
 int neat_crease_fill(const double* verts, int nv, int nf, int E, void* ws, int n_lines, int n_junc, double* junctions, int* vertex, int* lines,
                      unsigned char* kind, unsigned char* curved, void* stream) {
   CreaseWs w;
-  if (!crease_layout(ws, nv, nf, CR_SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || E < 0 || E > w.M || n_lines < 0 || n_lines > E || n_junc < 0 ||
+  if (!crease_layout(ws, nv, nf, SCAN_WG, &w) || !ws || ((uintptr_t)ws & 255) || E < 0 || E > w.M || n_lines < 0 || n_lines > E || n_junc < 0 ||
       n_junc > nv || (long long)n_junc > 2ll * n_lines || (n_lines > 0 && n_junc < 2))
     return -1;
   if (n_lines == 0) return 0;
@@ -1573,10 +1564,10 @@ int neat_crease_fill(const double* verts, int nv, int nf, int E, void* ws, int n
                      (const int*)w.vstate, 0.0, w.cinfo, (int*)nullptr, (int*)nullptr, (const int*)w.coff, n_lines, w.lab, w.ltag);
   hipLaunchKernelGGL(crease_tagkey_kernel, grid1(n_lines, CR_WG), dim3(CR_WG), 0, st, n_lines, (const int*)w.ltag, w.ka, w.va);
   NEAT_CHECK(hipGetLastError());
-  NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.va, w.vb, (size_t)n_lines, 0u, 3u, st));
+  NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.ka, w.kb, w.va, w.vb, (size_t)n_lines, 0u, 3u, st));
   hipLaunchKernelGGL(crease_abkey_kernel, grid1(n_lines, CR_WG), dim3(CR_WG), 0, st, n_lines, (const int*)w.vb, (const unsigned long long*)w.lab, w.ka);
   NEAT_CHECK(hipGetLastError());
-  NEAT_PASS(crease_sort_pairs(w, w.ka, w.kb, w.vb, w.va, (size_t)n_lines, 0u, 64u, st));
+  NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.ka, w.kb, w.vb, w.va, (size_t)n_lines, 0u, 64u, st));
   hipLaunchKernelGGL(crease_lines_kernel, grid1(n_lines, CR_WG), dim3(CR_WG), 0, st, n_lines, (const unsigned long long*)w.kb, (const int*)w.va,
                      (const int*)w.ltag, (const int*)w.jmap, lines, kind, curved);
   hipLaunchKernelGGL(crease_junction_kernel, grid1(nv, CR_WG), dim3(CR_WG), 0, st, verts, nv, (const int*)w.jflag, (const int*)w.jmap, n_junc, junctions,
@@ -1605,10 +1596,10 @@ int neat_wf2d_build(const double* segments, const int* segoff, const double* wei
   if (!segments || !segoff || !weight || !ws || ((uintptr_t)ws & 255) || !vertices || !degree || !kind || !score || !spread || !t_edge || !ends ||
       !edges || !eweight || !esrc)
     return -1;
-  const dim3 per_seg(grid1(S, WF_WG)), per_end(grid1(2 * S, WF_WG)), per_wave(grid1(2 * S, WF_WAVES)), pairs((unsigned)((long long)V * w.tiles));
+  const dim3 per_seg(grid1(S, WF_WG)), per_wave(grid1(2 * S, WF_WAVES)), pairs((unsigned)((long long)V * w.tiles));
   hipLaunchKernelGGL(wf_segment_kernel, per_seg, dim3(WF_WG), 0, st, segments, segoff, V, S, gap, frac, w.rec, w.view, w.parent, w.last);
   hipLaunchKernelGGL(wf_meet_kernel, pairs, dim3(WF_WG), 0, st, segoff, S, w.tiles, (const double*)w.rec, sin_min, w.parent);
-  hipLaunchKernelGGL(wf_flatten_kernel, per_end, dim3(WF_WG), 0, st, 2 * S, w.parent, w.last);
+  hipLaunchKernelGGL(uf_flatten_kernel, grid1(2 * S, UF_WG), dim3(UF_WG), 0, st, 2 * S, w.parent, w.last);
   NEAT_CHECK(hipGetLastError());
   hipLaunchKernelGGL(wf_vertex_scan_kernel, dim3(1), dim3(1024), 0, st, S, V, segoff, (const int*)w.parent, w.vidx, voff);
   hipLaunchKernelGGL(wf_junction_kernel, per_wave, dim3(WF_WG), 0, st, 2 * S, (const int*)w.parent, (const int*)w.last, (const int*)w.vidx,
@@ -1646,11 +1637,10 @@ int neat_wf3d_build(const double* lines3d, const double* support, int N, const i
       (S > 0 && (!members || !estimate || !endv || !view)))
     return -1;
   const size_t n_rec = 2 * (size_t)S, n_pair = (size_t)pairs_max;
-  size_t need[3] = {0, 0, 0};                                            // what the three sorts want, asked before anything is launched
-  if (n_rec > 0) NEAT_CHECK(rocprim::radix_sort_keys(nullptr, need[0], w.rkey, w.rskey, n_rec, 0u, 64u, st));
-  if (n_rec > 0 && n_pair > 0) NEAT_CHECK(rocprim::radix_sort_keys(nullptr, need[1], w.pkey, w.pskey, n_pair, 0u, 64u, st));
-  NEAT_CHECK(rocprim::radix_sort_pairs(nullptr, need[2], w.ekey, w.eskey, w.eline, w.esline, (size_t)N, 0u, 64u, st));
-  if (std::max(need[0], std::max(need[1], need[2])) > w.sort_bytes) return -2;
+  // what the three sorts want, asked before anything is launched
+  if (n_rec > 0) NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.rkey, w.rskey, n_rec, 0u, 64u, st, false));
+  if (n_rec > 0 && n_pair > 0) NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.pkey, w.pskey, n_pair, 0u, 64u, st, false));
+  NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.ekey, w.eskey, w.eline, w.esline, (size_t)N, 0u, 64u, st, false));
   const int n2 = 2 * N;
   NEAT_CHECK(hipMemsetAsync(w.total, 0, sizeof(long long), st));
   hipLaunchKernelGGL(wf3_init_kernel, grid1(n2, WF3_WG), dim3(WF3_WG), 0, st, n2, w.parent, w.last, w.lvotes);
@@ -1659,30 +1649,27 @@ int neat_wf3d_build(const double* lines3d, const double* support, int N, const i
     hipLaunchKernelGGL(wf3_ends_kernel, grid1(S, WF3_WG), dim3(WF3_WG), 0, st, lines3d, N, members, estimate, endv, view, V, S, NV, end_frac, w.rkey,
                        w.vview);
     NEAT_CHECK(hipGetLastError());
-    size_t tb = need[0];
-    NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.rkey, w.rskey, n_rec, 0u, 64u, st));
+    NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.rkey, w.rskey, n_rec, 0u, 64u, st));
     hipLaunchKernelGGL(wf3_pair_count_kernel, grid1(2 * S, WF3_WG), dim3(WF3_WG), 0, st, (const wf3_key*)w.rskey, 2 * S, w.rcnt);
-    hipLaunchKernelGGL(wf3_pair_scan_kernel, dim3(1), dim3(1024), 0, st, 2 * S, (const int*)w.rcnt, w.roff, w.total);
+    hipLaunchKernelGGL(count_scan_kernel<long long>, dim3(1), dim3(1024), 0, st, 2 * S, (const int*)w.rcnt, w.roff, w.total);
     if (n_pair > 0) {
       NEAT_CHECK(hipMemsetAsync(w.pkey, 0xff, n_pair * sizeof(wf3_key), st));
       hipLaunchKernelGGL(wf3_pair_fill_kernel, grid1(2 * S, WF3_WG), dim3(WF3_WG), 0, st, (const wf3_key*)w.rskey, 2 * S, (const long long*)w.roff,
                          (const int*)w.vview, NV, pairs_max, w.pkey);
       NEAT_CHECK(hipGetLastError());
-      tb = need[1];
-      NEAT_CHECK(rocprim::radix_sort_keys(w.sort, tb, w.pkey, w.pskey, n_pair, 0u, 64u, st));
+      NEAT_PASS(sort_keys(w.sort, w.sort_bytes, w.pkey, w.pskey, n_pair, 0u, 64u, st));
       hipLaunchKernelGGL(wf3_link_kernel, dim3((unsigned)((pairs_max + WF3_WG - 1) / WF3_WG)), dim3(WF3_WG), 0, st, (const wf3_key*)w.pskey, pairs_max, lines3d, N, min_votes, reach,
                          sin_min, w.parent, w.lvotes);
     }
   }
-  hipLaunchKernelGGL(wf_flatten_kernel, grid1(n2, WF_WG), dim3(WF_WG), 0, st, n2, w.parent, w.last);
+  hipLaunchKernelGGL(uf_flatten_kernel, grid1(n2, UF_WG), dim3(UF_WG), 0, st, n2, w.parent, w.last);
   NEAT_CHECK(hipGetLastError());
   hipLaunchKernelGGL(wf3_vertex_scan_kernel, dim3(1), dim3(1024), 0, st, n2, (const int*)w.parent, w.vidx, n_vertices);
   hipLaunchKernelGGL(wf3_vertex_kernel, grid1(n2, WF3_WAVES), dim3(WF3_WG), 0, st, n2, (const int*)w.parent, (const int*)w.last, (const int*)w.vidx,
                      (const int*)w.lvotes, lines3d, vertices, degree, kind, votes, spread);
   hipLaunchKernelGGL(wf3_edge_key_kernel, grid1(N, WF3_WG), dim3(WF3_WG), 0, st, N, (const int*)w.parent, (const int*)w.vidx, w.ekey, w.eline, w.keep);
   NEAT_CHECK(hipGetLastError());
-  size_t tb = need[2];
-  NEAT_CHECK(rocprim::radix_sort_pairs(w.sort, tb, w.ekey, w.eskey, w.eline, w.esline, (size_t)N, 0u, 64u, st));
+  NEAT_PASS(sort_pairs(w.sort, w.sort_bytes, w.ekey, w.eskey, w.eline, w.esline, (size_t)N, 0u, 64u, st));
   hipLaunchKernelGGL(wf3_edge_pick_kernel, grid1(N, WF3_WG), dim3(WF3_WG), 0, st, N, (const wf3_key*)w.eskey, (const int*)w.esline, support, w.keep);
   hipLaunchKernelGGL(wf3_edge_scan_kernel, dim3(1), dim3(1024), 0, st, N, (const int*)w.keep, w.eidx, (const long long*)w.total, pairs_max, n_vertices,
                      n_edges);

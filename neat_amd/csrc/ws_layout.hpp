@@ -34,6 +34,11 @@ class WsCarver {
 };
 inline size_t ws_offset(const void* base, const void* p) { return (size_t)((uintptr_t)p - (uintptr_t)base); }
 
+// Room for rocprim's radix sort of a list of n keys (with or without values), fixed by n alone so that no workspace size depends on the
+// installed rocprim or on a device being present: its temporary keys and values (12 bytes an element at most), its
+// histograms and per-block look-back states.  A call asks rocprim and refuses (-2) if it wants more: sort_keys / sort_pairs in neat_aux.hip
+inline size_t sort_scratch_bytes(long long n) { return n > 0 ? (size_t)32 * (size_t)n + ((size_t)4 << 20) : 0; }
+
 // ---- lsap: float64 duals, then the int work arrays (LsapArgs in kernels_junction.hpp names them); neither region is padded ------------------
 struct LsapWs { double* d; int* i; size_t total; };
 inline void lsap_layout(void* ws, int nr, int nc, LsapWs* w) {
@@ -250,14 +255,15 @@ inline bool post_refine_layout(void* ws, long long n, long long mmax, int parse_
 }
 
 // snap, M = 2 n end points: box float [9] | counts int [2] (cells, peaks) | key, skey, head, flag, cnt, pidx, near int [M] each |
-// dist2 float [M] | idx int [n] | pkey, spkey 64-bit [n] each | the sort's temporary storage
+// dist2 float [M] | idx int [n] | pkey, spkey 64-bit [n] each | the sorts' temporary storage: sort_scratch_bytes of the larger list, M
 struct PostSnapWs {
   float* box; int *counts, *key, *skey, *head, *flag, *cnt, *pidx, *near; float* dist2; int* idx; unsigned long long *pkey, *spkey; void* sort;
-  size_t total;
+  size_t sort_bytes, total;
 };
-inline bool post_snap_layout(void* ws, long long n, long long G, size_t sort_bytes, PostSnapWs* w) {
+inline bool post_snap_layout(void* ws, long long n, long long G, PostSnapWs* w) {
   if (!post_grid_ok(G) || !post_counts_ok(n, 1, 0)) return false;
   const size_t M = 2 * (size_t)n;
+  w->sort_bytes = sort_scratch_bytes(2 * n);
   WsCarver c(ws);
   w->box = c.take<float>(9);
   w->counts = c.take<int>(2);
@@ -266,16 +272,14 @@ inline bool post_snap_layout(void* ws, long long n, long long G, size_t sort_byt
   w->idx = c.take<int>((size_t)n);
   w->pkey = c.take<unsigned long long>((size_t)n);
   w->spkey = c.take<unsigned long long>((size_t)n);
-  w->sort = c.take<char>(sort_bytes);
+  w->sort = c.take<char>(w->sort_bytes);
   w->total = c.end();
   return true;
 }
 
 // ---- ray casting: two buffers.  The tree: the status word, the boxes [2 L][6] of a heap of L = 2^k >= max(nf, 1) leaves, the sorted
 // triangles [nf][tri_stride].  The build's scratch: Morton keys and face ids with their sorted twins, the per-workgroup boxes (wg faces
-// each), the scene box, and room for the radix sort fixed by nf alone, so that the size does not depend on a device being present:
-// rocprim's temporary keys and values (12 bytes a triangle), its histograms and per-block look-back states; the build asks rocprim and
-// refuses if it wants more
+// each), the scene box, and the radix sort's room (sort_scratch_bytes)
 constexpr int RC_MAX_FACES = 1 << 24;
 struct RaycastWs {
   int L, per, tiles;
@@ -293,7 +297,7 @@ inline bool raycast_layout(void* bvh, void* ws, int nf, int wg, int tri_stride, 
   w->nodes = b.take<float>((size_t)2 * w->L * 6);
   w->tris = b.take<double>((size_t)nf * tri_stride);
   w->bvh_total = b.end();
-  w->sort_bytes = nf > 0 ? (size_t)32 * nf + ((size_t)4 << 20) : 0;
+  w->sort_bytes = sort_scratch_bytes(nf);
   WsCarver c(ws);
   w->key = c.take<unsigned long long>((size_t)nf);
   w->skey = c.take<unsigned long long>((size_t)nf);
@@ -421,8 +425,8 @@ inline bool scenegen_layout(void* ws, int V, int E, ScenegenWs* w) {
 // state: two status words, the half-edges kept, then chains, E, lines and junctions as the calls left them | ka, kb, va, vb [N] the
 // sorts' keys and values, in and out | per vertex: weld, vhead, vslot, rep (the weld), vstate, jflag, jmap | fn [nf][4] | mark, slot [M]
 // (flags and their scans: kinds, then chain heads) | elo, ehi, ekind, parent [M] | ckey [M] the edges in chain order, cstart [M + 1],
-// cinfo [M][4], cnl, coff [M] | lab, ltag [M] the lines before their sort | tile: the scans' tile sums | the radix sort's temporary
-// storage, fixed as raycast_layout fixes it; a call asks rocprim and refuses if it wants more
+// cinfo [M][4], cnl, coff [M] | lab, ltag [M] the lines before their sort | tile: the scans' tile sums | the radix sort's room
+// (sort_scratch_bytes)
 constexpr int CR_MAX_VERTS = 1 << 26;
 struct CreaseWs {
   int M; size_t N;
@@ -437,7 +441,7 @@ inline bool crease_layout(void* ws, int nv, int nf, int scan_tile, CreaseWs* w) 
   w->M = 3 * nf;
   const size_t M = (size_t)w->M, V = (size_t)nv;
   w->N = V > 2 * M ? V : 2 * M;
-  w->sort_bytes = (size_t)32 * w->N + ((size_t)4 << 20);
+  w->sort_bytes = sort_scratch_bytes((long long)w->N);
   WsCarver c(ws);
   w->state = c.take<int>(64);
   w->ka = c.take<unsigned long long>(w->N);
@@ -492,8 +496,7 @@ inline bool wf2d_layout(void* ws, int V, int S, int nmax, int tile, Wf2dWs* w) {
 // for pairs_max pair keys.  An end id is below 2 N < 2^24 and a view below 2^16, so a pair key (24 + 24 + 16 bits) fits 64 bits.
 // total: the pairs there are | rkey, rskey [2 S] the records and their sort | rcnt [2 S], roff [2 S] the pairs a record starts and
 // those before it | vview [NV] | pkey, pskey [pairs_max] | per end id: parent (then the label), last, vidx, lvotes [2 N] each | per line:
-// ekey, eskey, eline, esline (the edge keys and their sort), keep, eidx [N] | the radix sort's temporary storage, fixed as crease_layout
-// fixes it; a call asks rocprim and refuses if it wants more
+// ekey, eskey, eline, esline (the edge keys and their sort), keep, eidx [N] | the radix sort's room (sort_scratch_bytes)
 constexpr int WF3_MAX_ENDS = 1 << 24;
 inline bool wf3d_counts_ok(long long V, long long S, long long N, long long NV, long long pairs_max) {
   if (V < 0 || S < 0 || N < 0 || NV < 0 || pairs_max < 0 || V > WF_MAX_VIEWS || 2 * N >= WF3_MAX_ENDS) return false;
@@ -510,7 +513,7 @@ inline bool wf3d_layout(void* ws, int V, int S, int N, int NV, long long pairs_m
   if (!wf3d_counts_ok(V, S, N, NV, pairs_max)) return false;
   const size_t s2 = 2 * (size_t)S, n = (size_t)N, p = (size_t)pairs_max;
   w->n_sort = s2 > p ? (s2 > n ? s2 : n) : (p > n ? p : n);
-  w->sort_bytes = (size_t)32 * w->n_sort + ((size_t)4 << 20);
+  w->sort_bytes = sort_scratch_bytes((long long)w->n_sort);
   WsCarver c(ws);
   w->total = c.take<long long>(32);
   w->rkey = c.take<unsigned long long>(s2);

@@ -62,6 +62,9 @@ int main() {
     CHECK(ws_offset(nullptr, c.take<double>(3, 8)) == 0 && ws_offset(nullptr, c.take<int>(1, 4)) == 24 && c.end(4) == 28);
     CHECK(ws_offset(nullptr, c.take<char>(0)) == 256 && c.end() == 256 && ws_offset(nullptr, c.take<long long>(2, 8)) == 256 && c.end(8) == 272);
   }
+  // the radix sort's room: nothing for an empty list, 32 bytes an element and 4 MiB otherwise, no wrap at the largest list
+  CHECK(sort_scratch_bytes(-1) == 0 && sort_scratch_bytes(0) == 0 && sort_scratch_bytes(1) == 32 + ((size_t)4 << 20));
+  CHECK(sort_scratch_bytes(4097) == 32 * (size_t)4097 + ((size_t)4 << 20) && sort_scratch_bytes(0x7fffffffLL) == 32 * (size_t)0x7fffffff + ((size_t)4 << 20));
   // count bounds
   CHECK(post_counts_ok(0, 0, 0) && post_counts_ok(50000, 64, 32000) && post_counts_ok(0x7fffffffLL / 6, 1, 0));
   CHECK(!post_counts_ok(-1, 1, 1) && !post_counts_ok(1, -1, 1) && !post_counts_ok(1, 1, -1));
@@ -100,17 +103,17 @@ int main() {
     for (long long G : {2LL, 8LL, 512LL, 1024LL}) {
       CHECK(layout_ok([&](void* b, Regions& r, size_t& t) {
         PostSnapWs w;
-        if (!post_snap_layout(b, n, G, 777, &w)) return false;
+        if (!post_snap_layout(b, n, G, &w) || w.sort_bytes != sort_scratch_bytes(2 * n)) return false;
         const size_t M4 = (size_t)(8 * n);
         r = {{w.box, 36, 256}, {w.counts, 8, 256}, {w.key, M4, 256}, {w.skey, M4, 256}, {w.head, M4, 256}, {w.flag, M4, 256}, {w.cnt, M4, 256},
              {w.pidx, M4, 256}, {w.near, M4, 256}, {w.dist2, M4, 256}, {w.idx, (size_t)(4 * n), 256}, {w.pkey, (size_t)(8 * n), 256},
-             {w.spkey, (size_t)(8 * n), 256}, {w.sort, 777, 256}};
+             {w.spkey, (size_t)(8 * n), 256}, {w.sort, w.sort_bytes, 256}};
         t = w.total;
         return true;
       }));
     }
     PostSnapWs ws;
-    CHECK(!post_snap_layout(nullptr, n, 2048, 0, &ws) && !post_snap_layout(nullptr, n, 1, 0, &ws));
+    CHECK(!post_snap_layout(nullptr, n, 2048, &ws) && !post_snap_layout(nullptr, n, 1, &ws));
 
     // ---- lsap (n rows against 1, 8 and n columns; float64 first, 8-byte aligned; ints behind them, 4-byte aligned), dbscan
     for (long long nc : {1LL, 8LL, n}) {
@@ -453,7 +456,7 @@ int main() {
   PostRefineWs wr;
   CHECK(!post_refine_layout(nullptr, -1, 1, PARSE_TILE, &wr) && !post_refine_layout(nullptr, 1, -1, PARSE_TILE, &wr));
   PostSnapWs wsn;
-  CHECK(!post_snap_layout(nullptr, -1, 8, 0, &wsn));
+  CHECK(!post_snap_layout(nullptr, -1, 8, &wsn));
   ParseGroupWs wg;
   CHECK(!parse_group_layout(nullptr, -1, 1, PARSE_TILE, &wg) && !parse_group_layout(nullptr, 1, -1, PARSE_TILE, &wg));
   ParseVoteWs wv;

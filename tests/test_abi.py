@@ -201,7 +201,8 @@ def test_tool_workspace_sizes_and_offsets_are_pinned():
     recorded from the library before the layouts moved to csrc/ws_layout.hpp: arguments around every tile size (0, 1, 255, 256, 257,
     4096, 4097; grids of 2048 nodes, one tile of the mesh, and of 2050, the nearest above that three axes of two nodes and more can
     make) and arguments each query refuses (0, or None for neat_show_ws_layout's -1).  The queries touch no device.
-    neat_post_snap_ws_bytes is pinned where it does not include rocprim's own temporary storage (no lines, refusals)."""
+    neat_post_snap_ws_bytes with lines was added when its sort region became sort_scratch_bytes(2 n): those three values are worked out
+    by hand from post_snap_layout's region list, every region rounded up to 256 bytes."""
     import json
     from neat_amd import _lib
     lib = _lib.lib()

@@ -303,6 +303,17 @@ def test_snap_random_soup(G, n):
 
 
 @pytest.mark.gpu
+def test_snap_sorts_in_room_sized_by_the_count_alone():
+    """The sort region is sort_scratch_bytes(2 n), whatever rocprim would ask for: at n = 1 that is 4 MiB for a sort of two int keys and
+    one of a single 64-bit key, and at n = 300 with unique on both sorts run in it."""
+    rng = np.random.default_rng(7)
+    verts = rng.uniform(-1, 1, (12, 3))
+    for n, kw in ((1, {}), (300, {"unique": True})):
+        lines = (verts[rng.integers(0, 12, (n, 2))] + rng.normal(0, 0.01, (n, 2, 3))).astype(np.float32)
+        check_snap(lines, 64, **kw)
+
+
+@pytest.mark.gpu
 def test_snap_cases():
     from neat_amd import post
     # end points on half-integer cells (G = 5 over [0, 4]: delta = 1): 0.5 -> 0, 1.5 -> 2, 2.5 -> 2, 3.5 -> 4
