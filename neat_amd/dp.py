@@ -109,12 +109,11 @@ class FlatGradBucket:
     def all_reduce_mean(self, flat_grad=None):
         """grad_i <- mean over ranks of grad_i (a parameter with no gradient on this rank contributes zeros).
         `flat_grad`: the gradients already live in this flat buffer -> reduced in place."""
-        if not dist.is_initialized() or (dist.get_world_size(self.group) == 1 and not self.force_collective):
+        if not self.active():
             return
-        world = dist.get_world_size(self.group)
         if flat_grad is not None:
             dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=self.group)
-            flat_grad.mul_(1.0 / world)
+            flat_grad.mul_(1.0 / dist.get_world_size(self.group))
             return
         self.pack()
         self.reduce_packed()

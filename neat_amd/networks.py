@@ -272,6 +272,28 @@ def _to_device_async(t, device, site=None):
     return out
 
 
+class DrawSite:
+    """One host-made input of a captured step (neat_amd.train.Trainer): `draw()` makes the next CPU value, `dev` is the persistent device
+    tensor the graph reads, `ring` four pinned staging buffers, each with the event of the launch that last read it.  A site is made by
+    adding it to its layout's registry, whose order IS the refill order: the forward's sites as the eager forward draws, then the trainer's."""
+
+    def __init__(self, registry, name, draw, dev):
+        self.draw, self.dev, self.ring = draw, dev, None
+        registry[name] = self
+
+    def stage(self, pos):
+        """A fresh draw in staging buffer `pos` of the ring -> (pinned buffer, its event: to be recorded behind the launch that reads it)."""
+        if self.ring is None:
+            # all four staging buffers at once, on the site's first refill (inside Trainer.capture()): pinned allocations cost
+            # milliseconds the first time a process asks for them -- grown one per replay they landed in the first timed
+            # replays of a fresh layout (sampler step: 5.2 instead of 4.1 ms over the first 20 replays)
+            self.ring = [(torch.empty_like(self.dev, device="cpu").pin_memory(), torch.cuda.Event()) for _ in range(4)]
+        pinned, ev = self.ring[pos % 4]
+        ev.synchronize()                    # the copy that last used this staging buffer is long done
+        pinned.copy_(self.draw())
+        return pinned, ev
+
+
 def _device_copy(obj, attr, device):
     """Device-resident copy of a per-view CPU tensor attribute, made once (a pageable H2D copy stalls the host)."""
     cache = obj.__dict__.setdefault("_device_cache", {})
@@ -625,16 +647,14 @@ class VolSDFNetwork(_HipModule):
 
     def _cpu_random(self, name, draw, device):
         """Randoms are drawn on the CPU (the reference's RNG stream).  Normally: draw + asynchronous pinned copy.  With
-        `static_randoms` set (a dict; HIP-graph capture / replay, neat_amd.train.Trainer): the forward reads a persistent
-        device tensor per draw site, which the trainer refills (same draw order) before every replay."""
+        `static_randoms` set (a layout's registry of DrawSites; HIP-graph capture / replay, neat_amd.train.Trainer): the forward reads a
+        persistent device tensor per draw site, which the trainer refills (same draw order) before every replay."""
         if self.static_randoms is None:
             return _to_device_async(draw(), device, name)
-        slot = self.static_randoms.get(name)
-        if slot is None:
-            t = draw()
-            slot = {"draw": draw, "dev": t.to(device), "order": len(self.static_randoms)}
-            self.static_randoms[name] = slot
-        return slot["dev"]
+        site = self.static_randoms.get(name)
+        if site is None:
+            site = DrawSite(self.static_randoms, name, draw, draw().to(device))
+        return site.dev
 
     def _eikonal_points(self, n_rays, cam_loc, ray_dirs, z_eik, junctions):
         """Eikonal points: uniform in the bounding cube + one near-surface sample per ray (rend_a :515-527):

@@ -36,22 +36,46 @@ class FlatAdam(torch.optim.Optimizer):
         # step-dependent numbers of a CAPTURED launch (capture_step): (lr / bias_correction1, 1 / sqrt(bias_correction2)) per tensor, in
         # device memory; refreshed by the trainer before every replay with next_coef()
         self.coef = torch.zeros(2 * len(sizes), device=dev)
+        self._realias()                        # the module's parameters now alias the flat buffer
         for i, p in enumerate(self._params):
             off, n = self._offsets[i], sizes[i]
-            view = self.flat_param[off:off + n].view(p.shape)
-            view.copy_(p.data)
-            p.data = view                      # the module's parameters now alias the flat buffer
             self.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.exp_avg[off:off + n].view(p.shape),
                              "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape)}
+
+    def _grad_pointers(self, flat_grad, normalise):
+        """The kernel's gradient pointer table -> (table, has, keep); has[i]: parameter i has a gradient.  flat_grad given: all have one,
+        at their offsets in that buffer (one table per buffer, cached on its address).  None: the .grad tensors as they are now; one that
+        is not contiguous float32 (not the usual case) is normalised into `keep` (alive until the caller has launched), or refused."""
+        n = len(self._params)
+        if flat_grad is not None:
+            cache = getattr(self, "_flat_ptrs", None)
+            if cache is None or cache[0] != flat_grad.data_ptr():
+                tab = (ctypes.c_void_p * n)()
+                for i in range(n):
+                    tab[i] = flat_grad.data_ptr() + 4 * self._offsets[i]
+                cache = self._flat_ptrs = (flat_grad.data_ptr(), tab)
+            return cache[1], [True] * n, []
+        tab, has, keep = (ctypes.c_void_p * n)(), [], []
+        for i, p in enumerate(self._params):
+            g = p.grad
+            if g is not None and (g.dtype != torch.float32 or not g.is_contiguous()):
+                if not normalise:
+                    raise RuntimeError("FlatAdam.capture_step: contiguous float32 gradients only")
+                g = g.float().contiguous()
+                keep.append(g)
+            if g is not None:
+                tab[i] = g.data_ptr()
+            has.append(g is not None)
+        return tab, has, keep
 
     @torch.no_grad()
     def step(self, closure=None, flat_grad=None):
         """flat_grad: ALL gradients live in this flat fp32 buffer, laid out like the parameters (dp.FlatGradBucket.flat after the
-        all-reduce): the pointer table is built once per buffer, no per-parameter host work in the step.
+        all-reduce).
         Semantics of this (data-parallel) form = DistributedDataParallel's: EVERY parameter steps, a parameter that had no gradient on
         any rank steps with the zeros the bucket packed for it (its moments decay).  That is deliberate -- which parameters have a
         gradient is a property of one rank's batch (e.g. no matched junction on this view), and ranks that skipped different
-        parameters would drift apart; the pointer-table form below keeps torch.optim.Adam's single-process rule (no gradient: no
+        parameters would drift apart; the per-parameter .grad form keeps torch.optim.Adam's single-process rule (no gradient: no
         step, no step count)."""
         loss = None
         if closure is not None:
@@ -59,29 +83,12 @@ class FlatAdam(torch.optim.Optimizer):
                 loss = closure()
         group = self.param_groups[0]
         self._realias()
-        keep = []                                  # non-contiguous / non-fp32 gradients are normalised first (not the usual case)
-        if flat_grad is not None:
-            if flat_grad.numel() != self.numel or flat_grad.dtype != torch.float32 or flat_grad.device != self.flat_param.device:
-                raise ValueError("FlatAdam.step(flat_grad=...): one fp32 buffer with the parameters' layout on their device")
-            cache = getattr(self, "_flat_ptrs", None)
-            if cache is None or cache[0] != flat_grad.data_ptr():
-                tab = (ctypes.c_void_p * len(self._params))()
-                for i in range(len(self._params)):
-                    tab[i] = flat_grad.data_ptr() + 4 * self._offsets[i]
-                cache = self._flat_ptrs = (flat_grad.data_ptr(), tab)
-            ptrs = cache[1]
-            for i in range(len(self._params)):
-                self._steps[i] += 1
-        else:
-            ptrs = (ctypes.c_void_p * len(self._params))()
-            for i, p in enumerate(self._params):
-                g = p.grad
-                if g is None:
-                    continue
-                if g.dtype != torch.float32 or not g.is_contiguous():
-                    g = g.float().contiguous()
-                    keep.append(g)
-                ptrs[i] = g.data_ptr()
+        if flat_grad is not None and (flat_grad.numel() != self.numel or flat_grad.dtype != torch.float32
+                                      or flat_grad.device != self.flat_param.device):
+            raise ValueError("FlatAdam.step(flat_grad=...): one fp32 buffer with the parameters' layout on their device")
+        ptrs, has, keep = self._grad_pointers(flat_grad, normalise=True)      # (keep: alive until the launch below is issued)
+        for i, h in enumerate(has):
+            if h:
                 self._steps[i] += 1
         b1, b2 = group["betas"]
         P = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -101,20 +108,7 @@ class FlatAdam(torch.optim.Optimizer):
         `self.coef` with next_coef(has) before every replay.  Nothing is stepped by this call (a capture does not execute)."""
         group = self.param_groups[0]
         self._realias()
-        tab = (ctypes.c_void_p * len(self._params))()
-        has = []
-        for i, p in enumerate(self._params):
-            if flat_grad is not None:
-                tab[i] = flat_grad.data_ptr() + 4 * self._offsets[i]
-                has.append(True)
-            else:
-                g = p.grad
-                ok = g is not None and g.dtype == torch.float32 and g.is_contiguous()
-                if g is not None and not ok:
-                    raise RuntimeError("FlatAdam.capture_step: contiguous float32 gradients only")
-                if ok:
-                    tab[i] = g.data_ptr()
-                has.append(ok)
+        tab, has, _ = self._grad_pointers(flat_grad, normalise=False)     # (a normalised copy would not be the tensor the graph writes)
         b1, b2 = group["betas"]
         P = lambda t: ctypes.c_void_p(t.data_ptr())
         _lib.check(_lib.lib().neat_adam_step_coef(P(self.flat_param), tab, self._offsets, len(self._params), P(self.exp_avg), P(self.exp_avg_sq),

@@ -30,7 +30,7 @@ def timed(fn, n=30):
 
 print("graph.replay() only      : %.3f ms" % timed(entry.graph.replay))
 print("replay + Adam + scheduler: %.3f ms" % timed(lambda: tr._finish_step(entry)))
-print("refill + replay + Adam   : %.3f ms" % timed(lambda: (tr._refill_randoms(entry), tr._finish_step(entry))))
+print("refill + replay + Adam   : %.3f ms" % timed(lambda: (tr._stage(entry), tr._finish_step(entry))))
 print("Trainer.step             : %.3f ms" % timed(lambda: tr.step(inp, gt)))
 lr = tr.optimizer.param_groups[0]["lr"]
 tr.optimizer.param_groups[0]["lr"] = 0.0
